@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """bench.py -- MCRaT's photon loop on the BASELINE.json workload (configs[1]).
 
-    python bench.py                                   # 1 GPU, defaults
+    python bench.py                                   # 1 GPU, defaults: the headline alone
+    python bench.py --full                            # ... and every figure beside it (roofline, other shapes, CPU baselines, ...)
+    python bench.py --dump-outputs DIR                # ... and what the timed path computed in its last step, as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Workload: synthetic 2-D FLASH-like cylindrical GRB-jet frame (16 384 leaf blocks = 1 048 576 cells, Lundman
@@ -18,9 +20,9 @@ timed region.  Two run shapes of the same loop (Src/mcrat.c:761-851):
                           (step kernel, HBM-bound) and scatters one.  A *step* is one pass.  This is the shape
                           the HBM roofline is priced on.
 
-Prints ONE JSON line (rank 0): `value` = scatter events per second of the selected mode (whole job), plus
-photon-steps/s, the roofline object of that mode's dominant kernel, a short measurement of the other mode, and
-the CPU baseline (oracle/ = faithful C restatement of the reference, one host core, bounded sample, same shape).
+Prints ONE JSON line (rank 0): `value` = scatter events per second of the selected mode (whole job), `ms_per_step`,
+photon-steps/s; with --full also the roofline object of that mode's dominant kernel, a short measurement of the other
+mode, and the CPU baseline (oracle/ = faithful C restatement of the reference, one host core, bounded sample, same shape).
 """
 
 import argparse
@@ -40,6 +42,8 @@ import numpy as np  # noqa: E402
 ALGORITHMIC_BYTES_PER_PHOTON_STEP = 110      # SURVEY.md section 8(d) / BASELINE.md section 2
 HBM_PEAK_GBS = 8000.0                        # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 SEED = 0x4D435261
+DUMP_BYTES = 64 << 20                        # --dump-outputs: at most this much in all
+DUMP_RECORDS = 1 << 18                       # photons sampled into --dump-outputs (23 float64 columns each: 48 MB)
 
 
 def committed_traffic(pattern):
@@ -56,6 +60,54 @@ def committed_traffic(pattern):
 
 def sub_photons(ph, lo, hi):
     return {k: (v[lo:hi].copy() if isinstance(v, np.ndarray) else v) for k, v in ph.items()}
+
+
+def dump_arrays(path, arrays):
+    """--dump-outputs: every array as path/<name>.npy in float64 (a record's `type` as its character code)"""
+    os.makedirs(path, exist_ok=True)
+    out = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    out = {k: a.view(np.uint8) if a.dtype.kind == "S" else a for k, a in out.items()}
+    total = sum(8 * a.size for a in out.values())
+    if total > DUMP_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte budget" % (total, DUMP_BYTES))
+    for k, a in out.items():
+        np.save(os.path.join(path, k + ".npy"), a.astype(np.float64))
+
+
+def photon_columns(records):
+    """struct photon records -> {photons_<field>: column}"""
+    return {"photons_" + f: records[f] for f in records.dtype.names}
+
+
+def sample_photons(cols):
+    """a fixed sample of DUMP_RECORDS photons of SoA columns (the same indices for the same photon count)"""
+    n = len(cols["p0"])
+    idx = np.sort(np.random.default_rng(SEED).choice(n, DUMP_RECORDS, replace=False)) if n > DUMP_RECORDS else np.arange(n)
+    out = {"photons_" + f: np.asarray(v)[idx] for f, v in cols.items()}
+    out["photons_index"] = idx
+    return out
+
+
+def sample_lists(views):
+    """views: the lists of the rank pool(s) in list order.  The whole lists of a fixed sample of them (the first ones of a seeded
+    permutation that hold DUMP_RECORDS photons, in list order) -> photons_<field> and photons_list (the list of every record)"""
+    order = np.random.default_rng(SEED).permutation(len(views))
+    take, have = [], 0
+    for r in order:
+        if have >= DUMP_RECORDS:
+            break
+        take.append(int(r))
+        have += views[r].n
+    take.sort()
+    recs = [views[r].get_photons_aos() for r in take]
+    out = photon_columns(np.concatenate(recs))
+    out["photons_list"] = np.repeat(np.array(take), [len(a) for a in recs])
+    return {k: v[:DUMP_RECORDS] for k, v in out.items()}
+
+
+def summary_columns(summaries):
+    """the per-list reductions of a rank pool (mcrat_hip_pool_summaries) -> {list_<field>: one value per list}"""
+    return {"list_" + k: np.array([getattr(s, k) for s in summaries], dtype=np.float64) for k, _ in summaries[0]._fields_}
 
 
 def cpu_baseline_list(frame, ph, cfg, n_sample, iters):
@@ -297,6 +349,11 @@ def bench_cfg5(args):
     loop_ms, loop_launches = max(x[0] for x in loop_prof), sum(x[1] for x in loop_prof)     # (pools side by side: the longest pool's loop time)
     loop_gbs = ALGORITHMIC_BYTES_PER_PHOTON_STEP * tot[7] / (loop_ms * 1e-3) / 1e9 if loop_ms > 0 else 0.0
     loop_gbs_ref_def = ALGORITHMIC_BYTES_PER_PHOTON_STEP * tot[1] / (loop_ms * 1e-3) / 1e9 if loop_ms > 0 else 0.0
+    if args.dump_outputs:
+        # the lists as the last timed scatter frame left them (a fixed sample of whole lists) and every list's reductions
+        out = sample_lists([P.pool.pool_rank(r - P.lo, r) for P in pools for r in range(P.lo, P.hi)])
+        out.update(summary_columns([s for P in pools for s in P.pool.pool_summaries()]))
+        dump_arrays(args.dump_outputs, out)
     cpu = None
     if not args.no_cpu_baseline:
         try:
@@ -415,7 +472,17 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--shared-clock-rounds", type=int, default=300,
                     help="also time this many rounds of the one-list-over-all-GPUs mode (0: skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the roofline passes, strong scaling, FAST mode, the list-size sweep, the other "
+                         "run shape, the PCIe-inclusive and host-driver figures, ingest, the hot frame, the CPU baselines and the shared-clock line "
+                         "(each still subject to its own option above).  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float64): the photon "
+                         "records of a fixed sample of lists (or photons), at most %d MB in all, and the per-list results (rank 0)" % (DUMP_BYTES >> 20))
     args = ap.parse_args()
+    if not args.full:
+        # the headline alone: every extra below hangs off one of these three (the roofline passes off --full itself)
+        args.other_mode, args.shared_clock_rounds, args.no_cpu_baseline = 0, 0, True
     steps = args.steps if args.steps > 0 else (20 if args.mode == "ranks" else 2000)
     warmup = args.warmup if args.warmup >= 0 else (2 if args.mode == "ranks" else 50)
     if args.config == "cfg5":
@@ -487,6 +554,25 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
+    def dump_pools(pools, last_frame=None):
+        """--dump-outputs of the rank pools `pools` (in list order) as the last timed frame left them; last_frame: that frame's FrameStats per list"""
+        if not args.dump_outputs or rank != 0:
+            return
+        out = sample_lists([p.views[j] for p in pools for j in range(p.n_pool_ranks)])
+        out.update(summary_columns([s for p in pools for s in p.pool_summaries()]))
+        if last_frame is not None:
+            out.update({"list_last_frame_" + k: np.array([getattr(s, k) for s in last_frame], dtype=np.float64)
+                        for k in ("iterations", "photon_steps", "frame_scatt_cnt", "time_now")})
+        dump_arrays(args.dump_outputs, out)
+
+    def dump_photons(e, st):
+        """--dump-outputs of one list's photons (a fixed sample) and its loop statistics after the timed passes / rounds"""
+        if not args.dump_outputs or rank != 0:
+            return
+        out = sample_photons(e.get_photons())
+        out.update({"frame_" + k: np.array([getattr(st, k)], dtype=np.float64) for k in ("iterations", "frame_scatt_cnt", "time_now")})
+        dump_arrays(args.dump_outputs, out)
+
     def make_engine(mode, profile=False, per_sync=None, photons=None, lists=None, stream_base=None, stream=stream, share_from=None, layout=None):
         if mode == "ranks":
             # a rank pool: every list its own length, stream and clock, all lists propagated by one launch (mcrat_hip_pool_*)
@@ -527,9 +613,9 @@ def main():
             it += st.iterations
         return ev, ps, it
 
-    def run_pooled(l0, l1, k_frames, k_warm, photons=None, stream_base=None, layout=None, n_pools=None):
+    def run_pooled(l0, l1, k_frames, k_warm, photons=None, stream_base=None, layout=None, n_pools=None, dump=False):
         """the lists [l0, l1) as --pools rank pools on their own HIP streams, a host thread each; k_warm untimed frames, then k_frames frames
-        timed between two barriers -> (events, photon_steps, passes, seconds)"""
+        timed between two barriers -> (events, photon_steps, passes, seconds); dump: --dump-outputs of the lists after the last frame"""
         import threading
         pools = max(1, min(n_pools if n_pools else (int(args.pools) if args.pools > 0 else 3), l1 - l0))
         engines, keep = [], []
@@ -563,13 +649,16 @@ def main():
             th.join()
         sync()
         dt = time.perf_counter() - t0
+        if dump:
+            dump_pools(engines)
         for e in reversed(engines):           # (the pools that read engines[0]'s frame go first)
             e.close()
         return sum(x[0] for x in tot), sum(x[1] for x in tot), sum(x[2] for x in tot), dt
 
-    def run_queued(l0, l1, k_frames, k_warm, photons=None, stream_base=None, layout=None):
+    def run_queued(l0, l1, k_frames, k_warm, photons=None, stream_base=None, layout=None, dump=False):
         """the lists [l0, l1) as ONE rank pool, all k_frames frames in ONE launch (the frame queue): every frame of a list starts from the resident
-        snapshot with the frame's seed, exactly the frames run_ranks gives it one launch at a time -> (events, photon_steps, passes, seconds, launch_ms)"""
+        snapshot with the frame's seed, exactly the frames run_ranks gives it one launch at a time -> (events, photon_steps, passes, seconds, launch_ms);
+        dump: --dump-outputs of the lists as the last frame left them"""
         e = make_engine("ranks", profile=True, photons=photons, lists=(l0, l1), stream_base=stream_base, layout=layout)
         e.snapshot_photons()
         R = l1 - l0
@@ -594,10 +683,12 @@ def main():
         dt = time.perf_counter() - t0
         a = np.frombuffer(st, dtype=np.dtype([("it", "<i8"), ("ps", "<i8"), ("sc", "<i8"), ("rest", "V%d" % (C.sizeof(engine.FrameStats) - 24))]))
         launch_ms = (st[0].step_kernel_ms, int(st[0].step_kernel_launches))      # summed duration and number of the loop kernel's launches in the timed call
+        if dump:
+            dump_pools([e], [st[(k_frames - 1) * R + r] for r in range(R)])
         e.close()
         return int(a["sc"].sum()), int(a["ps"].sum()), int(a["it"].sum()), dt, launch_ms
 
-    def measure_ranks(k_frames, k_warm, with_roofline):
+    def measure_ranks(k_frames, k_warm, with_roofline, dump=False):
         # The adopted ranks never wait for each other (the reference's MPI ranks are asynchronous processes), so they need not share one
         # launch either: --pools P deals the lists out to P rank pools, each on its own HIP stream and driven by its own host thread
         # (as P processes sharing the GPU would be).  A step is still one hydro frame for ALL lists; what changes is that a pool whose last
@@ -606,9 +697,9 @@ def main():
         # (frame, list) item: a list that is through frame f starts f + 1 as soon as a workgroup slot is free (mcrat_hip_pool_run_frames).
         queue_launch_ms = None
         if args.launch_shape == "queue":
-            ev, ps, it, dt, queue_launch_ms = run_queued(0, n_lists, k_frames, k_warm)
+            ev, ps, it, dt, queue_launch_ms = run_queued(0, n_lists, k_frames, k_warm, dump=dump)
         else:
-            ev, ps, it, dt = run_pooled(0, n_lists, k_frames, k_warm)
+            ev, ps, it, dt = run_pooled(0, n_lists, k_frames, k_warm, dump=dump)
         nr = n_lists
         roof = None
         if with_roofline:
@@ -692,7 +783,7 @@ def main():
             ev, ps, it, dt = run_pooled(lo, hi, k_frames, k_warm, photons=common, stream_base=0)
         return ev, ps, dt, hi - lo
 
-    def measure_list(k_steps, k_warm, prof_steps):
+    def measure_list(k_steps, k_warm, prof_steps, dump=False):
         e = make_engine("list", per_sync=max(50, min(500, k_steps)))
         e.begin_frame(SEED, 0.0, remaining)
         w = e.run(k_warm) if k_warm > 0 else None          # includes the forced re-location pass
@@ -705,6 +796,8 @@ def main():
         dt = time.perf_counter() - t0
         if st.iterations - it0 != k_steps:
             raise SystemExit("the frame ended after %d of %d timed passes; lower --steps" % (st.iterations - it0, k_steps))
+        if dump:
+            dump_photons(e, st)
         roof = None
         if prof_steps > 0:
             # the step kernel's launches bracketed by HIP events, in a separate pass that continues the same frame
@@ -736,7 +829,7 @@ def main():
                     relocations_per_pass=(st.num_photons_find_new_element - rel0) / k_steps,
                     kn_rejections=st.kn_rejections, rescans=st.rescans)
 
-    def measure_shared(k_rounds, k_warm):
+    def measure_shared(k_rounds, k_warm, dump=False):
         """ONE list of world x n photons with one clock, its slots spread over the GPUs (mcrat_amd/shared_clock.py):
         per round every GPU steps its own slots, the 736-B proposals are all-gathered (RCCL), and every GPU walks the
         merged candidates.  A round decides one loop pass unless it ends undecided (midpass, Klein-Nishina chains)."""
@@ -759,17 +852,19 @@ def main():
             dt = time.perf_counter() - t0
         if done:
             raise SystemExit("the frame ended inside the timed rounds; lower the round count")
+        if dump:
+            dump_photons(e, st)
         passes = st.iterations - w.iterations
         e.close()
         return dict(events=st.frame_scatt_cnt - w.frame_scatt_cnt, photon_steps=n * passes, passes=passes, seconds=dt,
                     roofline=None, midpass_rounds=st.rescans - w.rescans, rounds=k_rounds)
 
     if args.mode == "ranks":
-        main_res = measure_ranks(steps, warmup, rank == 0)
+        main_res = measure_ranks(steps, warmup, rank == 0 and args.full, dump=True)
     elif args.mode == "list":
-        main_res = measure_list(steps, warmup, args.profile_steps if rank == 0 else 0)
+        main_res = measure_list(steps, warmup, args.profile_steps if rank == 0 and args.full else 0, dump=True)
     else:
-        main_res = measure_shared(steps, warmup)
+        main_res = measure_shared(steps, warmup, dump=True)
 
     t_max, events_all, steps_all = main_res["seconds"], float(main_res["events"]), float(main_res["photon_steps"])
     if dist is not None:

@@ -4,7 +4,10 @@ The layout of mc_proc_<rank>.h5 as the reference's printPhotons writes it (SURVE
 Src/mcrat_io.c -- the reference cannot be run here (GSL is absent), but what it asks of the HDF5 library is in its text: the file and
 group name formats, and for every H5Dcreate2 inside printPhotons the dataset name, the memory type, the dataspace / creation-property
 variables and the compile-time switch it sits under; the chunk and maximum dimensions those variables are made with; and the append
-idiom (H5Dset_extent to old + new, hyperslab at offset old).  Only these facts are stored -- no source text."""
+idiom (H5Dset_extent to old + new, hyperslab at offset old).  Only these facts are stored -- no source text.
+
+    python tests/golden/make_h5_listing.py --check     compares a fresh extraction with the committed file instead of writing it
+"""
 import json
 import os
 import re
@@ -14,7 +17,7 @@ REF = "/root/reference/Src/mcrat_io.c"
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
-def main():
+def main(check=False):
     src = open(REF).read()
     start = src.index("void printPhotons(")
     end = src.index("\nint saveCheckpoint(")
@@ -62,13 +65,19 @@ def main():
            "file_name": {"format": names.group(1), "prefix": names.group(2), "suffix": names.group(3)},
            "group_name": {"format": group.group(1), "of": "frame"},
            "declarations": decl, "dataspaces": spaces, "chunking": chunks, "datasets": datasets, "append": append}
-    with open(os.path.join(HERE, "mc_proc_listing.json"), "w") as f:
-        json.dump(out, f, indent=1)
-        f.write("\n")
+    path, text = os.path.join(HERE, "mc_proc_listing.json"), json.dumps(out, indent=1) + "\n"
+    if check:
+        with open(path) as f:
+            if f.read() != text:
+                sys.exit("mc_proc_listing.json is not what the reference gives today: run this script without --check")
+        print("mc_proc_listing.json is current")
+        return
+    with open(path, "w") as f:
+        f.write(text)
     print("%d datasets:" % len(datasets), " ".join(d["name"] + ("[%s]" % d["switch"] if d["switch"] else "") for d in datasets))
 
 
 if __name__ == "__main__":
     if not os.path.exists(REF):
         sys.exit("the reference is not here: the committed mc_proc_listing.json stands")
-    main()
+    main(check="--check" in sys.argv[1:])

@@ -10,7 +10,7 @@ from mcrat_amd import synth
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # the reference's sample_mc.par content is restated here as the grammar's known-answer case
-# (same positional layout as /root/reference/sample_mc.par; values chosen for the test)
+# (same positional layout as the reference's sample_mc.par, tests/golden/sample_mc.par; values chosen for the test)
 SAMPLE = """[Hydro/MHD Simulation Block]
 
 5.               # Number of frames per second of hydro simulation
@@ -107,9 +107,7 @@ def test_hot_cross_section_file(host, tmp_path):
 
 
 def test_reference_sample_file_parses_if_present(host):
-    ref = "/root/reference/sample_mc.par"          # not present on the GPU box; read as data, not imported
-    if not os.path.exists(ref):
-        pytest.skip("reference tree not mounted here")
+    ref = os.path.join(ROOT, "tests", "golden", "sample_mc.par")      # the reference's own sample_mc.par, stored as a data fixture
     p = McPar()
     assert host.mcrat_host_read_mcpar(ref.encode(), C.byref(p)) == 0
     assert p.fps == 5.0 and p.last_frame == 3000 and p.n_theta_j == 3 and p.min_photons == 1000 and p.max_photons == 5000

@@ -8,7 +8,7 @@ i=0
 for ctrs in "SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE" "InstrFetchLatency" "SQ_IFETCH SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_VALU"; do
   i=$((i+1))
   echo "== pass $i ($ctrs)"
-  rocprofv3 --pmc $ctrs --kernel-trace --output-format csv -d $out/p$i -- python3 bench.py --steps 5 --warmup 1 --other-mode 0 --host-driver 0 --no-cpu-baseline --shared-clock-rounds 0 $EXTRA > $out/p$i.json 2> $out/p$i.err; echo "exit=$?"
+  rocprofv3 --pmc $ctrs --kernel-trace --output-format csv -d $out/p$i -- python3 bench.py --steps 5 --warmup 1 --other-mode 0 --host-driver 0 --no-cpu-baseline --shared-clock-rounds 0 --full $EXTRA > $out/p$i.json 2> $out/p$i.err; echo "exit=$?"
 done
 find $out -name "*kernel_trace.csv" -delete
 find $out -name "*agent_info.csv" -delete
