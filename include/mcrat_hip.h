@@ -597,8 +597,12 @@ int mcrat_hip_pool_layout(const mcrat_hip_ctx *pool, int *n_ranks, int *slots_pe
  * frame; the contexts keep their frames staged while the call runs) -- a real run stages frame f + 1 for the slab the photons can reach from frame
  * f (phMinMax widened by c / fps) before the launch: a list in frame f + 1 then finds its photons in the cells of THAT frame, exactly as after
  * mcrat_hip_share_hydro(pool, hydro[f + 1]) + one launch per frame.  stats: [n_frames * n_ranks], what
- * mcrat_hip_pool_frame_stats would have reported after each frame (lists that sat a frame out: zeros).  Not with the cyclo-synchrotron switch (its
- * hook needs the host between passes).  Afterwards the pool is as after the last frame's mcrat_hip_run. */
+ * mcrat_hip_pool_frame_stats would have reported after each frame (lists that sat a frame out: zeros); stats[0] also carries the whole call's totals:
+ * step_kernel_ms and step_kernel_launches (a context created with profile = 1) and, with TAU_CALCULATION == TABLE, table_fallbacks -- summed over the
+ * counters of the pool and of every context named in hydro (each frame's look-ups count on the context its frame is staged on; the call clears them all
+ * first).  A list that opens a frame with remaining_time <= 0 runs no pass in it but is still restored (restore_each_frame) and captured
+ * (capture_frames) as in any other frame.  Not with the cyclo-synchrotron switch (its hook needs the host between passes).  Afterwards the pool is
+ * as after the last frame's mcrat_hip_run. */
 typedef struct mcrat_hip_frame_plan {
     int n_frames;
     int chain_clock;

@@ -2969,6 +2969,10 @@ extern "C" int mcrat_hip_pool_run_frames(mcrat_hip_ctx *c, const mcrat_hip_frame
     tq_b = clock_us();
     HIPCHK(c, hipMemsetAsync(db + off_rec, 0, sizeof(LoopState) * N, c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_table_fallbacks, 0, sizeof(int), c->stream));
+    // TAU_CALCULATION == TABLE: a frame's off-table look-ups count on the context its hydro frame is staged on (HydroDev::table_fallbacks); every
+    // such counter starts the call from zero and the call reports their sum
+    for (const HydroDev &h : hyv)
+        if (c->kc.table && h.table_fallbacks) HIPCHK(c, hipMemsetAsync(h.table_fallbacks, 0, sizeof(int), c->stream));
     if (!c->rank_block_fixed) { choose_rank_block(c); c->rank_block_fixed = true; }
     tq_c = clock_us();
     FrameQueueDev fq{};
@@ -3175,6 +3179,19 @@ extern "C" int mcrat_hip_pool_run_frames(mcrat_hip_ctx *c, const mcrat_hip_frame
     c->rank_block_fixed = false;
     stats[0].step_kernel_ms = c->prof_step_ms;               // (profile = 1: the launch's duration, on the first item)
     stats[0].step_kernel_launches = c->prof_launches;
+    if (c->kc.table) {                                       // (the call's off-table look-ups, over every staged frame's counter)
+        long long fallbacks = 0;
+        for (size_t k = 0; k < hyv.size(); ++k) {
+            const HydroDev &h = hyv[k];
+            bool seen = false;                               // (a pool that shares another context's frame counts on that context's counter)
+            for (size_t j = 0; j < k; ++j) seen = seen || hyv[j].table_fallbacks == h.table_fallbacks;
+            int m = 0;
+            if (!h.table_fallbacks || seen) continue;
+            if (hipMemcpy(&m, h.table_fallbacks, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { fallbacks = -1; break; }
+            fallbacks += m;
+        }
+        stats[0].table_fallbacks = fallbacks;
+    }
     if (timing)
         fprintf(stderr, "pool_run_frames: %d frames x %d lists: plan -> queue %.0f us (checks %.0f, items %.0f, memsets + block choice %.0f, order %.0f), upload + launch calls %.0f us, waiting for the device %.0f us (kernel %.0f us), records -> stats %.0f us\n",
                 F, R, tq_filled - tq0, tq_a - tq0, tq_b - tq_a, tq_c - tq_b, tq_filled - tq_c, tq_launched - tq_filled, tq_synced - tq_launched, 1e3 * c->prof_step_ms, clock_us() - tq_synced);

@@ -1224,6 +1224,16 @@ __global__ __launch_bounds__(RANK_BLOCK, RANK_WAVES_PER_SIMD) void rank_loop_ker
     __syncthreads();
     if (st.done || n <= 0) {
         if (item >= 0 && tid == 0) { states[rank] = st; lay.fq.records[item] = st; }
+        // a frame with no time left (remaining_time <= 0) still leaves the list as the frame-by-frame path does: restored from the snapshot, and
+        // in its frame's capture (fresh, st.done and n come from the item and LDS: the branch is the whole workgroup's, as the copies need)
+        if (fresh && n > 0) {
+            if (lay.fq.restore) {
+                copy_list_columns(gph.r0, gph.col_stride, gph.idx, gph.flags, gph.type, base, n, lay.fq.snap_delta, 0, tid, RANK_BLOCK);
+                __syncthreads();
+            }
+            if (lay.fq.capture_delta != 0 && item / lay.n_ranks < lay.fq.n_frames - 1)
+                copy_list_columns(gph.r0, gph.col_stride, gph.idx, gph.flags, gph.type, base, n, 0, lay.fq.capture_delta + (long long)(item / lay.n_ranks) * lay.fq.capture_stride, tid, RANK_BLOCK);
+        }
         return;
     }
     if (fresh && lay.fq.restore) {                           // the frame starts from the snapshot of the list (mcrat_hip_restore_photons, for this list)

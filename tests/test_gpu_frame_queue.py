@@ -281,13 +281,15 @@ def test_captured_frames_are_the_lists_as_each_frame_left_them(hip, monkeypatch,
         ref.run(0)
         for r in range(R):
             t_now[r] = ref.views[r].frame_statistics().time_now
-        want.append((ref.get_photons_range(0, R * window).copy(), ref.pool_summaries(), ref.get_output()))
+        want.append((ref.get_photons_range(0, ref.n).copy(), ref.pool_summaries(), ref.get_output()))
     # (the captures' memory is whatever the allocator hands out: the slots no list owns -- the tails of the windows -- must still read as empty ones)
     import torch
     junk = torch.full((64 << 20,), 3.0e7, dtype=torch.float64, device="cuda")
     del junk
     torch.cuda.empty_cache()
     q = _pool(hip, frame, cfg, subs, streams, window)
+    stride = q.n // R
+    assert stride == ref.n // R >= window
     frame_end = np.array([[(f + 1) / fps for r in range(R)] for f in range(F)])
     q.pool_run_frames(open_, seeds, np.zeros((F, R)), frame_end.copy(), frame_end=frame_end, chain_clock=True, capture=True)
     for f in range(F):
@@ -295,13 +297,14 @@ def test_captured_frames_are_the_lists_as_each_frame_left_them(hip, monkeypatch,
         if f < F - 1:
             with pytest.raises(hip.McratHipError):                                  # nothing runs while a capture is selected
                 q.run(0)
-        got, summ = q.get_photons_range(0, R * window), q.pool_summaries()
+        got, summ = q.get_photons_range(0, q.n), q.pool_summaries()
         out = q.get_output()                                                        # printPhotons' compaction over the whole pool: weight != 0
         assert len(out["p0"]) == len(want[f][2]["p0"]) == sum(lens)
         for k in ("p0", "r0", "weight", "num_scatt", "s3"):
             assert np.array_equal(out[k], want[f][2][k]), (f, k)
         for r in range(R):
-            a, b = got[r * window:r * window + lens[r]], want[f][0][r * window:r * window + lens[r]]
+            lo = r * stride                                                         # (the pool rounds its windows up: 1100 -> 1536 slots)
+            a, b = got[lo:lo + lens[r]], want[f][0][lo:lo + lens[r]]
             for name in a.dtype.names:                                              # (field by field: the records' padding bytes are not data)
                 assert np.array_equal(a[name], b[name], equal_nan=a[name].dtype.kind == "f"), (f, r, name)
             for k in ("min_r", "max_r", "min_theta", "max_theta", "avg_r", "avg_scatt", "max_scatt", "min_scatt", "num_output", "list_capacity"):
@@ -361,4 +364,115 @@ def test_a_plan_with_staged_frames_in_table_mode(hip):
     with pytest.raises(hip.McratHipError):
         q.pool_run_frames(open_, seeds, np.zeros((F, R)), frame_end.copy(), frame_end=frame_end, chain_clock=True, hydro=[None, bare])
     for e in (bare, q, ref, holder):
+        e.close()
+
+
+def _same_records(a, b, what):
+    for name in a.dtype.names:                                                      # (field by field: the records' padding bytes are not data)
+        assert np.array_equal(a[name], b[name], equal_nan=a[name].dtype.kind == "f"), (what, name)
+
+
+@pytest.mark.parametrize("form", ["queue", "frame-by-frame"])
+def test_a_frame_with_no_time_left_is_captured_as_it_went_in(hip, monkeypatch, form):
+    """a list whose frame 0 opens with remaining_time = 0 is done at once (mcrat.c:761: the loop never runs) -- but frame 0's outputs still hold
+    it: its capture is the list as it went in, and printPhotons' compaction (get_output) keeps its photons.  It goes on in frame 1 from there"""
+    for k, v in FORMS[form].items():
+        monkeypatch.setenv(k, v)
+    lens = [137, 1000, 512, 64]
+    frame, cfg, subs, streams = _setup(hip, lens)
+    F, R, window = 2, len(lens), 1024
+    fps = frame["fps"]
+    seeds = np.array([[91 + 5 * r + 1000003 * f for r in range(R)] for f in range(F)], dtype=np.uint64)
+    open_ = np.ones((F, R), dtype=np.int32)
+    frame_end = np.array([[(f + 1) / fps for r in range(R)] for f in range(F)])
+    rem = frame_end.copy()
+    idle = 1
+    rem[0][idle] = 0.0
+    q = _pool(hip, frame, cfg, subs, streams, window)
+    stride = q.n // R                                                               # (the pool rounds its windows up)
+    before = q.get_photons_range(idle * stride, lens[idle])
+    got = q.pool_run_frames(open_, seeds, np.zeros((F, R)), rem, frame_end=frame_end, chain_clock=True, capture=True)
+    assert got[0][idle].iterations == 0 and got[0][idle].time_now == 0.0
+    assert got[1][idle].frame_scatt_cnt > 0                                          # (the list itself is not inert)
+    q.pool_select_frame(0)
+    _same_records(q.get_photons_range(idle * stride, lens[idle]), before, "capture of frame 0")
+    out = q.get_output()
+    assert len(out["p0"]) == sum(lens)
+    q.pool_select_frame(-1)
+    q.close()
+
+
+@pytest.mark.parametrize("form", ["queue", "frame-by-frame"])
+def test_a_restored_frame_with_no_time_left_is_the_snapshot(hip, monkeypatch, form):
+    """restore_each_frame: every frame starts from the snapshot, also one with remaining_time = 0 -- the list is then left as the snapshot holds it,
+    not as its previous frame left it"""
+    for k, v in FORMS[form].items():
+        monkeypatch.setenv(k, v)
+    lens = [400, 1000, 512, 976]
+    frame, cfg, subs, streams = _setup(hip, lens)
+    F, R, window = 3, len(lens), 1024
+    fps = frame["fps"]
+    seeds = np.array([[7 + 11 * r + 1000003 * f for r in range(R)] for f in range(F)], dtype=np.uint64)
+    open_ = np.ones((F, R), dtype=np.int32)
+    rem = np.full((F, R), 1.0 / fps)
+    idle = 2
+    rem[F - 1][idle] = 0.0
+    q = _pool(hip, frame, cfg, subs, streams, window)
+    q.snapshot_photons()
+    stride = q.n // R                                                               # (the pool rounds its windows up)
+    snap = q.get_photons_range(idle * stride, lens[idle])
+    got = q.pool_run_frames(open_, seeds, np.zeros((F, R)), rem, restore_each_frame=True)
+    assert got[F - 1][idle].iterations == 0
+    assert got[F - 2][idle].frame_scatt_cnt > 0                                      # (its previous frame moved it)
+    _same_records(q.get_photons_range(idle * stride, lens[idle]), snap, "the list after its last frame")
+    q.close()
+
+
+@pytest.mark.parametrize("form", ["queue", "frame-by-frame"])
+def test_a_plan_reports_the_table_fallbacks_of_every_staged_frame(hip, oracle, monkeypatch, form):
+    """TAU_CALCULATION == TABLE with a table that starts above the photons' energies (tests/test_gpu_parity.py: every look-up is integrated
+    afresh, 2560 samples): a plan's second frame staged on another context counts there.  stats[0].table_fallbacks is the whole call's count,
+    held to the bound mcrat_hip_run is held to: the oracle's count, plus at most one per scattering"""
+    from tests.test_gpu_pool import _hot_table
+    from tests.test_gpu_parity import _compare
+    from tests.test_gpu_queue_instantiations import _oracle_frames
+    for k, v in FORMS[form].items():
+        monkeypatch.setenv(k, v)
+    tab = _hot_table()
+    grid = (-2.0, 6.0, -4.0, 4.0)
+    lens = [100, 120, 80]
+    frame, ph, cfg = synth.config1(n_photons=sum(lens), n0=16, n1=16)
+    subs = _lists(ph, lens)
+    F, R, window = 2, len(lens), 128
+    streams = [5 + 3 * r for r in range(R)]
+    seeds = np.array([[9 + r + 1000003 * f for r in range(R)] for f in range(F)], dtype=np.uint64)
+    t0 = 0.0
+    rem, frame_end, want = _oracle_frames(oracle, frame, cfg, subs, [[int(s) for s in row] for row in seeds], streams, t0,
+                                          dict(hot_table=tab, grid=grid, fallback_calls=2560))
+
+    def context(profile):
+        e = hip.Engine(cfg["dimensions"], cfg["geometry"], cfg["stokes"], tau_calculation=hip.TAU_TABLE, profile=profile)
+        e.set_hot_cross_section(tab, grid)
+        assert e.table_fallback_calls(2560) == 2560
+        e.set_hydro(frame)
+        return e
+    holder = context(False)
+    q = context(True)
+    q.pool_create(R, window)
+    for r in range(R):
+        q.pool_rank(r, streams[r])
+    q.pool_set_photons(list(range(R)), [synth.photons_to_aos(s, hip.PHOTON_DTYPE) for s in subs])
+    ends = np.array([[frame_end[f]] * R for f in range(F)])
+    got = q.pool_run_frames(np.ones((F, R), dtype=np.int32), seeds, np.full((F, R), t0), np.full((F, R), rem), frame_end=ends, chain_clock=True,
+                            hydro=[None, holder])
+    if form == "queue":
+        assert got[0][0].step_kernel_launches == 1
+    for r in range(R):
+        assert (got[1][r].iterations, got[1][r].frame_scatt_cnt) == (want[r][1][1].iterations, want[r][1][1].frame_scatt_cnt), r
+        _compare(q.views[r].get_photons(), want[r][1][0], rtol=1e-6)               # (1e-6: the integrand's cancellation, tests/test_gpu_parity.py)
+    calls = [sum(want[r][f][1].table_fallbacks for r in range(R)) for f in range(F)]
+    scatt = sum(got[f][r].frame_scatt_cnt for f in range(F) for r in range(R))
+    assert calls[1] > scatt > 0                                                     # (frame 1's look-ups alone outnumber the bound's slack)
+    assert sum(calls) <= got[0][0].table_fallbacks <= sum(calls) + scatt, (got[0][0].table_fallbacks, calls, scatt)
+    for e in (q, holder):
         e.close()
