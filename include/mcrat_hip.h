@@ -711,6 +711,23 @@ int mcrat_hip_shared_clock_finish(mcrat_hip_ctx *ctx, mcrat_hip_frame_stats *sta
 int mcrat_hip_set_rng_tape(mcrat_hip_ctx *ctx, const double *uniforms, long long n);
 int mcrat_hip_rng_tape_position(mcrat_hip_ctx *ctx, long long *position, int *ran_out);
 
+/* Tapes for the lists of a rank pool.  MCRaT is run as many MPI ranks, each with its own gsl_rng_ranlxs0 stream (Src/mcrat.c:99-103, reseeded per
+ * frame :701); a maintainer who records several ranks replays them here as the lists of one pool.  Per list k: uniforms[k][0, n[k]) are the doubles
+ * that rank's generator returned, consumed as mcrat_hip_set_rng_tape consumes them -- per pass one gsl_rng_uniform_pos per located slot in ascending
+ * slot order (Src/mclib.c:646-675), then photonEvent's draws (Src/electron.c:81,196,217-233; Src/mcrat_scattering.c:519-574).  uniforms[k] == NULL or
+ * n[k] == 0: list k keeps its keyed streams (bit for bit what it gives in a pool without tapes).  Replaces every list's tape; positions start at 0 and
+ * carry over from frame to frame.  Every value must lie in [0, 1) (MCRAT_HIP_EINVAL).  A taped list ignores its seed in mcrat_hip_pool_begin_frames
+ * and in a frame plan.
+ * A pool that holds tapes runs every frame through the tape build of the loop kernel: 256 threads per list, columns in HBM/L2 -- neither the choice
+ * of workgroup size nor the MCRAT_HIP_RANK_* overrides apply -- and mcrat_hip_pool_run_frames runs its plan one launch per frame (captures and
+ * mcrat_hip_pool_select_frame as there).  Refused with MCRAT_HIP_ESTATE: these calls on a view or a context that is no pool; on a pool that holds tapes,
+ * mcrat_hip_pool_propagate_frames_fast, mcrat_hip_pool_scatter_frames_cyclosynch and mcrat_hip_run on one of its views; tapes on a pool with the
+ * cyclo-synchrotron switch.  Not covered: mcrat_host_run_ranks (its injection and per-frame reseeding draw from keyed streams).
+ *   mcrat_hip_pool_rng_tape_positions   per list: entries read so far (0 for a keyed list), ran_out != 0 if it needed more than its tape holds
+ *                                       (that list's results are then meaningless).  Synchronises the stream. */
+int mcrat_hip_pool_set_rng_tapes(mcrat_hip_ctx *pool, const double *const *uniforms /* [n_ranks] */, const long long *n /* [n_ranks] */);
+int mcrat_hip_pool_rng_tape_positions(mcrat_hip_ctx *pool, long long *position /* [n_ranks] */, int *ran_out /* [n_ranks] */);
+
 /* The device functions of the path, one at a time, on arrays -- for function-level parity tests against the reference functions
  * (tests/test_gpu_functions.py; the loop does not use this entry).  in / out: n rows of doubles, row layouts:
  *   KN_CROSS_SECTION       in  energy_ratio                          out sigma / sigma_T        kleinNishinaCrossSection, mcrat_scattering.c:597

@@ -105,6 +105,10 @@ struct mcrat_hip_ctx {
     double *d_tape = nullptr;
     long long tape_n = 0;
     long long *d_tape_cursor = nullptr;   // {cursor, error word} in one 16-byte block
+    // ... for the lists of a rank pool (mcrat_hip_pool_set_rng_tapes): every list's tape concatenated, one TapeList per list; a pool with
+    // d_pool_tapes runs every frame through the tape build (launch_rank_loop_tape)
+    double *d_pool_tape = nullptr;
+    TapeList *d_pool_tapes = nullptr;
     int fast_auto_windows = 32;       // FAST mode with fast_windows <= 0: the refresh cadence, from what the last FAST frame looked like (fast_cadence)
     bool rank_block_fixed = false;
     double rank_passes_per_list = 0;  // of the last completed frame
@@ -339,6 +343,8 @@ extern "C" void mcrat_hip_destroy(mcrat_hip_ctx *c)
     if (c->d_hot_table) (void)hipFree(c->d_hot_table);
     if (c->d_tape) (void)hipFree(c->d_tape);
     if (c->d_tape_cursor) (void)hipFree(c->d_tape_cursor);
+    if (c->d_pool_tape) (void)hipFree(c->d_pool_tape);
+    if (c->d_pool_tapes) (void)hipFree(c->d_pool_tapes);
     if (c->d_table_fallbacks) (void)hipFree(c->d_table_fallbacks);
     if (c->d_sc) (void)hipFree(c->d_sc);
     if (c->sc_own_send && c->sc_send) (void)hipFree(c->sc_send);
@@ -2470,6 +2476,12 @@ extern "C" int mcrat_hip_rank_stats(mcrat_hip_ctx *c, int rank, mcrat_hip_frame_
 }
 
 // ---------------------------------------------------------------------------------------------- rank pool
+static void drop_pool_tapes(mcrat_hip_ctx *c)
+{
+    if (c->d_pool_tape) { (void)hipFree(c->d_pool_tape); c->d_pool_tape = nullptr; }
+    if (c->d_pool_tapes) { (void)hipFree(c->d_pool_tapes); c->d_pool_tapes = nullptr; }
+}
+
 extern "C" int mcrat_hip_pool_create(mcrat_hip_ctx *c, int n_ranks, int slots_per_rank)
 {
     if (!c || n_ranks <= 0 || slots_per_rank <= 0) return MCRAT_HIP_EINVAL;
@@ -2482,6 +2494,7 @@ extern "C" int mcrat_hip_pool_create(mcrat_hip_ctx *c, int n_ranks, int slots_pe
         if (v) { v->parent = nullptr; destroy_view(v); }
     c->views.clear();
     c->is_pool = false;
+    drop_pool_tapes(c);                              // (they were the old lists')
     c->cfg.virtual_rank_photons = (int)stride;
     int rc = alloc_photons(c, (int)(stride * (size_t)n_ranks));       // zeroed: no slot belongs to a list yet
     if (rc) return rc;
@@ -2742,6 +2755,65 @@ extern "C" int mcrat_hip_rng_tape_position(mcrat_hip_ctx *c, long long *position
     return MCRAT_HIP_OK;
 }
 
+// The tape for the lists of a rank pool: per list, the doubles MCRaT's generator returned for that rank (tools/ref_harness; every MPI rank has its own
+// stream, mcrat.c:99-103,701), consumed as mcrat_hip_set_rng_tape consumes one -- by the tape build of the loop kernel (kernels.hip,
+// rank_loop_kernel<.., TAPE>), which every frame of a pool that holds tapes runs through.  uniforms[k] == NULL or n[k] == 0: list k keeps its keyed
+// streams.  Replaces every list's tape; positions start at 0.  A taped list ignores its seed.
+extern "C" int mcrat_hip_pool_set_rng_tapes(mcrat_hip_ctx *c, const double *const *uniforms, const long long *n)
+{
+    if (!c) return MCRAT_HIP_EINVAL;
+    if (c->parent || !c->is_pool) { c->last_error = "tapes for many lists are set on a rank pool (mcrat_hip_set_rng_tape: one list)"; return MCRAT_HIP_ESTATE; }
+    if (c->cfg.cyclosynchrotron_switch) { c->last_error = "CYCLOSYNCHROTRON_SWITCH is on: the cyclo-synchrotron hook has no tape build"; return MCRAT_HIP_ESTATE; }
+    if (!uniforms || !n) return MCRAT_HIP_EINVAL;
+    const int R = c->n_ranks;
+    long long total = 0;
+    for (int r = 0; r < R; ++r) {
+        if (n[r] < 0) return MCRAT_HIP_EINVAL;
+        if (!uniforms[r]) continue;
+        for (long long k = 0; k < n[r]; ++k)
+            if (!(uniforms[r][k] >= 0.0 && uniforms[r][k] < 1.0)) { c->last_error = "a tape holds a value outside [0, 1)"; return MCRAT_HIP_EINVAL; }
+        total += n[r];
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    drop_pool_tapes(c);
+    if (total == 0) return MCRAT_HIP_OK;
+    std::vector<TapeList> h((size_t)R);
+    memset(h.data(), 0, sizeof(TapeList) * (size_t)R);
+    double *buf = nullptr;
+    HIPCHK(c, hipMalloc((void **)&buf, sizeof(double) * (size_t)total));
+    c->d_pool_tape = buf;
+    long long off = 0;
+    for (int r = 0; r < R; ++r) {
+        if (!uniforms[r] || n[r] == 0) continue;
+        h[(size_t)r].offset = off;
+        h[(size_t)r].n = n[r];
+        HIPCHK(c, hipMemcpy(buf + off, uniforms[r], sizeof(double) * (size_t)n[r], hipMemcpyHostToDevice));
+        off += n[r];
+    }
+    TapeList *d = nullptr;
+    HIPCHK(c, hipMalloc((void **)&d, sizeof(TapeList) * (size_t)R));
+    c->d_pool_tapes = d;
+    HIPCHK(c, hipMemcpy(d, h.data(), sizeof(TapeList) * (size_t)R, hipMemcpyHostToDevice));
+    return MCRAT_HIP_OK;
+}
+
+// per list: entries of its tape read so far (zeros skipped by uniform_pos included; 0 for a keyed list) and whether it needed more than its tape
+// holds (its results are then meaningless).  Synchronises the stream.
+extern "C" int mcrat_hip_pool_rng_tape_positions(mcrat_hip_ctx *c, long long *position, int *ran_out)
+{
+    if (!c) return MCRAT_HIP_EINVAL;
+    if (c->parent || !c->is_pool || !c->d_pool_tapes) { c->last_error = "no rank pool with tapes (mcrat_hip_pool_set_rng_tapes)"; return MCRAT_HIP_ESTATE; }
+    const int R = c->n_ranks;
+    std::vector<TapeList> h((size_t)R);
+    HIPCHK(c, hipMemcpyAsync(h.data(), c->d_pool_tapes, sizeof(TapeList) * (size_t)R, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int r = 0; r < R; ++r) {
+        if (position) position[r] = h[(size_t)r].cursor;
+        if (ran_out) ran_out[r] = h[(size_t)r].error != 0;
+    }
+    return MCRAT_HIP_OK;
+}
+
 static int ensure_events(mcrat_hip_ctx *c, size_t n)
 {
     while (c->ev.size() < n) {
@@ -2832,8 +2904,12 @@ static int run_ranks(mcrat_hip_ctx *c, long long max_iterations, mcrat_hip_frame
             if (rc) return rc;
             HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
         }
-        HIPCHK(c, launch_rank_loop(c->kc, c->ph, c->hy, c->d_rstates, c->key, c->n_ranks, c->rank_stride, longest, c->is_pool ? c->d_desc : nullptr, nullptr, nullptr, batch,
-                                   c->rank_block + (c->rank_fuse ? 1000 : 0), c->stream));
+        if (c->d_pool_tapes)                       // a pool that holds tapes: the tape build, whatever the choice above
+            HIPCHK(c, launch_rank_loop_tape(c->kc, c->ph, c->hy, c->d_rstates, c->key, c->n_ranks, c->rank_stride, c->d_desc, c->d_pool_tape, c->d_pool_tapes, batch,
+                                            c->stream));
+        else
+            HIPCHK(c, launch_rank_loop(c->kc, c->ph, c->hy, c->d_rstates, c->key, c->n_ranks, c->rank_stride, longest, c->is_pool ? c->d_desc : nullptr, nullptr, nullptr,
+                                       batch, c->rank_block + (c->rank_fuse ? 1000 : 0), c->stream));
         if (c->cfg.profile) {
             HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
             HIPCHK(c, hipEventSynchronize(c->ev[1]));
@@ -3011,6 +3087,7 @@ extern "C" int mcrat_hip_pool_run_frames(mcrat_hip_ctx *c, const mcrat_hip_frame
     for (int x = 0; x < FRAME_QUEUE_XCDS; ++x) xcd_of_class[x] = x;
     std::vector<unsigned> tickets((size_t)FRAME_QUEUE_XCDS * FRAME_TICKET_STRIDE);
     bool one_by_one = getenv("MCRAT_HIP_NO_FRAME_QUEUE") && atoi(getenv("MCRAT_HIP_NO_FRAME_QUEUE")) != 0;      // (A/B: the plan frame by frame)
+    one_by_one = one_by_one || c->d_pool_tapes != nullptr;              // (a pool that holds tapes: the tape build has no queue form)
     for (int attempt = 0; !one_by_one; ++attempt) {
         // the open items in the order they are taken: per XCD (list r belongs to XCD r % 8: a list never changes L2) frame-major; one workgroup per item,
         // and as the hardware deals workgroups round-robin over the XCDs, eight times the longest XCD's list of them
@@ -3135,8 +3212,12 @@ extern "C" int mcrat_hip_pool_run_frames(mcrat_hip_ctx *c, const mcrat_hip_frame
             HIPCHK(c, launch_init_states_multi(c->d_rstates, R, d_open, d_t, d_rem, c->stream));
             for (;;) {
                 if (c->cfg.profile) { rc = ensure_events(c, 2); if (rc) return rc; HIPCHK(c, hipEventRecord(c->ev[0], c->stream)); }
-                HIPCHK(c, launch_rank_loop(c->kc, c->ph, hyv[(size_t)hy_of_frame[(size_t)f]], c->d_rstates, c->key, R, c->rank_stride, longest, c->d_desc, nullptr, nullptr,
-                                           per_frame_cap, c->rank_block + (c->rank_fuse ? 1000 : 0), c->stream));
+                if (c->d_pool_tapes)                  // (each frame reads on from each list's position)
+                    HIPCHK(c, launch_rank_loop_tape(c->kc, c->ph, hyv[(size_t)hy_of_frame[(size_t)f]], c->d_rstates, c->key, R, c->rank_stride, c->d_desc, c->d_pool_tape,
+                                                    c->d_pool_tapes, per_frame_cap, c->stream));
+                else
+                    HIPCHK(c, launch_rank_loop(c->kc, c->ph, hyv[(size_t)hy_of_frame[(size_t)f]], c->d_rstates, c->key, R, c->rank_stride, longest, c->d_desc, nullptr,
+                                               nullptr, per_frame_cap, c->rank_block + (c->rank_fuse ? 1000 : 0), c->stream));
                 if (c->cfg.profile) HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
                 HIPCHK(c, hipMemcpyAsync(c->h_rstates, c->d_rstates, sizeof(LoopState) * (size_t)R, hipMemcpyDeviceToHost, c->stream));
                 HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3234,6 +3315,10 @@ extern "C" int mcrat_hip_run(mcrat_hip_ctx *c, long long max_iterations, mcrat_h
         return MCRAT_HIP_ESTATE;
     }
     if (c->n_ranks > 0) return run_ranks(c, max_iterations, stats);
+    if (c->parent && c->parent->d_pool_tapes) {
+        c->last_error = "the pool holds tapes of uniforms (mcrat_hip_pool_set_rng_tapes): run the pool, whose tape build reads them, not one of its views";
+        return MCRAT_HIP_ESTATE;
+    }
     const int per_sync = c->cfg.iterations_per_sync;
     long long it = 0;
     int rc;
@@ -3365,6 +3450,7 @@ extern "C" int mcrat_hip_pool_propagate_frames_fast(mcrat_hip_ctx *c, const int 
 {
     if (!c || !open || !seeds || !time_now || !remaining_time) return MCRAT_HIP_EINVAL;
     if (!c->is_pool) return MCRAT_HIP_ESTATE;
+    if (c->d_pool_tapes) { c->last_error = "the pool holds tapes of uniforms (mcrat_hip_pool_set_rng_tapes): FAST mode has no tape build"; return MCRAT_HIP_ESTATE; }
     int rc = fast_refusals(c);
     if (rc) return rc;
     const int R = c->n_ranks;
@@ -3717,6 +3803,7 @@ extern "C" int mcrat_hip_pool_scatter_frames_cyclosynch(mcrat_hip_ctx *c, const 
     if (!c || !cs || !lists || !counts || cs->b_field_calc < 0 || cs->b_field_calc > 2 || max_photons <= 0 || !(fps > 0)) return MCRAT_HIP_EINVAL;
     if (!c->is_pool) return MCRAT_HIP_ESTATE;
     if (!c->cfg.cyclosynchrotron_switch) { c->last_error = "the pool was created with cyclosynchrotron_switch = 0"; return MCRAT_HIP_ESTATE; }
+    if (c->d_pool_tapes) { c->last_error = "the pool holds tapes of uniforms (mcrat_hip_pool_set_rng_tapes): the cyclo-synchrotron hook has no tape build"; return MCRAT_HIP_ESTATE; }
     if (!c->have_hydro || !c->hcol_buf) return MCRAT_HIP_ESTATE;
     const int R = c->n_ranks;
     int rc;

@@ -1003,7 +1003,9 @@ __global__ __launch_bounds__(EVENT_BLOCK) void event_kernel(PhotonDev ph, HydroD
 // serial dependency through the whole list by construction), not a fast one.
 constexpr int TAPE_BLOCK = 1024;
 
-__device__ __forceinline__ int block_exclusive_scan_1024(int v, int *s_w, int &total)
+// (BLOCK threads, BLOCK / 64 words of s_w)
+template <int BLOCK>
+__device__ __forceinline__ int block_exclusive_scan(int v, int *s_w, int &total)
 {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     int x = v;
@@ -1012,16 +1014,42 @@ __device__ __forceinline__ int block_exclusive_scan_1024(int v, int *s_w, int &t
     if (lane == 63) s_w[w] = x;
     __syncthreads();
     if (w == 0) {
-        int t = lane < TAPE_BLOCK / 64 ? s_w[lane] : 0;
+        int t = lane < BLOCK / 64 ? s_w[lane] : 0;
 #pragma unroll
-        for (int off = 1; off < 16; off <<= 1) { const int y = __shfl_up(t, off, 64); if (lane >= off) t += y; }
-        if (lane < TAPE_BLOCK / 64) s_w[lane] = t;
+        for (int off = 1; off < BLOCK / 64; off <<= 1) { const int y = __shfl_up(t, off, 64); if (lane >= off) t += y; }
+        if (lane < BLOCK / 64) s_w[lane] = t;
     }
     __syncthreads();
-    total = s_w[TAPE_BLOCK / 64 - 1];
+    total = s_w[BLOCK / 64 - 1];
     const int before = (w > 0 ? s_w[w - 1] : 0) + x - v;
     __syncthreads();
     return before;
+}
+
+// The next `need` (<= BLOCK) non-zero entries of a tape from `pos` on into s_u[0, need), window by window of BLOCK entries; returns the position
+// behind the last one taken.  An entry needed beyond the tape's end raises *error (a filler stands in for it).  All BLOCK threads call it.
+template <int BLOCK>
+__device__ __forceinline__ long long tape_take_nonzero(const double *u, long long n, int *error, long long pos, int need, double *s_u, int *s_w,
+                                                       long long *s_pos)
+{
+    const int tid = threadIdx.x;
+    int have = 0;
+    while (have < need) {
+        const long long q = pos + tid;
+        const double v = q < n ? u[q] : 0.25 + 0.5 * (double)(tid & 1);      // (beyond the tape: flagged below)
+        const bool nz = v != 0.0;
+        int found = 0;
+        const int k = block_exclusive_scan<BLOCK>(nz ? 1 : 0, s_w, found);
+        if (nz && have + k < need) s_u[have + k] = v;
+        if (nz && have + k == need - 1) *s_pos = q + 1;                      // the entry that completes the chunk: the cursor stops behind it
+        if (q >= n && have + k < need) *error = 1;                           // an entry beyond the tape's end was needed
+        __syncthreads();
+        if (have + found >= need) { pos = *s_pos; have = need; }
+        else { have += found; pos += BLOCK; }
+        __syncthreads();
+    }
+    if (pos > n) { if (tid == 0) *error = 1; pos = n; }
+    return pos;
 }
 
 __global__ __launch_bounds__(TAPE_BLOCK) void tape_draw_kernel(PhotonDev ph, const LoopState *__restrict__ st, TapeDev tape, Cand *__restrict__ block_min,
@@ -1045,24 +1073,8 @@ __global__ __launch_bounds__(TAPE_BLOCK) void tape_draw_kernel(PhotonDev ph, con
         const bool valid = i < ph.n && (ph.flags[i] & FLAG_VALID);
         const bool located = valid && ph.idx[i] != -1;
         int need = 0;
-        const int rank = block_exclusive_scan_1024(located ? 1 : 0, s_w, need);
-        // the next `need` non-zero entries of the tape, window by window
-        int have = 0;
-        while (have < need) {
-            const long long q = pos + tid;
-            const double v = q < tape.n ? tape.u[q] : 0.25 + 0.5 * (double)(tid & 1);      // (beyond the tape: flagged below)
-            const bool nz = v != 0.0;
-            int found = 0;
-            const int k = block_exclusive_scan_1024(nz ? 1 : 0, s_w, found);
-            if (nz && have + k < need) s_u[have + k] = v;
-            if (nz && have + k == need - 1) s_pos = q + 1;                 // the entry that completes the chunk: the cursor stops behind it
-            if (q >= tape.n && have + k < need) *tape.error = 1;             // an entry beyond the tape's end was needed
-            __syncthreads();
-            if (have + found >= need) { pos = s_pos; have = need; }
-            else { have += found; pos += TAPE_BLOCK; }
-            __syncthreads();
-        }
-        if (pos > tape.n) { if (tid == 0) *tape.error = 1; pos = tape.n; }
+        const int rank = block_exclusive_scan<TAPE_BLOCK>(located ? 1 : 0, s_w, need);
+        pos = tape_take_nonzero<TAPE_BLOCK>(tape.u, tape.n, tape.error, pos, need, s_u, s_w, &s_pos);
         if (valid) {
             double t = ph.tts[i];                                          // slots without a cell: 1e12 / c, stored by step_kernel (mclib.c:620,684)
             if (located) {
@@ -1134,6 +1146,18 @@ struct RankLayout {
     const CsHookArgs *hook;   // ... or, when given (and the kernel built with CSH), what the hook needs to run right there, inside the loop
     FrameQueueDev fq;     // n_frames > 0: persistent workgroups take (frame, list) items from a ticket (launch.hpp)
 };
+// ... of the tape build (TAPE): the pool's recorded streams (launch.hpp, TapeList)
+struct TapeLayout : RankLayout {
+    const double *tape_u; // every list's tape, concatenated
+    TapeList *tapes;      // [n_ranks]
+};
+// the tape build's LDS beside the loop's: a chunk's uniforms, the scans' words, and the list's cursor for the launch (TapeSource reads it on)
+template <int BLOCK>
+struct TapeLds {
+    double u[BLOCK];
+    int w[BLOCK / 64];
+    long long pos, cursor;
+};
 
 // Four lists per CU.  Measured by varying the number of lists on a dense jet: a workgroup alone on its CU needs 25 us per
 // pass, two per CU 27 us each -- a pass is a chain of latencies (LDS -> sqrt -> gather -> Philox -> log; two dependent loads and a
@@ -1159,11 +1183,15 @@ constexpr int rank_lds_bytes_per_slot(int block) { return block == 256 ? 7 * (in
 // QUEUE: the build that can take (frame, list) items from the frame queue (launch.hpp, FrameQueueDev).  A build of its own because carrying the
 // queue's paths costs a build that does not use them 25 spilled doubles per lane (measured: the 2-D spherical Stokes build 128 -> 328 B of scratch, cfg3's
 // frame 6.0 -> 8.2 ms), and instantiated only for the 256-thread lists with their columns in LDS; every other launch form runs a plan frame by frame.
-template <int DIMS, int GEOM, bool STOKES, bool RESIDENT, int RANK_BLOCK, bool FUSE, bool CSH = false, bool QUEUE = false>
+// TAPE: the build in which a list can draw from a recorded stream instead of its keyed ones (launch.hpp, TapeList): per pass, after phase 1 and 2
+// have re-located the slots with keyed draws, the list's free times are drawn again from its tape in ascending slot order, and the walk reads on from
+// there with the serial samplers.  A validation mode, instantiated only for 256 threads with the columns in HBM/L2, without the fused pass or the queue.
+template <int DIMS, int GEOM, bool STOKES, bool RESIDENT, int RANK_BLOCK, bool FUSE, bool CSH = false, bool QUEUE = false, bool TAPE = false>
 // (one wavefront per SIMD for the small-list builds -- up to 512 registers, spills to AGPRs, no scratch -- measured slower: cfg5's 64-thread lists
 // frac 0.394 -> 0.365, cfg3's 128-thread lists 0.32 -> 0.21: the second wavefront hides more latency than the scratch traffic costs)
 __global__ __launch_bounds__(RANK_BLOCK, RANK_WAVES_PER_SIMD) void rank_loop_kernel(PhotonDev gph, HydroDev hy_arg, LoopState *states, RngKey key,
-                                                                RankLayout lay, long long max_passes, int lds_slots)
+                                                                std::conditional_t<TAPE, TapeLayout, RankLayout> lay, long long max_passes,
+                                                                int lds_slots)
 {
     constexpr int EVENT_BLOCK = RANK_BLOCK;                    // (shadows the event kernel's block size inside this kernel)
 #ifndef RANK_NS_SPHERICAL
@@ -1179,6 +1207,11 @@ __global__ __launch_bounds__(RANK_BLOCK, RANK_WAVES_PER_SIMD) void rank_loop_ker
     // the slow-path queue shares memory with the event walk's sorted list: the queue is empty before the list is written
     static_assert(sizeof(sh.list) >= sizeof(int) * RANK_QCAP, "queue fits into the sorted-list storage");
     int *const s_q = reinterpret_cast<int *>(sh.list);
+    [[maybe_unused]] TapeLds<RANK_BLOCK> *tl = nullptr;
+    if constexpr (TAPE) {
+        __shared__ TapeLds<RANK_BLOCK> s_tape;
+        tl = &s_tape;
+    }
     int tid = threadIdx.x, lane = tid & 63;                   // (not const: the queue builds launder them between two items, see the loop below)
     const bool queued = QUEUE ? lay.fq.n_frames > 0 : false;
     // One list through one frame: the whole loop of mcrat.c:761-851.  Without a queue the workgroup does this once, for list blockIdx.x, from the
@@ -1220,6 +1253,15 @@ __global__ __launch_bounds__(RANK_BLOCK, RANK_WAVES_PER_SIMD) void rank_loop_ker
     } else if (tid == 0) {
         st = states[rank];
         if (st.last_scattered_index >= 0) st.last_scattered_index += idx_shift;
+    }
+    // the list's recorded stream (TAPE): read on from where its last frame stopped; a list without one keeps its keyed streams
+    [[maybe_unused]] bool taped = false;
+    [[maybe_unused]] TapeSource tsrc;
+    if constexpr (TAPE) {
+        const TapeList td = lay.tapes[rank];
+        taped = td.n > 0;
+        tsrc.t.u = lay.tape_u + td.offset; tsrc.t.n = td.n; tsrc.t.cursor = &tl->cursor; tsrc.t.error = &lay.tapes[rank].error;
+        if (tid == 0) tl->cursor = td.cursor;
     }
     __syncthreads();
     if (st.done || n <= 0) {
@@ -1300,7 +1342,9 @@ __global__ __launch_bounds__(RANK_BLOCK, RANK_WAVES_PER_SIMD) void rank_loop_ker
     // wavefront's, event_block) compute the NEXT pass's while they would otherwise wait at the barrier, into a scratch column (ListCols::draw_log).
     // Phase 1 then reads 8 B per slot instead of running ten Philox rounds per pair and a logarithm per slot: the same bits, a shorter pass.
 #ifndef MCRAT_NO_SHADOW_DRAWS
-    constexpr bool SHADOW = RANK_BLOCK > 64;                 // (a list of one wavefront has nobody in the walk's shadow: it draws in phase 1, as before)
+    // (a list of one wavefront has nobody in the walk's shadow: it draws in phase 1, as before; nor the tape build: a taped list's next draws
+    // start where this pass's walk stops, and its keyed lists draw in phase 1 the same bits)
+    constexpr bool SHADOW = RANK_BLOCK > 64 && !TAPE;
 #else
     constexpr bool SHADOW = false;                           // (A/B build)
 #endif
@@ -1606,6 +1650,37 @@ __global__ __launch_bounds__(RANK_BLOCK, RANK_WAVES_PER_SIMD) void rank_loop_ker
                 }
             }
         }
+        if constexpr (TAPE) {
+            // calcMeanFreePath with the list's tape (mclib.c:646-675; as tape_draw_kernel for one list): the slots re-located above take one
+            // gsl_rng_uniform_pos each -- the next non-zero entry -- in ascending slot order, chunk by chunk; their keyed free times, the minimum and
+            // the shortlist are replaced
+            if (taped) {
+                __syncthreads();                                 // phase 2's cells, free times and shortlist entries are complete
+                if (tid == 0) s_sln = 0;
+                best.init();
+                long long pos = tl->cursor;
+                __syncthreads();
+                for (int c0 = 0; c0 < n_pass; c0 += RANK_BLOCK) {
+                    const int i = base + c0 + tid;
+                    const bool valid = c0 + tid < n_pass && (ph.flags(i) & FLAG_VALID);
+                    const bool located = valid && ph.idx(i) != -1;
+                    int need = 0;
+                    const int k = block_exclusive_scan<RANK_BLOCK>(located ? 1 : 0, tl->w, need);
+                    pos = tape_take_nonzero<RANK_BLOCK>(tsrc.t.u, tsrc.t.n, tsrc.t.error, pos, need, tl->u, tl->w, &tl->pos);
+                    if (valid) {
+                        double t = ph.tts(i);                        // slots without a cell: 1e12 / c (mclib.c:620,684)
+                        if (located) {
+                            t = div_by_c(ph.ntau(i) * log(tl->u[k]));   // mclib.c:675-687
+                            ph.tts(i) = t;
+                        }
+                        best.offer(t, i);
+                        if (t < t_cut) shortlist_lds(t, i);
+                    }
+                    __syncthreads();
+                }
+                if (tid == 0) tl->cursor = pos;
+            }
+        }
         wave_min_pair_dpp(best.t, best.i);
         if (lane == 0) { sh.wt[tid >> 6] = best.t; sh.wi[tid >> 6] = best.i; }
         if (relocated) atomicAdd(reinterpret_cast<unsigned long long *>(&st.n_relocated), (unsigned long long)relocated);
@@ -1624,7 +1699,12 @@ __global__ __launch_bounds__(RANK_BLOCK, RANK_WAVES_PER_SIMD) void rank_loop_ker
         // the wavefronts that do not walk draw for the next pass now; they join the others at the barrier behind the walk (event_block)
         if constexpr (SHADOW) { if (frame_goes_on && tid >= 64) draw_logs(iter + 1, 64, RANK_BLOCK - 64); }
         (void)frame_goes_on;
-        event_block<DIMS, GEOM, STOKES, RANK_BLOCK>(ph, hy, &st, rk, sh, s_sln, gmin, base, n_pass, iter, st.remaining_time, st.last_scattered_index, st.t_est);
+        if constexpr (TAPE) {
+            if (taped) event_block<DIMS, GEOM, STOKES, RANK_BLOCK>(ph, hy, &st, rk, sh, s_sln, gmin, base, n_pass, iter, st.remaining_time, st.last_scattered_index, st.t_est, tsrc);
+            else event_block<DIMS, GEOM, STOKES, RANK_BLOCK>(ph, hy, &st, rk, sh, s_sln, gmin, base, n_pass, iter, st.remaining_time, st.last_scattered_index, st.t_est);
+        } else {
+            event_block<DIMS, GEOM, STOKES, RANK_BLOCK>(ph, hy, &st, rk, sh, s_sln, gmin, base, n_pass, iter, st.remaining_time, st.last_scattered_index, st.t_est);
+        }
         if (tid == 0) {
             st.force_relocate = 0;
             // cyclo-synchrotron lists: if photonEvent reported a pool photon (it becomes a comptonised one and is replaced, mcrat.c:786-795)
@@ -1707,6 +1787,7 @@ __global__ __launch_bounds__(RANK_BLOCK, RANK_WAVES_PER_SIMD) void rank_loop_ker
             if (st.last_scattered_index >= 0) st.last_scattered_index -= idx_shift;
             states[rank] = st;
             if (item >= 0) lay.fq.records[item] = st;
+            if constexpr (TAPE) lay.tapes[rank].cursor = tl->cursor;
         }
         // the list as this frame leaves it, for the frame's outputs (printPhotons, saveCheckpoint: mcrat.c:881-906), before its next frame moves it on
         if (item >= 0 && lay.fq.capture_delta != 0 && item / lay.n_ranks < lay.fq.n_frames - 1 && st.done == LOOP_DONE) {
@@ -2595,6 +2676,22 @@ hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const H
     });
     if (queued && !queue_launched && launched == hipSuccess) return hipErrorNotSupported;      // no queue build of this launch form: frame by frame then
     return launched;
+}
+
+// the tape build: one launch form for every list length (256 threads, columns in HBM/L2, no fused pass)
+hipError_t launch_rank_loop_tape(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, int n_ranks, int rank_stride,
+                                 const RankDesc *desc, const double *u, TapeList *tapes, long long max_passes, hipStream_t stream)
+{
+    if (!desc || !u || !tapes) return hipErrorInvalidValue;
+    TapeLayout lay;
+    static_cast<RankLayout &>(lay) = RankLayout{n_ranks, rank_stride, ph.n, desc, nullptr, nullptr, FrameQueueDev{}};
+    lay.tape_u = u;
+    lay.tapes = tapes;
+    return dispatch(kc, [&](auto D, auto G) {
+        constexpr int DV = decltype(D)::value, GV = decltype(G)::value;
+        if (kc.stokes) rank_loop_kernel<DV, GV, true, false, 256, false, false, false, true><<<dim3(n_ranks), dim3(256), 0, stream>>>(ph, hy, states, key, lay, max_passes, 0);
+        else rank_loop_kernel<DV, GV, false, false, 256, false, false, false, true><<<dim3(n_ranks), dim3(256), 0, stream>>>(ph, hy, states, key, lay, max_passes, 0);
+    });
 }
 
 hipError_t launch_fast_frame(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, RngKey key, double remaining_time, int windows,

@@ -72,6 +72,19 @@ constexpr int FRAME_QUEUE_XCDS = 8, FRAME_TICKET_STRIDE = 16;     // (a ticket p
 hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key,
                             int n_ranks, int rank_stride, int longest_list, const RankDesc *desc, struct CsFrame *cs, const struct CsHookArgs *hook,
                             long long max_passes, int block, hipStream_t stream, const FrameQueueDev *fq = nullptr, int n_open = 0);
+// The tape build of the rank pool (mcrat_hip_pool_set_rng_tapes): every list of a pool that holds tapes goes through it, whatever choose_rank_block
+// would pick -- 256 threads per list, columns in HBM/L2, no fused pass, no frame queue.  A list with a tape takes its free-path draws and its events'
+// draws from it, in MCRaT's call order, as the one-list tape path does (launch_tape_pass); a list without one draws from its keyed streams exactly as
+// the keyed builds do.  Its tape is entries [offset, offset + n) of `u`; `cursor` is read when the list's frame starts and written when it ends.
+struct TapeList {
+    long long offset;                // the list's first entry in the pool's concatenated tape buffer
+    long long n;                     // its entries (0: the list keeps its keyed streams)
+    long long cursor;                // the next unread entry, relative to offset
+    int error;                       // != 0: the list needed more entries than its tape holds (its results are then meaningless)
+    int pad;
+};
+hipError_t launch_rank_loop_tape(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, int n_ranks, int rank_stride,
+                                 const RankDesc *desc, const double *u, TapeList *tapes, long long max_passes, hipStream_t stream);
 // shared clock with a device-initiated exchange (staging.hip): recv[r] = rank r's receive buffer (2 x world proposals, by round parity),
 // flag[r] = rank r's stamps (SC_MAX_WORLD words, one per sender, + a word counting waits that gave up + the rank's own round number)
 struct ScPeers { ScProposal *recv[SC_MAX_WORLD]; unsigned long long *flag[SC_MAX_WORLD]; };

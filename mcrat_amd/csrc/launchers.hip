@@ -17,6 +17,8 @@ hipError_t launch_tape_pass(const KernelConfig &kc, const PhotonDev &ph, const H
 hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key,
                             int n_ranks, int rank_stride, int longest_list, const RankDesc *desc, CsFrame *cs, const CsHookArgs *hook, long long max_passes,
                             int block, hipStream_t stream, const FrameQueueDev *fq, int n_open);
+hipError_t launch_rank_loop_tape(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, int n_ranks, int rank_stride,
+                                 const RankDesc *desc, const double *u, TapeList *tapes, long long max_passes, hipStream_t stream);
 hipError_t launch_sc_propose(const KernelConfig &kc, bool force_relocate, const PhotonDev &ph, const HydroDev &hy, LoopState *st,
                              ScState *sc, RngKey key, Cand *block_min, int blocks, Shortlist *sl, ScProposal *out, const ScFold &fold, hipStream_t stream);
 hipError_t launch_sc_resolve(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, ScState *sc, RngKey key,
@@ -41,6 +43,8 @@ hipError_t launch_tape_pass(const KernelConfig &kc, const PhotonDev &ph, const H
 hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key,
                             int n_ranks, int rank_stride, int longest_list, const RankDesc *desc, CsFrame *cs, const CsHookArgs *hook, long long max_passes,
                             int block, hipStream_t stream, const FrameQueueDev *fq, int n_open);
+hipError_t launch_rank_loop_tape(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, int n_ranks, int rank_stride,
+                                 const RankDesc *desc, const double *u, TapeList *tapes, long long max_passes, hipStream_t stream);
 hipError_t launch_sc_propose(const KernelConfig &kc, bool force_relocate, const PhotonDev &ph, const HydroDev &hy, LoopState *st,
                              ScState *sc, RngKey key, Cand *block_min, int blocks, Shortlist *sl, ScProposal *out, const ScFold &fold, hipStream_t stream);
 hipError_t launch_sc_resolve(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, ScState *sc, RngKey key,
@@ -59,6 +63,8 @@ hipError_t launch_tape_pass(const KernelConfig &kc, const PhotonDev &ph, const H
 hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key,
                             int n_ranks, int rank_stride, int longest_list, const RankDesc *desc, CsFrame *cs, const CsHookArgs *hook, long long max_passes,
                             int block, hipStream_t stream, const FrameQueueDev *fq, int n_open);
+hipError_t launch_rank_loop_tape(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, int n_ranks, int rank_stride,
+                                 const RankDesc *desc, const double *u, TapeList *tapes, long long max_passes, hipStream_t stream);
 hipError_t launch_sc_propose(const KernelConfig &kc, bool force_relocate, const PhotonDev &ph, const HydroDev &hy, LoopState *st,
                              ScState *sc, RngKey key, Cand *block_min, int blocks, Shortlist *sl, ScProposal *out, const ScFold &fold, hipStream_t stream);
 hipError_t launch_sc_resolve(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, ScState *sc, RngKey key,
@@ -77,6 +83,8 @@ hipError_t launch_tape_pass(const KernelConfig &kc, const PhotonDev &ph, const H
 hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key,
                             int n_ranks, int rank_stride, int longest_list, const RankDesc *desc, CsFrame *cs, const CsHookArgs *hook, long long max_passes,
                             int block, hipStream_t stream, const FrameQueueDev *fq, int n_open);
+hipError_t launch_rank_loop_tape(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, int n_ranks, int rank_stride,
+                                 const RankDesc *desc, const double *u, TapeList *tapes, long long max_passes, hipStream_t stream);
 hipError_t launch_sc_propose(const KernelConfig &kc, bool force_relocate, const PhotonDev &ph, const HydroDev &hy, LoopState *st,
                              ScState *sc, RngKey key, Cand *block_min, int blocks, Shortlist *sl, ScProposal *out, const ScFold &fold, hipStream_t stream);
 hipError_t launch_sc_resolve(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, ScState *sc, RngKey key,
@@ -95,6 +103,8 @@ hipError_t launch_tape_pass(const KernelConfig &kc, const PhotonDev &ph, const H
 hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key,
                             int n_ranks, int rank_stride, int longest_list, const RankDesc *desc, CsFrame *cs, const CsHookArgs *hook, long long max_passes,
                             int block, hipStream_t stream, const FrameQueueDev *fq, int n_open);
+hipError_t launch_rank_loop_tape(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, int n_ranks, int rank_stride,
+                                 const RankDesc *desc, const double *u, TapeList *tapes, long long max_passes, hipStream_t stream);
 hipError_t launch_sc_propose(const KernelConfig &kc, bool force_relocate, const PhotonDev &ph, const HydroDev &hy, LoopState *st,
                              ScState *sc, RngKey key, Cand *block_min, int blocks, Shortlist *sl, ScProposal *out, const ScFold &fold, hipStream_t stream);
 hipError_t launch_sc_resolve(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, ScState *sc, RngKey key,
@@ -113,6 +123,8 @@ hipError_t launch_tape_pass(const KernelConfig &kc, const PhotonDev &ph, const H
 hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key,
                             int n_ranks, int rank_stride, int longest_list, const RankDesc *desc, CsFrame *cs, const CsHookArgs *hook, long long max_passes,
                             int block, hipStream_t stream, const FrameQueueDev *fq, int n_open);
+hipError_t launch_rank_loop_tape(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, int n_ranks, int rank_stride,
+                                 const RankDesc *desc, const double *u, TapeList *tapes, long long max_passes, hipStream_t stream);
 hipError_t launch_sc_propose(const KernelConfig &kc, bool force_relocate, const PhotonDev &ph, const HydroDev &hy, LoopState *st,
                              ScState *sc, RngKey key, Cand *block_min, int blocks, Shortlist *sl, ScProposal *out, const ScFold &fold, hipStream_t stream);
 hipError_t launch_sc_resolve(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, ScState *sc, RngKey key,
@@ -160,6 +172,12 @@ hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const H
                             int block, hipStream_t stream, const FrameQueueDev *fq, int n_open)
 {
     MCRAT_ROUTE(launch_rank_loop, kc, ph, hy, states, key, n_ranks, rank_stride, longest_list, desc, cs, hook, max_passes, block, stream, fq, n_open);
+}
+
+hipError_t launch_rank_loop_tape(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, int n_ranks, int rank_stride,
+                                 const RankDesc *desc, const double *u, TapeList *tapes, long long max_passes, hipStream_t stream)
+{
+    MCRAT_ROUTE(launch_rank_loop_tape, kc, ph, hy, states, key, n_ranks, rank_stride, desc, u, tapes, max_passes, stream);
 }
 
 hipError_t launch_sc_propose(const KernelConfig &kc, bool force_relocate, const PhotonDev &ph, const HydroDev &hy, LoopState *st,

@@ -266,6 +266,8 @@ SYMBOLS = {
     "mcrat_hip_shared_clock_exchange_wait": (C.c_int, [_ctx]),
     "mcrat_hip_set_rng_tape": (C.c_int, [_ctx, _dp, C.c_longlong]),
     "mcrat_hip_rng_tape_position": (C.c_int, [_ctx, C.POINTER(C.c_longlong), _ip]),
+    "mcrat_hip_pool_set_rng_tapes": (C.c_int, [_ctx, C.POINTER(_dp), C.POINTER(C.c_longlong)]),
+    "mcrat_hip_pool_rng_tape_positions": (C.c_int, [_ctx, C.POINTER(C.c_longlong), _ip]),
     "mcrat_hip_shared_clock_exchange": (C.c_int, [_ctx]),
     "mcrat_hip_shared_clock_reset_exchange": (C.c_int, [_ctx]),
     "mcrat_hip_shared_clock_buffers": (C.c_int, [_ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
@@ -744,6 +746,26 @@ class Engine:
         pos, out = C.c_longlong(0), C.c_int(0)
         self._check(self.lib.mcrat_hip_rng_tape_position(self.ctx, C.byref(pos), C.byref(out)), "rng_tape_position")
         return pos.value, bool(out.value)
+
+    def pool_set_rng_tapes(self, tapes):
+        """one recorded stream per list of the pool (float64 arrays of uniforms in [0,1), consumed as set_rng_tape consumes one); None for a
+        list that keeps its keyed streams.  Replaces every list's tape and starts them at position 0; all None: the pool is keyed again"""
+        tapes = list(tapes)
+        R = getattr(self, "n_pool_ranks", len(tapes))        # (a view or a context without lists: the library refuses the call)
+        if len(tapes) != R:
+            raise ValueError("pool_set_rng_tapes: %d tapes for %d lists" % (len(tapes), R))
+        arrs = [None if t is None else _f8(t).ravel() for t in tapes]
+        ptrs = (_dp * R)(*[(a.ctypes.data_as(_dp) if a is not None and a.size else None) for a in arrs])
+        n = (C.c_longlong * R)(*[(int(a.size) if a is not None else 0) for a in arrs])
+        self._check(self.lib.mcrat_hip_pool_set_rng_tapes(self.ctx, ptrs, n), "pool_set_rng_tapes")
+
+    def pool_rng_tape_positions(self):
+        """-> (positions, ran_out): numpy arrays over the lists of the pool (entries read so far; whether a list needed more than its tape holds)"""
+        R = getattr(self, "n_pool_ranks", 0)
+        pos, out = np.zeros(max(R, 1), dtype=np.int64)[:R], np.zeros(max(R, 1), dtype=np.int32)[:R]
+        self._check(self.lib.mcrat_hip_pool_rng_tape_positions(self.ctx, pos.ctypes.data_as(C.POINTER(C.c_longlong)), out.ctypes.data_as(_ip)),
+                    "pool_rng_tape_positions")
+        return pos, out.astype(bool)
 
     def begin_frame(self, seed, time_now, remaining_time):
         self._check(self.lib.mcrat_hip_begin_frame(self.ctx, int(seed), float(time_now), float(remaining_time)), "begin_frame")
