@@ -1137,6 +1137,40 @@ __device__ __attribute__((noinline)) void copy_list_columns(double *r0, unsigned
     }
 }
 
+// The restore of a list whose per-pass columns live in LDS during the frame (ListCols<MASK>): those columns go from the snapshot (+from) straight into
+// the LDS copy, every other column (and the type) to the live lists.  The live copy of the LDS columns is not written: nobody reads it during the
+// frame (the accessors go to LDS) and the loop's epilogue stores all of them when the launch leaves the list, finished or not.  As copy_list_columns:
+// all of a slot's loads in flight before its first store, and a function of its own for the same reason.
+template <unsigned MASK>
+__device__ __attribute__((noinline)) void restore_list_columns_lds(double *r0, unsigned col_stride, int *idx, unsigned char *flags, char *type, int base,
+                                                                   int n, long long from, unsigned char *lds, int lds_slots, int tid, int block)
+{
+    using Cols = ListCols<MASK>;
+    static_assert((MASK & COLBIT_IDX) && (MASK & COLBIT_FLAGS), "idx and flags are among the LDS columns");
+    typedef __attribute__((address_space(3))) unsigned char *LdsBytes;
+    typedef __attribute__((address_space(3))) double *LdsDoubles;
+    typedef __attribute__((address_space(3))) int *LdsInts;
+    const LdsBytes l = (LdsBytes)lds;
+    for (int il = tid; il < n; il += block) {
+        const size_t i = (size_t)base + il;
+        double v[N_DOUBLE_COLS];
+#pragma unroll
+        for (int k = 0; k < N_DOUBLE_COLS; ++k)
+            v[k] = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(r0 + (size_t)k * col_stride + i) + from);
+        const int ci = *reinterpret_cast<const int *>(reinterpret_cast<const char *>(idx + i) + from);
+        const unsigned char cf = *reinterpret_cast<const unsigned char *>(reinterpret_cast<const char *>(flags + i) + from);
+        const char ct = *(reinterpret_cast<const char *>(type + i) + from);
+#pragma unroll
+        for (int k = 0; k < N_DOUBLE_COLS; ++k) {
+            if (Cols::in_lds(k)) ((LdsDoubles)l)[Cols::lds_pos(k) * lds_slots + il] = v[k];
+            else r0[(size_t)k * col_stride + i] = v[k];
+        }
+        ((LdsInts)(l + Cols::lds_idx_bytes(lds_slots)))[il] = ci;
+        (l + Cols::lds_flags_bytes(lds_slots))[il] = cf;
+        type[i] = ct;
+    }
+}
+
 struct RankLayout {
     int n_ranks;
     int stride;           // slots reserved per rank
@@ -1278,9 +1312,20 @@ __global__ __launch_bounds__(RANK_BLOCK, RANK_WAVES_PER_SIMD) void rank_loop_ker
         }
         return;
     }
+    // Lean restore (the queue builds keep all the per-pass columns in LDS): those columns go from the snapshot straight into LDS and only the others
+    // to the live lists (restore_list_columns_lds) -- no live copy written and read back, no barrier and no second sweep in front of the first pass.
+    // Not for cyclo-synchrotron lists: settle_pass_limit and the hook's hand-over read idx and type of the live lists.
+    [[maybe_unused]] bool lean_restored = false;
     if (fresh && lay.fq.restore) {                           // the frame starts from the snapshot of the list (mcrat_hip_restore_photons, for this list)
-        copy_list_columns(gph.r0, gph.col_stride, gph.idx, gph.flags, gph.type, base, n, lay.fq.snap_delta, 0, tid, RANK_BLOCK);
-        __syncthreads();
+#ifndef MCRAT_NO_LEAN_RESTORE
+        if constexpr (QUEUE && RESIDENT && RANK_BLOCK == 256) lean_restored = lay.cs == nullptr;
+#endif
+        if (lean_restored) {
+            restore_list_columns_lds<LIST_MASK_FULL>(gph.r0, gph.col_stride, gph.idx, gph.flags, gph.type, base, n, lay.fq.snap_delta, s_dyn, lds_slots, tid, RANK_BLOCK);
+        } else {
+            copy_list_columns(gph.r0, gph.col_stride, gph.idx, gph.flags, gph.type, base, n, lay.fq.snap_delta, 0, tid, RANK_BLOCK);
+            __syncthreads();
+        }
     }
     // Cyclo-synchrotron lists double when they run out of null slots (photons.c:112-121), so half of a list can be null slots behind the
     // last photon.  A null slot takes no part in a pass -- no cell, never the earliest candidate, time_to_scatter = 1e12/c every time
@@ -1326,16 +1371,18 @@ __global__ __launch_bounds__(RANK_BLOCK, RANK_WAVES_PER_SIMD) void rank_loop_ker
     static_assert(Cols::lds_bytes_per_slot == (RESIDENT ? (size_t)rank_lds_bytes_per_slot(RANK_BLOCK) : 0), "launch_rank_loop sizes the dynamic LDS with this");
     const Cols ph(gph, RESIDENT ? s_dyn : nullptr, lds_slots, base);
     if constexpr (RESIDENT) {
-        for (int il = tid; il < n; il += EVENT_BLOCK) {
-            const int i = base + il;
-            ph.r0(i) = ph.template gcol<COL_R0>(i); ph.r1(i) = ph.template gcol<COL_R1>(i); ph.r2(i) = ph.template gcol<COL_R2>(i);
-            ph.ntau(i) = ph.template gcol<COL_NTAU>(i);
-            if constexpr (FULL_HOT) {
-                ph.u0(i) = ph.template gcol<COL_U0>(i); ph.u1(i) = ph.template gcol<COL_U1>(i); ph.u2(i) = ph.template gcol<COL_U2>(i);
-                ph.idx(i) = ph.g_idx_at(i); ph.flags(i) = ph.g_flags_at(i);
+        if (!lean_restored) {                                // (a lean restore has filled the LDS copy; the barrier behind the first draws covers it)
+            for (int il = tid; il < n; il += EVENT_BLOCK) {
+                const int i = base + il;
+                ph.r0(i) = ph.template gcol<COL_R0>(i); ph.r1(i) = ph.template gcol<COL_R1>(i); ph.r2(i) = ph.template gcol<COL_R2>(i);
+                ph.ntau(i) = ph.template gcol<COL_NTAU>(i);
+                if constexpr (FULL_HOT) {
+                    ph.u0(i) = ph.template gcol<COL_U0>(i); ph.u1(i) = ph.template gcol<COL_U1>(i); ph.u2(i) = ph.template gcol<COL_U2>(i);
+                    ph.idx(i) = ph.g_idx_at(i); ph.flags(i) = ph.g_flags_at(i);
+                }
             }
+            __syncthreads();
         }
-        __syncthreads();
     }
     // The free-path draws of a pass -- one Philox block per slot pair, log(u+) per slot (mclib.c:675-680; rng.hpp) -- depend on the pass number
     // and the slot alone, not on what the event before it does: the wavefronts that sit out the event walk (three of four; the walk is one
@@ -1359,6 +1406,8 @@ __global__ __launch_bounds__(RANK_BLOCK, RANK_WAVES_PER_SIMD) void rank_loop_ker
     if constexpr (SHADOW) {
         draw_logs(st.iteration, 0, EVENT_BLOCK);             // the first pass of this launch: nobody has drawn for it
         __syncthreads();
+    } else {
+        if (lean_restored) __syncthreads();                  // (the LDS copy is complete)
     }
     RANK_TICK(0);
 

@@ -77,6 +77,12 @@ struct ListCols {
     __device__ __forceinline__ double &gcol(int i) const { return base[(unsigned)K * stride + (unsigned)i]; }
     template <int K>
     static constexpr bool in_lds() { return ((MASK >> K) & 1u) != 0; }
+    // the LDS layout by itself, for code that fills the copy without an accessor (restore_list_columns_lds, kernels.hip): double column k sits
+    // lds_pos(k) * lds_slots doubles in, the idx column lds_idx_bytes(lds_slots) bytes, the flags lds_flags_bytes(lds_slots) bytes
+    static constexpr bool in_lds(int k) { return ((MASK >> k) & 1u) != 0; }
+    static constexpr int lds_pos(int k) { return __builtin_popcount(MASK & ((1u << k) - 1u)); }
+    static constexpr size_t lds_idx_bytes(int slots) { return (size_t)n_lds_doubles * slots * sizeof(double); }
+    static constexpr size_t lds_flags_bytes(int slots) { return lds_idx_bytes(slots) + ((MASK & COLBIT_IDX) ? (size_t)slots * sizeof(int) : 0); }
 
 #define MCRAT_X(name, K) __device__ __forceinline__ double &name(int i) const { return dcol<K>(i); }
     MCRAT_DOUBLE_COLS(MCRAT_X)
