@@ -738,7 +738,29 @@ int mcrat_hip_pool_rng_tape_positions(mcrat_hip_ctx *pool, long long *position /
  *   THERMAL_ELECTRON_WAVE  the same through the wavefront-wide sampler the event walk uses (one wavefront per row)
  *   ELECTRON_AND_SCATTER   in  temp, ph[4], s[4]                     out el[4], ph'[4], s'[4], occurred    singleThermalElectron then
  *                                                                    singleScatter (mcrat_scattering.c:151) on one stream; STOKES as the context's
- * Random numbers of row i: the engine's event stream {seed, iteration i, slot 0, the context's rng_stream} (rng.hpp). */
+ * The arithmetic forms the loop kernels use instead (physics.hpp, device_types.hpp; tests/test_gpu_loop_arithmetic.py compares them with
+ * extended precision).  Every entry calls the function the loop calls:
+ *   RCP_NR, RSQRT_NR, SQRT_NR   in  x                                 out 1/x, 1/sqrt(x), sqrt(x)   hardware estimate + two Newton steps
+ *   CELL_OPERANDS          in  a, b, c, gamma_cell, dens_lab         out w, nsig, gam, kf, kf_of_gamma(gam)   cell_staged_operands as the
+ *                                                                    device staging calls it; (a, b, c) the cell's velocity record
+ *   BOOST_WITH_PHOTON      in  b[3], g, kf, p[4]                     out p'[4]                  boost_with<true>: g, kf as given, zero_norm_lean'ed
+ *   BOOST_WITH_ELECTRON    in  b[3], g, kf, p[4]                     out p'[4]                  boost_with<false>
+ *   BOOST_STAGED_PHOTON    in  b[3], p[4]                            out p'[4]                  boost_with<true> with gam of cell_staged_operands(b)
+ *                                                                    and kf_of_gamma(gam): what a re-location runs
+ *   OPTICAL_DEPTH_STAGED   in  beta[3] (Cartesian), gamma_cell, dens_lab, p[3], norm   out tau, ntau    optical_depth_staged on the operands of
+ *                                                                    cell_staged_operands(beta, gamma_cell, dens_lab); ntau = -rcp_nr(tau)
+ *   AZIMUTH                in  x, y                                  out c, s, c_h, s_h         cos_sin_of_atan2(y, x); cos_sin_with_hypot(y, x, h)
+ *                                                                    with h = sqrt(x*x + y*y) as hydro_coords hands it over
+ *   HYDRO_COORDS           in  x, y, z                               out a0, a1, a2             hydro_coords<DIMENSIONS, geometry> of the context
+ *                                                                    (mcratCoordinateToHydroCoordinate, geometry.c:15; -1 where an axis is absent)
+ *   THERMAL_CROSS_SECTION  in  photon_comv_e, fluid_temp             out norm, fallback, eps, theta   thermal_cross_section_lookup on the context's
+ *                                                                    table: fallback = 1 where the loop would integrate afresh at (eps, theta),
+ *                                                                    else 0, 0, 0; norm = 1, 0, 0, 0 on a context without a table (DIRECT).
+ *                                                                    MCRAT_HIP_EINVAL while mcrat_hip_create_hot_cross_section runs on the context
+ *                                                                    in another thread (a courtesy: a context stays one thread at a time)
+ *   KN_CROSS_SECTION_IEEE  in  energy_ratio                          out sigma / sigma_T        kn_cross_section_ieee (the reference's divisions)
+ * Random numbers of row i: the engine's event stream {seed, iteration i, slot 0, the context's rng_stream} (rng.hpp).
+ * fn outside [1, MCRAT_HIP_FN_COUNT): MCRAT_HIP_EINVAL. */
 #define MCRAT_HIP_FN_KN_CROSS_SECTION       1
 #define MCRAT_HIP_FN_LORENTZ_BOOST_PHOTON   2
 #define MCRAT_HIP_FN_LORENTZ_BOOST_ELECTRON 3
@@ -746,6 +768,19 @@ int mcrat_hip_pool_rng_tape_positions(mcrat_hip_ctx *pool, long long *position /
 #define MCRAT_HIP_FN_THERMAL_ELECTRON       5
 #define MCRAT_HIP_FN_THERMAL_ELECTRON_WAVE  6
 #define MCRAT_HIP_FN_ELECTRON_AND_SCATTER   7
+#define MCRAT_HIP_FN_RCP_NR                 8
+#define MCRAT_HIP_FN_RSQRT_NR               9
+#define MCRAT_HIP_FN_SQRT_NR               10
+#define MCRAT_HIP_FN_CELL_OPERANDS         11
+#define MCRAT_HIP_FN_BOOST_WITH_PHOTON     12
+#define MCRAT_HIP_FN_BOOST_WITH_ELECTRON   13
+#define MCRAT_HIP_FN_BOOST_STAGED_PHOTON   14
+#define MCRAT_HIP_FN_OPTICAL_DEPTH_STAGED  15
+#define MCRAT_HIP_FN_AZIMUTH               16
+#define MCRAT_HIP_FN_HYDRO_COORDS          17
+#define MCRAT_HIP_FN_THERMAL_CROSS_SECTION 18
+#define MCRAT_HIP_FN_KN_CROSS_SECTION_IEEE 19
+#define MCRAT_HIP_FN_COUNT                 20   /* one past the last code */
 int mcrat_hip_eval_function(mcrat_hip_ctx *ctx, int fn, int n, const double *in, double *out, uint64_t seed);
 
 /* per-frame reductions on the resident photons ------------------------------- */

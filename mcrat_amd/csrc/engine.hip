@@ -83,6 +83,7 @@ struct mcrat_hip_ctx {
     int hot_fallback_calls = 500000;   // hot_x_section.c:348
     double hot_grid[4] = {0, 0, 0, 0};          // log10 photon energy min/max, log10 theta min/max
     int *d_table_fallbacks = nullptr;
+    int hot_creating = 0;              // a thread is inside mcrat_hip_create_hot_cross_section on this context (read and written atomically)
 
     // loop
     LoopState *d_state = nullptr;
@@ -395,9 +396,11 @@ extern "C" int mcrat_hip_create_hot_cross_section(mcrat_hip_ctx *c, double *ther
     double *d = nullptr;
     HIPCHK(c, hipMalloc((void **)&d, count * sizeof(double)));
     HotTableParams p{n_ph_e, n_t, log_ph_e_min, log_ph_e_max, log_t_min, log_t_max, calls, (unsigned long long)seed};
+    __atomic_store_n(&c->hot_creating, 1, __ATOMIC_RELEASE);      // mcrat_hip_eval_function refuses THERMAL_CROSS_SECTION meanwhile
     hipError_t e = launch_hot_table(p, d, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(thermal_table, d, count * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    __atomic_store_n(&c->hot_creating, 0, __ATOMIC_RELEASE);
     (void)hipFree(d);
     HIPCHK(c, e);
     return MCRAT_HIP_OK;
@@ -4274,14 +4277,21 @@ extern "C" int mcrat_hip_avg_energy(mcrat_hip_ctx *c, double *erg)
 
 extern "C" int mcrat_hip_eval_function(mcrat_hip_ctx *c, int fn, int n, const double *in, double *out, uint64_t seed)
 {
-    static const int in_w[8] = {0, 1, 7, 7, 13, 5, 5, 9}, out_w[8] = {0, 1, 4, 4, 4, 4, 4, 13};
-    if (!c || n <= 0 || !in || !out || fn < 1 || fn > 7) return MCRAT_HIP_EINVAL;
+    // row widths by code (include/mcrat_hip.h): 1-7 the reference-shaped functions, 8-19 the loop's own forms
+    static const int in_w[MCRAT_HIP_FN_COUNT] = {0, 1, 7, 7, 13, 5, 5, 9, 1, 1, 1, 5, 9, 9, 7, 9, 2, 3, 2, 1};
+    static const int out_w[MCRAT_HIP_FN_COUNT] = {0, 1, 4, 4, 4, 4, 4, 13, 1, 1, 1, 5, 4, 4, 4, 2, 4, 3, 4, 1};
+    if (!c || n <= 0 || !in || !out || fn < 1 || fn >= MCRAT_HIP_FN_COUNT) return MCRAT_HIP_EINVAL;
+    // A courtesy beyond the contract (one context, one thread at a time): a look-up asked for while another thread is inside
+    // mcrat_hip_create_hot_cross_section on this context is refused.  That call writes a scratch buffer and the caller's array only, never the
+    // context's table, so the answer would be the look-up on whatever table the context held before -- rarely what a caller in the middle of
+    // making a table means.  (No last_error here: the other thread may be writing it.)
+    if (fn == MCRAT_HIP_FN_THERMAL_CROSS_SECTION && __atomic_load_n(&c->hot_creating, __ATOMIC_ACQUIRE)) return MCRAT_HIP_EINVAL;
     const size_t bi = sizeof(double) * (size_t)in_w[fn] * (size_t)n, bo = sizeof(double) * (size_t)out_w[fn] * (size_t)n;
     double *d_in = nullptr, *d_out = nullptr;
     HIPCHK(c, hipMalloc((void **)&d_in, bi));
     if (hipMalloc((void **)&d_out, bo) != hipSuccess) { (void)hipFree(d_in); return MCRAT_HIP_ENOMEM; }
     hipError_t e = hipMemcpyAsync(d_in, in, bi, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = launch_eval_function(fn, c->kc.stokes, n, d_in, d_out, seed, c->key.stream, c->stream);
+    if (e == hipSuccess) e = launch_eval_function(c->kc, c->hy, fn, n, d_in, d_out, seed, c->key.stream, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, bo, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     (void)hipFree(d_in);

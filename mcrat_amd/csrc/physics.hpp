@@ -38,6 +38,11 @@ __device__ __forceinline__ double rcp_nr(double x) { return 1.0 / x; }
 __device__ __forceinline__ double rsqrt_nr(double x) { return 1.0 / sqrt(x); }
 __device__ __forceinline__ double sqrt_nr(double x) { return sqrt(x); }
 #else
+// Supported domain of rcp_nr: +-0, +-inf, NaN (the hardware's answers) and every normal x, where the result is within 1 spacing of
+// the correctly rounded one, subnormal results (|x| > 2^1022) included.  A subnormal x whose reciprocal is finite
+// (2^-1024 < |x| < 2^-1022) is outside it: within 1 spacing as well, except next to the largest double, where the estimate itself
+// (the hardware's v_rcp_f64) overflows and is returned as it is -- 1/x comes back as +-inf there.
+// (The loop's arguments are optical depths per cm, 1e-30 and up, Lorentz factors and energies.)
 __device__ __forceinline__ double rcp_nr(double x)
 {
     const double r0 = __builtin_amdgcn_rcp(x);
@@ -47,6 +52,14 @@ __device__ __forceinline__ double rcp_nr(double x)
     r = fma(r, e, r);
     return (fabs(r0) < INFINITY && r0 != 0.0) ? r : r0;     // 1/0, 1/inf, NaN: the hardware's answer (+-inf, +-0, NaN)
 }
+// Supported domain of rsqrt_nr and sqrt_nr: x = 0 and every NORMAL x (2^-1022 <= x), where the result is within 2 spacings of the
+// correctly rounded one (tests/test_gpu_loop_arithmetic.py).
+// Outside it:
+//   x = inf        rsqrt_nr gives 0, as 1/sqrt does, but sqrt_nr gives inf * 0 = NaN where sqrt gives inf.  No caller passes it.
+//   subnormal x    x = m 2^-1074: h = 0.5 * x is rounded to a multiple of 2^-1074 (m = 1: to 0), a relative error d with |d| <= 1/m,
+//                  and two Newton steps towards 1/sqrt(2h) leave |-d/2 + 3d^2/8 - 5d^3/16 + d^4/16| <= 1.25/m of relative error --
+//                  finite and positive, no more.
+// The loop never gets there: its arguments are squared momenta (>= 1e-60), squared radii and 1 - v^2 >= 1e-7.
 __device__ __forceinline__ double rsqrt_nr(double x)
 {
     const double y0 = __builtin_amdgcn_rsq(x);
@@ -247,6 +260,14 @@ __device__ __forceinline__ void beta_from_record(double a, double b, double c, d
 }
 
 // cos and sin of atan2(y, x) without the angle (atan2(0,0) = 0 -> (1,0))
+// Range: x*x + y*y must neither overflow nor lose bits to underflow -- max(|x|, |y|) < 2^511 (6.7e153), and hypot(x, y) >= 2^-484
+// (4e-146), from where on a square that has gone subnormal lies below half an ulp of the sum; between 2^-511 and 2^-484 the error grows,
+// below 2^-537 the sum is 0 and the point counts as (0, 0).  The same range holds for cos_sin_with_hypot through the caller's
+// sqrt(x*x + y*y).  (The loop's radii are 1e6 to 1e17 cm, its photon momenta 1e-20 to 1e-15 g cm/s.)
+// Zeros: off the origin s = y * (1/h) keeps y's sign on a zero, as sin(atan2(+-0, x)) does.  AT the origin the sine is the literal +0
+// whatever the sign of y, where sin(atan2(-0, +-0)) is -0: the cosine (+-1 by the sign of x, signed zero included) is atan2's, the
+// sine's zero sign is not.  Harmless: the sine only multiplies a velocity or momentum component that is added to another term
+// (beta_from_record; the rotations of single_scatter), and x + (-0) == x + (+0) for every x but -0.
 // (written with selects, not branches, like zero_norm and lorentz_boost below: the values are the same, and a thread that takes several
 // photons through these functions in lockstep -- relocate_lockstep, kernels.hip -- gets one straight-line block to interleave)
 __device__ __forceinline__ void cos_sin_of_atan2(double y, double x, double &c, double &s)
@@ -379,8 +400,10 @@ __device__ __forceinline__ int table_cell(double x0, double dx, int n_cells, dou
     return i;
 }
 
-// kleinNishinaCrossSection (mcrat_scattering.c:597-623) with the reference's own divisions: 2e6-sized terms cancel to O(1) at the 1e-3 seam, so where the
-// value enters an optical depth (below) it is computed in the reference's operation order (kn_cross_section's reciprocals are for the acceptance test)
+// kleinNishinaCrossSection (mcrat_scattering.c:597-623) with the reference's own divisions, in the reference's operation order: where the value enters
+// an optical depth (below) it is the reference's bits at the 1e-3 seam, where 2e6-sized terms cancel to O(1) (kn_cross_section's reciprocals are for
+// the acceptance test).  It is NOT closer to the exact value than kn_cross_section: both take log(fl(1 + 2e)) times 1/e^3, and that shared rounding
+// (1/(2e) roundings of the largest term) dwarfs what the divisions save (tests/test_gpu_loop_arithmetic.py).
 __device__ __forceinline__ double kn_cross_section_ieee(double e)
 {
     if (e >= 1e-3)

@@ -951,7 +951,11 @@ class Engine:
         return int(self.lib.mcrat_hip_device_bytes(self.ctx))
 
     FN = dict(kn_cross_section=(1, 1, 1), lorentz_boost_photon=(2, 7, 4), lorentz_boost_electron=(3, 7, 4), stokes_rotation=(4, 13, 4),
-              thermal_electron=(5, 5, 4), thermal_electron_wave=(6, 5, 4), electron_and_scatter=(7, 9, 13))
+              thermal_electron=(5, 5, 4), thermal_electron_wave=(6, 5, 4), electron_and_scatter=(7, 9, 13),
+              # the loop's own arithmetic forms (include/mcrat_hip.h; tests/test_gpu_loop_arithmetic.py)
+              rcp_nr=(8, 1, 1), rsqrt_nr=(9, 1, 1), sqrt_nr=(10, 1, 1), cell_operands=(11, 5, 5), boost_with_photon=(12, 9, 4),
+              boost_with_electron=(13, 9, 4), boost_staged_photon=(14, 7, 4), optical_depth_staged=(15, 9, 2), azimuth=(16, 2, 4),
+              hydro_coords=(17, 3, 3), thermal_cross_section=(18, 2, 4), kn_cross_section_ieee=(19, 1, 1))
 
     def eval_function(self, name, rows, seed=0):
         """one device function of physics.hpp on an array of argument rows (mcrat_hip_eval_function); returns the result rows"""

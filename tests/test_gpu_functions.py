@@ -4,7 +4,9 @@ vectors of tests/golden/functions.npz and on the edge cases a trajectory reaches
 (mcrat_scattering.c:610), a fluid at rest and gamma = 100 in lorentzBoost (mclib.c:302), photon directions along the flow and along
 z in stokesRotation (mcrat_scattering.c:103), both sides of the 1e7 K switch of singleThermalElectron (electron.c:208), unpolarised
 light in kleinNishinaScatter (mcrat_scattering.c:548).  Tolerances: no random numbers 1e-13; sampled quantities 1e-11 (the same
-stream on both sides; the accepted sample is the same one, its value differs by libm's last ulps through a few boosts)."""
+stream on both sides; the accepted sample is the same one, its value differs by libm's last ulps through a few boosts).
+The arithmetic forms the loop kernels themselves call (boost_with, cell_staged_operands, optical_depth_staged, rcp_nr / rsqrt_nr / sqrt_nr, the
+azimuth selects, hydro_coords, the table look-up) are in tests/test_gpu_loop_arithmetic.py, against extended precision."""
 import ctypes as C
 import os
 
