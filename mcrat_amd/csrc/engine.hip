@@ -127,8 +127,12 @@ struct mcrat_hip_ctx {
     std::vector<int> snap_lens;       // the lists' lengths when mcrat_hip_snapshot_photons was taken
     RankDesc *d_desc = nullptr;
     RankDesc *h_desc = nullptr;       // pinned
-    void *d_fq = nullptr, *h_fq = nullptr;   // the frame queue's block (mcrat_hip_pool_run_frames): ticket, frames_done, order, items, records; pinned mirror
+    void *d_fq = nullptr, *h_fq = nullptr;   // the frame queue's block (mcrat_hip_pool_run_frames): order, items, hydro frames, list descriptions, ticket, frames_done, records; pinned mirror
     size_t fq_bytes = 0;
+    std::vector<int> fq_first, fq_last, fq_hy_of_frame, fq_stalled;   // ... and that call's scratch, kept from call to call
+    std::vector<HydroDev> fq_hyv;
+    std::vector<const mcrat_hip_ctx *> fq_hy_ctx;
+    RankDeviceInfo dev{0, 0};         // the context's device and its CU count, read once (mcrat_hip_init); cus == 0: not known, the launchers ask
     mcrat_hip_ctx *parent = nullptr;  // this context is the view of list view_rank of `parent`
     int view_rank = -1;
     uint32_t view_stream = 0;
@@ -229,6 +233,8 @@ extern "C" int mcrat_hip_init(mcrat_hip_ctx **out, const mcrat_hip_config *cfg)
     mcrat_hip_ctx *c = new (std::nothrow) mcrat_hip_ctx();
     if (!c) return MCRAT_HIP_ENOMEM;
     c->cfg = *cfg;
+    c->dev.device = cfg->device;
+    if (hipDeviceGetAttribute(&c->dev.cus, hipDeviceAttributeMultiprocessorCount, cfg->device) != hipSuccess || c->dev.cus < 0) { (void)hipGetLastError(); c->dev.cus = 0; }
     if (c->cfg.iterations_per_sync <= 0) c->cfg.iterations_per_sync = 256;
     c->kc.dimensions = cfg->dimensions;
     c->kc.geometry = cfg->geometry;
@@ -2412,6 +2418,35 @@ static void state_to_stats(const LoopState &h, long long slots, mcrat_hip_frame_
     s->time_now = h.time_now;
 }
 
+// the same from a frame queue's record (launch.hpp, FrameRecord)
+static void record_to_stats(const FrameRecord &h, long long slots, mcrat_hip_frame_stats *s)
+{
+    memset(s, 0, sizeof *s);
+    s->iterations = h.iterations;
+    s->photon_steps = h.iterations * slots;
+    s->slot_steps = h.slot_steps;
+    s->frame_scatt_cnt = h.frame_scatt_cnt;
+    s->num_photons_find_new_element = h.n_relocated;
+    s->not_found = h.not_found;
+    s->kn_rejections = h.kn_rejections;
+    s->rescans = h.rescans;
+    s->last_scattered_index = h.last_scattered_index;
+    s->last_scattered_temp = h.last_scattered_temp;
+    s->last_time_step = h.last_time_step;
+    s->remaining_time = h.remaining_time;
+    s->time_now = h.time_now;
+}
+
+// ... and the host's copy of a list's LoopState as the frame that left the record left it: everything the host reads of it (state_to_stats, done); the
+// members only the kernel uses stay on the device (states[rank]), the state of a finished frame holds no pending advance
+static void record_to_state(const FrameRecord &h, LoopState *s)
+{
+    memset(s, 0, sizeof *s);
+    s->remaining_time = h.remaining_time; s->time_now = h.time_now; s->done = h.done; s->skip_idx = -1; s->last_scattered_index = h.last_scattered_index;
+    s->last_time_step = h.last_time_step; s->last_scattered_temp = h.last_scattered_temp; s->iterations = h.iterations; s->frame_scatt_cnt = h.frame_scatt_cnt;
+    s->n_relocated = h.n_relocated; s->not_found = h.not_found; s->kn_rejections = h.kn_rejections; s->rescans = h.rescans; s->slot_steps = h.slot_steps;
+}
+
 static int rank_slots(const mcrat_hip_ctx *c, int r)
 {
     if (c->is_pool) return c->h_desc[r].len;
@@ -2850,6 +2885,20 @@ static int ensure_events(mcrat_hip_ctx *c, size_t n);
 // are too long to keep in LDS, or the frames are optically thin: a thin frame is a dozen passes in which half the photons
 // change cell, i.e. slow-path throughput per list, and there 256 threads per list do better.  The engine cannot know the
 // optical depth before it has run a frame; it looks at the previous one (passes per list).
+// the device as the context has known it since its creation (a view asks its pool's)
+static const RankDeviceInfo *device_info(const mcrat_hip_ctx *c)
+{
+    if (c->dev.cus <= 0 && c->parent) c = c->parent;
+    return c->dev.cus > 0 ? &c->dev : nullptr;
+}
+static int device_cus(const mcrat_hip_ctx *c)
+{
+    if (const RankDeviceInfo *d = device_info(c)) return d->cus;
+    int cus = 256, dev = 0;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    return cus;
+}
+
 static void choose_rank_block(mcrat_hip_ctx *c)
 {
     if (const char *e = getenv("MCRAT_HIP_RANK_BLOCK")) {
@@ -2858,8 +2907,7 @@ static void choose_rank_block(mcrat_hip_ctx *c)
         if (const char *f = getenv("MCRAT_HIP_RANK_FUSE")) c->rank_fuse = atoi(f) != 0;
         return;
     }
-    int cus = 256, dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int cus = device_cus(c);
     const bool many = c->n_ranks > 2 * cus && longest_rank_list(c) <= 1024;
     // ... and, whatever the frame looks like, when there are many times more lists than the device holds at once: four lists per CU then
     // overlap one list's walk with the others' passes all the time (10 246 lists, thin frames: cfg2 5.70 -> 4.96 ms, cfg3 8.44 -> 7.08 ms;
@@ -2912,7 +2960,7 @@ static int run_ranks(mcrat_hip_ctx *c, long long max_iterations, mcrat_hip_frame
                                             c->stream));
         else
             HIPCHK(c, launch_rank_loop(c->kc, c->ph, c->hy, c->d_rstates, c->key, c->n_ranks, c->rank_stride, longest, c->is_pool ? c->d_desc : nullptr, nullptr, nullptr,
-                                       batch, c->rank_block + (c->rank_fuse ? 1000 : 0), c->stream));
+                                       batch, c->rank_block + (c->rank_fuse ? 1000 : 0), c->stream, nullptr, 0, device_info(c)));
         if (c->cfg.profile) {
             HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
             HIPCHK(c, hipEventSynchronize(c->ev[1]));
@@ -2962,9 +3010,13 @@ extern "C" int mcrat_hip_pool_run_frames(mcrat_hip_ctx *c, const mcrat_hip_frame
     }
     // the staged hydro frames of the plan: index 0 the pool's own, then every other context named in plan->hydro (it keeps its frame staged while the
     // call runs; same switches as the pool -- its HydroDev is handed to the pool's kernels as it is)
-    std::vector<HydroDev> hyv(1, c->hy);
-    std::vector<const mcrat_hip_ctx *> hy_ctx(1, c);
-    std::vector<int> hy_of_frame((size_t)p->n_frames, 0);
+    // (the call's scratch lives on the context: no allocation per call once a plan of this size has been seen)
+    std::vector<HydroDev> &hyv = c->fq_hyv;
+    std::vector<const mcrat_hip_ctx *> &hy_ctx = c->fq_hy_ctx;
+    std::vector<int> &hy_of_frame = c->fq_hy_of_frame;
+    hyv.assign(1, c->hy);
+    hy_ctx.assign(1, c);
+    hy_of_frame.assign((size_t)p->n_frames, 0);
     if (p->hydro)
         for (int f = 0; f < p->n_frames; ++f) {
             const mcrat_hip_ctx *o = p->hydro[f];
@@ -2985,18 +3037,60 @@ extern "C" int mcrat_hip_pool_run_frames(mcrat_hip_ctx *c, const mcrat_hip_frame
     if (N > 0x7fffffffull) return MCRAT_HIP_EINVAL;
     // MCRAT_HIP_QUEUE_TIMING=1: where the call's host time goes, on stderr (development aid)
     static const bool timing = getenv("MCRAT_HIP_QUEUE_TIMING") && atoi(getenv("MCRAT_HIP_QUEUE_TIMING")) != 0;
+    // MCRAT_HIP_QUEUE_HOST_RECORDS=1 (A/B): the kernel stores the records straight into the pinned host block instead of device memory + one copy back
+    static const bool host_records = getenv("MCRAT_HIP_QUEUE_HOST_RECORDS") && atoi(getenv("MCRAT_HIP_QUEUE_HOST_RECORDS")) != 0;
     auto clock_us = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double tq0 = clock_us();
     double tq_filled = 0, tq_launched = 0, tq_synced = 0, tq_a = 0, tq_b = 0, tq_c = 0;
-    // the lists that take part, each in one run of consecutive frames
-    std::vector<int> first((size_t)R, -1), last((size_t)R, -1);
+    size_t bytes_up = 0, bytes_down = 0;
+    // The queue's block, device memory with a pinned mirror laid out alike: [order N | items N | hydro frames | list descriptions R] are only uploaded,
+    // [ticket | frames_done R] go both ways, [records N] only come back -- so one launch is ONE copy up ([0, off_rec)) and ONE copy down ([off_ticket, bytes)).
+    const size_t off_items = align_up(sizeof(int) * N, 64), off_hy = align_up(off_items + sizeof(FrameItem) * N, 256);
+    const size_t off_desc = align_up(off_hy + sizeof(HydroDev) * hyv.size(), 64), off_ticket = align_up(off_desc + sizeof(RankDesc) * (size_t)R, 256);
+    const size_t off_done = off_ticket + sizeof(unsigned) * FRAME_QUEUE_XCDS * FRAME_TICKET_STRIDE;
+    const size_t off_rec = align_up(off_done + sizeof(unsigned) * (size_t)R, 256), bytes = off_rec + sizeof(FrameRecord) * N;
+    if (c->fq_bytes < bytes) {
+        if (c->d_fq) { HIPCHK(c, hipFree(c->d_fq)); c->d_fq = nullptr; }
+        if (c->h_fq) { HIPCHK(c, hipHostFree(c->h_fq)); c->h_fq = nullptr; }
+        c->fq_bytes = 0;
+        HIPCHK(c, hipMalloc(&c->d_fq, bytes));
+        HIPCHK(c, hipHostMalloc(&c->h_fq, bytes, hipHostMallocDefault));
+        c->fq_bytes = bytes;
+    }
+    char *hb = static_cast<char *>(c->h_fq), *db = static_cast<char *>(c->d_fq);
+    unsigned *h_tickets = reinterpret_cast<unsigned *>(hb + off_ticket), *h_done = reinterpret_cast<unsigned *>(hb + off_done);
+    int *h_order = reinterpret_cast<int *>(hb);
+    FrameItem *h_items = reinterpret_cast<FrameItem *>(hb + off_items);
+    RankDesc *h_qdesc = reinterpret_cast<RankDesc *>(hb + off_desc);
+    FrameRecord *h_rec = reinterpret_cast<FrameRecord *>(hb + off_rec);
+    tq_a = clock_us();
+    // One pass over the plan: the lists that take part, each in one run of consecutive frames; the items (every member written: nothing of the staging
+    // block is cleared but the ticket and frames_done words); the open items per XCD.
+    // Which XCD a list belongs to: list r to XCD r % 8, where one launch per frame puts it too.  (Measured against contiguous eighths of the lists --
+    // neighbouring lists hold photons of neighbouring cells, so an XCD's L2 would have an eighth of the cells to hold: 0.567 against 0.52 ms per frame
+    // on the benchmark frame, the eighths differ in optical depth and the launch ends with the slowest XCD.)
+    auto list_class = [&](int r) { return r % FRAME_QUEUE_XCDS; };
+    int xcd_of_class[FRAME_QUEUE_XCDS];                      // which XCD's queue the lists of class k are in (identity unless an XCD turned out to start no workgroups)
+    for (int x = 0; x < FRAME_QUEUE_XCDS; ++x) xcd_of_class[x] = x;
+    int count[FRAME_QUEUE_XCDS] = {0};
+    std::vector<int> &first = c->fq_first, &last = c->fq_last;
+    first.assign((size_t)R, -1);
+    last.assign((size_t)R, -1);
     for (int f = 0; f < F; ++f) {
-        const int *open_f = p->open + (size_t)f * R;
+        const size_t t0 = (size_t)f * R;
+        const int hydro_f = hy_of_frame[(size_t)f];
         for (int r = 0; r < R; ++r) {
-            if (!open_f[r]) continue;
+            const size_t t = t0 + r;
+            FrameItem &it = h_items[t];
+            it.seed = p->seeds[t]; it.time_now = p->time_now[t]; it.remaining_time = p->remaining_time[t];
+            it.frame_end = p->frame_end ? p->frame_end[t] : 0.0;
+            it.open = p->open[t] ? 1 : 0;
+            it.hydro = hydro_f;
+            if (!it.open) continue;
             if (first[r] < 0) first[r] = f;
             else if (last[r] != f - 1) { c->last_error = "pool_run_frames: a list's open frames must be consecutive"; return MCRAT_HIP_EINVAL; }
             last[r] = f;
+            count[list_class(r)] += 1;
         }
     }
     for (int r = 0; r < R; ++r) {
@@ -3011,54 +3105,35 @@ extern "C" int mcrat_hip_pool_run_frames(mcrat_hip_ctx *c, const mcrat_hip_frame
                 return MCRAT_HIP_ESTATE;
             }
     }
-    for (int r = 0; r < R; ++r) {
+    for (int r = 0; r < R; ++r) {                            // (the queue's kernel reads the block's copy; the context's host copy is what the launch form is chosen from)
         const mcrat_hip_ctx *v = c->views[(size_t)r];
         RankDesc d{};
         if (first[r] >= 0) { d.len = v->ph.n; d.stream = v->key.stream; d.seed = p->seeds[(size_t)first[r] * R + r]; }
         c->h_desc[r] = d;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->d_desc, c->h_desc, sizeof(RankDesc) * (size_t)R, hipMemcpyHostToDevice, c->stream));
-    // the queue's block: [ticket | frames_done R | order N | items N] (uploaded per launch) then the records (read back)
-    const size_t off_done = 64 * FRAME_QUEUE_XCDS, off_order = align_up(off_done + sizeof(unsigned) * (size_t)R, 64), off_items = align_up(off_order + sizeof(int) * N, 64);
-    const size_t off_hy = align_up(off_items + sizeof(FrameItem) * N, 256);
-    const size_t off_rec = align_up(off_hy + sizeof(HydroDev) * hyv.size(), 256), bytes = off_rec + sizeof(LoopState) * N;
-    if (c->fq_bytes < bytes) {
-        if (c->d_fq) { HIPCHK(c, hipFree(c->d_fq)); c->d_fq = nullptr; }
-        if (c->h_fq) { HIPCHK(c, hipHostFree(c->h_fq)); c->h_fq = nullptr; }
-        c->fq_bytes = 0;
-        HIPCHK(c, hipMalloc(&c->d_fq, bytes));
-        HIPCHK(c, hipHostMalloc(&c->h_fq, bytes, hipHostMallocDefault));
-        c->fq_bytes = bytes;
-    }
-    tq_a = clock_us();
-    char *hb = static_cast<char *>(c->h_fq), *db = static_cast<char *>(c->d_fq);
-    unsigned *h_done = reinterpret_cast<unsigned *>(hb + off_done);
-    int *h_order = reinterpret_cast<int *>(hb + off_order);
-    FrameItem *h_items = reinterpret_cast<FrameItem *>(hb + off_items);
-    LoopState *h_rec = reinterpret_cast<LoopState *>(hb + off_rec);
-    memset(hb, 0, off_rec);
-    for (size_t t = 0; t < N; ++t) {
-        FrameItem &it = h_items[t];
-        it.seed = p->seeds[t]; it.time_now = p->time_now[t]; it.remaining_time = p->remaining_time[t];
-        it.frame_end = p->frame_end ? p->frame_end[t] : 0.0;
-        it.open = p->open[t] ? 1 : 0;
-        it.hydro = hy_of_frame[t / (size_t)R];
+        h_qdesc[r] = d;
     }
     memcpy(hb + off_hy, hyv.data(), sizeof(HydroDev) * hyv.size());
+    memset(hb + off_ticket, 0, off_rec - off_ticket);        // ticket, frames_done
     tq_b = clock_us();
-    HIPCHK(c, hipMemsetAsync(db + off_rec, 0, sizeof(LoopState) * N, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_table_fallbacks, 0, sizeof(int), c->stream));
     // TAU_CALCULATION == TABLE: a frame's off-table look-ups count on the context its hydro frame is staged on (HydroDev::table_fallbacks); every
-    // such counter starts the call from zero and the call reports their sum
-    for (const HydroDev &h : hyv)
-        if (c->kc.table && h.table_fallbacks) HIPCHK(c, hipMemsetAsync(h.table_fallbacks, 0, sizeof(int), c->stream));
+    // such counter starts the call from zero and the call reports their sum (DIRECT: no kernel touches the counters and nobody reads them)
+    if (c->kc.table) {
+        HIPCHK(c, hipMemsetAsync(c->d_table_fallbacks, 0, sizeof(int), c->stream));
+        for (const HydroDev &h : hyv)
+            if (h.table_fallbacks) HIPCHK(c, hipMemsetAsync(h.table_fallbacks, 0, sizeof(int), c->stream));
+    }
     if (!c->rank_block_fixed) { choose_rank_block(c); c->rank_block_fixed = true; }
     tq_c = clock_us();
     FrameQueueDev fq{};
     fq.n_frames = F; fq.restore = p->restore_each_frame ? 1 : 0; fq.chain_clock = p->chain_clock ? 1 : 0;
-    fq.ticket = reinterpret_cast<unsigned *>(db); fq.frames_done = reinterpret_cast<unsigned *>(db + off_done);
-    fq.order = reinterpret_cast<const int *>(db + off_order); fq.items = reinterpret_cast<const FrameItem *>(db + off_items);
-    fq.records = reinterpret_cast<LoopState *>(db + off_rec);
+    fq.ticket = reinterpret_cast<unsigned *>(db + off_ticket); fq.frames_done = reinterpret_cast<unsigned *>(db + off_done);
+    fq.order = reinterpret_cast<const int *>(db); fq.items = reinterpret_cast<const FrameItem *>(db + off_items);
+    fq.records = reinterpret_cast<FrameRecord *>(db + off_rec);
+    if (host_records) {                                      // (the pinned block as the device sees it)
+        void *mapped = nullptr;
+        HIPCHK(c, hipHostGetDevicePointer(&mapped, c->h_fq, 0));
+        fq.records = reinterpret_cast<FrameRecord *>(static_cast<char *>(mapped) + off_rec);
+    }
     fq.hydro = reinterpret_cast<const HydroDev *>(db + off_hy);
     fq.snap_delta = p->restore_each_frame ? (long long)(static_cast<char *>(c->ph_snap) - static_cast<char *>(c->ph_buf)) : 0;
     c->cap_frames = 0;
@@ -3082,24 +3157,24 @@ extern "C" int mcrat_hip_pool_run_frames(mcrat_hip_ctx *c, const mcrat_hip_frame
     if (const char *e = getenv("MCRAT_HIP_RANK_LAUNCH_CAP")) per_frame_cap = atoll(e) > 0 ? atoll(e) : per_frame_cap;
     const int longest = longest_rank_list(c);
     c->prof_step_ms = 0; c->prof_launches = 0;
-    // Which XCD a list belongs to: list r to XCD r % 8, where one launch per frame puts it too.  (Measured against contiguous eighths of the lists --
-    // neighbouring lists hold photons of neighbouring cells, so an XCD's L2 would have an eighth of the cells to hold: 0.567 against 0.52 ms per frame
-    // on the benchmark frame, the eighths differ in optical depth and the launch ends with the slowest XCD.)
-    auto list_class = [&](int r) { return r % FRAME_QUEUE_XCDS; };
-    int xcd_of_class[FRAME_QUEUE_XCDS];                      // which XCD's queue the lists of class k are in (identity unless an XCD turned out to start no workgroups)
-    for (int x = 0; x < FRAME_QUEUE_XCDS; ++x) xcd_of_class[x] = x;
-    std::vector<unsigned> tickets((size_t)FRAME_QUEUE_XCDS * FRAME_TICKET_STRIDE);
     bool one_by_one = getenv("MCRAT_HIP_NO_FRAME_QUEUE") && atoi(getenv("MCRAT_HIP_NO_FRAME_QUEUE")) != 0;      // (A/B: the plan frame by frame)
     one_by_one = one_by_one || c->d_pool_tapes != nullptr;              // (a pool that holds tapes: the tape build has no queue form)
+    // the frame of each list that a launch of this call left at its pass limit (-1: none): the one frame in progress whose record may be read
+    // (FrameRecord's validity rule); it stays that until frames_done has moved past it
+    std::vector<int> &stalled = c->fq_stalled;
+    stalled.assign((size_t)R, -1);
     for (int attempt = 0; !one_by_one; ++attempt) {
         // the open items in the order they are taken: per XCD (list r belongs to XCD r % 8: a list never changes L2) frame-major; one workgroup per item,
         // and as the hardware deals workgroups round-robin over the XCDs, eight times the longest XCD's list of them
         int n_open = 0, longest_xcd = 0;
         {
-            int count[FRAME_QUEUE_XCDS] = {0}, fill[FRAME_QUEUE_XCDS];
-            for (int f = 0; f < F; ++f)
-                for (int r = 0; r < R; ++r)
-                    if (h_items[(size_t)f * R + r].open) count[xcd_of_class[list_class(r)]] += 1;
+            int fill[FRAME_QUEUE_XCDS];
+            if (attempt > 0) {                               // (a relaunch: what is still open, in the queues the XCDs that exist draw from)
+                for (int x = 0; x < FRAME_QUEUE_XCDS; ++x) count[x] = 0;
+                for (int f = 0; f < F; ++f)
+                    for (int r = 0; r < R; ++r)
+                        if (h_items[(size_t)f * R + r].open) count[xcd_of_class[list_class(r)]] += 1;
+            }
             for (int x = 0; x < FRAME_QUEUE_XCDS; ++x) {
                 fq.order_off[x] = fill[x] = n_open;
                 n_open += count[x];
@@ -3114,21 +3189,24 @@ extern "C" int mcrat_hip_pool_run_frames(mcrat_hip_ctx *c, const mcrat_hip_frame
         if (n_groups == 0) break;                            // (no list opens a frame: the call has only sized the queue's buffers)
         tq_filled = clock_us();
         HIPCHK(c, hipMemcpyAsync(db, hb, off_rec, hipMemcpyHostToDevice, c->stream));
+        bytes_up += off_rec;
         if (c->cfg.profile) {
             int rc = ensure_events(c, 2);
             if (rc) return rc;
             HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
         }
         {
-            const hipError_t le = launch_rank_loop(c->kc, c->ph, c->hy, c->d_rstates, c->key, R, c->rank_stride, longest, c->d_desc, nullptr, nullptr, per_frame_cap,
-                                                   c->rank_block + (c->rank_fuse ? 1000 : 0), c->stream, &fq, n_groups);
+            const hipError_t le = launch_rank_loop(c->kc, c->ph, c->hy, c->d_rstates, c->key, R, c->rank_stride, longest, reinterpret_cast<const RankDesc *>(db + off_desc),
+                                                   nullptr, nullptr, per_frame_cap, c->rank_block + (c->rank_fuse ? 1000 : 0), c->stream, &fq, n_groups, device_info(c));
             if (le == hipErrorNotSupported && attempt == 0) { one_by_one = true; break; }      // no queue build of this launch form (kernels.hip)
             HIPCHK(c, le);
         }
         if (c->cfg.profile) HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-        HIPCHK(c, hipMemcpyAsync(tickets.data(), db, sizeof(unsigned) * tickets.size(), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(h_done, db + off_done, sizeof(unsigned) * (size_t)R, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(h_rec, db + off_rec, sizeof(LoopState) * N, hipMemcpyDeviceToHost, c->stream));
+        {   // tickets, frames_done and the records in one copy (records the kernel stored into the pinned block itself: the first two alone)
+            const size_t down = (host_records ? off_rec : bytes) - off_ticket;
+            HIPCHK(c, hipMemcpyAsync(hb + off_ticket, db + off_ticket, down, hipMemcpyDeviceToHost, c->stream));
+            bytes_down += down;
+        }
         tq_launched = clock_us();
         HIPCHK(c, hipStreamSynchronize(c->stream));
         tq_synced = clock_us();
@@ -3140,22 +3218,24 @@ extern "C" int mcrat_hip_pool_run_frames(mcrat_hip_ctx *c, const mcrat_hip_frame
         }
         bool all = true;
         for (int r = 0; r < R; ++r) {
-            if (h_done[r] & FRAME_STALLED) h_done[r] &= ~FRAME_STALLED;            // (the frame that ran into the pass limit = the frames before it are through)
+            // (the frame that ran into the pass limit = the frames before it are through)
+            if (h_done[r] & FRAME_STALLED) { h_done[r] &= ~FRAME_STALLED; stalled[(size_t)r] = (int)h_done[r]; }
             all = all && (first[r] < 0 || (int)h_done[r] == last[r] + 1);
         }
         if (all) break;
         {   // a device whose workgroups report fewer XCDs than eight (another partition mode): the queues nobody drew from move to XCDs that exist
             int alive[FRAME_QUEUE_XCDS], n_alive = 0;
             for (int x = 0; x < FRAME_QUEUE_XCDS; ++x)
-                if (tickets[(size_t)x * FRAME_TICKET_STRIDE] > 0) alive[n_alive++] = x;
+                if (h_tickets[(size_t)x * FRAME_TICKET_STRIDE] > 0) alive[n_alive++] = x;
             if (n_alive == 0) { c->last_error = "pool_run_frames: no workgroup drew an item"; return MCRAT_HIP_EHIP; }
             for (int k = 0; k < FRAME_QUEUE_XCDS; ++k)
-                if (tickets[(size_t)xcd_of_class[k] * FRAME_TICKET_STRIDE] == 0) xcd_of_class[k] = alive[k % n_alive];
+                if (h_tickets[(size_t)xcd_of_class[k] * FRAME_TICKET_STRIDE] == 0) xcd_of_class[k] = alive[k % n_alive];
         }
         if (attempt >= 1 << 16) { c->last_error = "pool_run_frames: lists that make no progress"; return MCRAT_HIP_EHIP; }
         // Lists whose frame ran into the launch's pass limit (and their later frames, whose workgroups gave up): their finished frames leave the queue, the
         // frame in progress goes on from its LoopState (open = 2), the rest as planned -- with the clock the host now knows.
-        memset(hb, 0, off_done);                                                   // ticket
+        // Only records this call is known to have written are read (FrameRecord): the stalled frame's, and those of frames that are through.
+        memset(h_tickets, 0, sizeof(unsigned) * FRAME_QUEUE_XCDS * FRAME_TICKET_STRIDE);
         for (int r = 0; r < R; ++r) {
             if (first[r] < 0) continue;
             const int nf = std::max((int)h_done[r], first[r]);                     // the first frame that is not complete
@@ -3163,8 +3243,8 @@ extern "C" int mcrat_hip_pool_run_frames(mcrat_hip_ctx *c, const mcrat_hip_frame
                 FrameItem &it = h_items[(size_t)f * R + r];
                 if (f < nf) { it.open = 0; continue; }
                 if (f > nf) continue;
-                const LoopState &rec = h_rec[(size_t)f * R + r];
-                if (rec.iterations > 0 && !rec.done) it.open = 2;
+                const FrameRecord &rec = h_rec[(size_t)f * R + r];
+                if (stalled[(size_t)r] == nf && rec.iterations > 0 && !rec.done) it.open = 2;
                 else if (p->chain_clock && f > first[r]) {                         // (its previous frame has left the queue: the clock it would have read there)
                     it.time_now = h_rec[(size_t)(f - 1) * R + r].time_now;
                     it.remaining_time = it.frame_end - it.time_now;
@@ -3220,7 +3300,7 @@ extern "C" int mcrat_hip_pool_run_frames(mcrat_hip_ctx *c, const mcrat_hip_frame
                                                     c->d_pool_tapes, per_frame_cap, c->stream));
                 else
                     HIPCHK(c, launch_rank_loop(c->kc, c->ph, hyv[(size_t)hy_of_frame[(size_t)f]], c->d_rstates, c->key, R, c->rank_stride, longest, c->d_desc, nullptr,
-                                               nullptr, per_frame_cap, c->rank_block + (c->rank_fuse ? 1000 : 0), c->stream));
+                                               nullptr, per_frame_cap, c->rank_block + (c->rank_fuse ? 1000 : 0), c->stream, nullptr, 0, device_info(c)));
                 if (c->cfg.profile) HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
                 HIPCHK(c, hipMemcpyAsync(c->h_rstates, c->d_rstates, sizeof(LoopState) * (size_t)R, hipMemcpyDeviceToHost, c->stream));
                 HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3230,14 +3310,17 @@ extern "C" int mcrat_hip_pool_run_frames(mcrat_hip_ctx *c, const mcrat_hip_frame
                 if (done) break;
             }
             for (int r = 0; r < R; ++r)
-                if (op[(size_t)r]) h_rec[(size_t)f * R + r] = c->h_rstates[r];
+                if (op[(size_t)r]) h_rec[(size_t)f * R + r].from_state(c->h_rstates[r]);
             if (c->cap_frames > 0 && f < F - 1)               // the pool as frame f leaves it
                 HIPCHK(c, hipMemcpyAsync(static_cast<char *>(c->ph_cap) + (size_t)f * c->ph_bytes, c->ph_buf, c->ph_bytes, hipMemcpyDeviceToDevice, c->stream));
         }
+        // the lists' descriptions as a queue launch leaves them: every list of the plan with its length, also one that sat the last frame out
+        // (mcrat_hip_rank_stats prices a list's passes with it)
+        for (int r = 0; r < R; ++r) c->h_desc[r] = h_qdesc[r];
     }
     for (size_t t = 0; t < N; ++t) {
         const int r = (int)(t % (size_t)R);
-        if (p->open[t]) state_to_stats(h_rec[t], c->views[(size_t)r]->ph.n, &stats[t]);
+        if (p->open[t]) record_to_stats(h_rec[t], c->views[(size_t)r]->ph.n, &stats[t]);
         else memset(&stats[t], 0, sizeof stats[t]);
     }
     // the pool as after the last frame's mcrat_hip_run
@@ -3255,7 +3338,7 @@ extern "C" int mcrat_hip_pool_run_frames(mcrat_hip_ctx *c, const mcrat_hip_frame
         v->frame_open = true;
         v->prof_step_ms = v->prof_event_ms = 0;
         v->prof_launches = 0;
-        c->h_rstates[r] = h_rec[t];
+        record_to_state(h_rec[t], &c->h_rstates[r]);          // (the host's copy of the list's state: what the statistics and `done` are read from)
         it_sum += h_rec[t].iterations;
         lists += 1;
     }
@@ -3277,8 +3360,9 @@ extern "C" int mcrat_hip_pool_run_frames(mcrat_hip_ctx *c, const mcrat_hip_frame
         stats[0].table_fallbacks = fallbacks;
     }
     if (timing)
-        fprintf(stderr, "pool_run_frames: %d frames x %d lists: plan -> queue %.0f us (checks %.0f, items %.0f, memsets + block choice %.0f, order %.0f), upload + launch calls %.0f us, waiting for the device %.0f us (kernel %.0f us), records -> stats %.0f us\n",
-                F, R, tq_filled - tq0, tq_a - tq0, tq_b - tq_a, tq_c - tq_b, tq_filled - tq_c, tq_launched - tq_filled, tq_synced - tq_launched, 1e3 * c->prof_step_ms, clock_us() - tq_synced);
+        fprintf(stderr, "pool_run_frames: %d frames x %d lists: plan -> queue %.0f us (checks %.0f, items %.0f, memsets + block choice %.0f, order %.0f), upload + launch calls %.0f us, waiting for the device %.0f us (kernel %.0f us), records -> stats %.0f us; %zu B up, %zu B down in %lld launch(es)%s\n",
+                F, R, tq_filled - tq0, tq_a - tq0, tq_b - tq_a, tq_c - tq_b, tq_filled - tq_c, tq_launched - tq_filled, tq_synced - tq_launched, 1e3 * c->prof_step_ms, clock_us() - tq_synced,
+                bytes_up, bytes_down, c->prof_launches, host_records ? ", records stored into the pinned block" : "");
     return MCRAT_HIP_OK;
 }
 
@@ -3845,8 +3929,7 @@ extern "C" int mcrat_hip_pool_scatter_frames_cyclosynch(mcrat_hip_ctx *c, const 
     // lists that change length: columns stay in HBM/L2 (longest = the window), so LDS does not limit the lists per CU; with more than
     // two lists per CU the 128-thread workgroups put four on one (cfg5 at 1e7 photons: 420 -> 380 ms per frame)
     {
-        int cus = 256, dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        const int cus = device_cus(c);
         c->rank_block = R > 2 * cus ? 128 : 256;
         // ... and with eight and more per CU one wavefront per list (eight on a CU): no wave ever waits at a barrier for the one that walks
         // the event (cfg5: 250 -> 230 ms per frame); only with the hook inside the loop (the hook kernel is written for 128 threads and more)
@@ -3874,7 +3957,7 @@ extern "C" int mcrat_hip_pool_scatter_frames_cyclosynch(mcrat_hip_ctx *c, const 
         }
         for (int k = 0; k < pairs_per_sync; ++k) {
             HIPCHK(c, launch_rank_loop(c->kc, c->ph, c->hy, c->d_rstates, c->key, R, c->rank_stride, 1 << 30, c->d_desc, d_cf, d_args, 4096, c->rank_block,
-                                       c->stream));
+                                       c->stream, nullptr, 0, device_info(c)));
             if (hook_kernel) HIPCHK(c, launch_cs_replace_pool(p, c->hy, c->hcol, c->d_rstates, c->ph, c->rank_stride, R, c->d_desc, d_cf, c->stream));
         }
         if (c->cfg.profile) {

@@ -19,7 +19,9 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <algorithm>
+#include <mutex>
 #include <type_traits>
+#include <vector>
 #include "device_types.hpp"
 #include "launch.hpp"
 #include "sc_exchange.hpp"
@@ -1299,7 +1301,7 @@ __global__ __launch_bounds__(RANK_BLOCK, RANK_WAVES_PER_SIMD) void rank_loop_ker
     }
     __syncthreads();
     if (st.done || n <= 0) {
-        if (item >= 0 && tid == 0) { states[rank] = st; lay.fq.records[item] = st; }
+        if (item >= 0 && tid == 0) { states[rank] = st; lay.fq.records[item].from_state(st); }
         // a frame with no time left (remaining_time <= 0) still leaves the list as the frame-by-frame path does: restored from the snapshot, and
         // in its frame's capture (fresh, st.done and n come from the item and LDS: the branch is the whole workgroup's, as the copies need)
         if (fresh && n > 0) {
@@ -1835,7 +1837,7 @@ __global__ __launch_bounds__(RANK_BLOCK, RANK_WAVES_PER_SIMD) void rank_loop_ker
             st.nseg = 0; st.skip_idx = -1;
             if (st.last_scattered_index >= 0) st.last_scattered_index -= idx_shift;
             states[rank] = st;
-            if (item >= 0) lay.fq.records[item] = st;
+            if (item >= 0) lay.fq.records[item].from_state(st);
             if constexpr (TAPE) lay.tapes[rank].cursor = tl->cursor;
         }
         // the list as this frame leaves it, for the frame's outputs (printPhotons, saveCheckpoint: mcrat.c:881-906), before its next frame moves it on
@@ -2620,9 +2622,51 @@ hipError_t launch_tape_pass(const KernelConfig &kc, const PhotonDev &ph, const H
 #ifndef RANK_SMALL
 #define RANK_SMALL 128                 // threads of the small workgroup (block == 128 below); -DRANK_SMALL=64 for the A/B of one-wave lists
 #endif
+// What the runtime has been asked about a kernel of this translation unit on a device.  The dynamic-LDS limit is the kernel's, not a context's: every
+// context of the process launches the same kernel, so the note is the process's (a context's own note would go stale when another context set a smaller
+// size).  The limit is only ever raised -- a launch may use less than the limit -- and the occupancy is kept for the LDS size it was asked for last.
+struct KernelNote { const void *kernel; int device, max_dyn, occ_dyn, per_cu; };
+static std::mutex g_kernel_notes_lock;
+static std::vector<KernelNote> g_kernel_notes;
+static KernelNote &kernel_note(const void *kernel, int device)      // (with the lock held)
+{
+    for (KernelNote &k : g_kernel_notes)
+        if (k.kernel == kernel && k.device == device) return k;
+    g_kernel_notes.push_back(KernelNote{kernel, device, -1, -1, 0});
+    return g_kernel_notes.back();
+}
+static int launch_device(const RankDeviceInfo *dev)
+{
+    int d = 0;
+    if (dev) return dev->device;
+    if (hipGetDevice(&d) != hipSuccess) { (void)hipGetLastError(); d = 0; }
+    return d;
+}
+// hipFuncSetAttribute(.., hipFuncAttributeMaxDynamicSharedMemorySize, dyn), unless the kernel's limit on this device is known to be at least dyn
+static hipError_t allow_dynamic_lds(const void *kernel, int device, int dyn)
+{
+    std::lock_guard<std::mutex> hold(g_kernel_notes_lock);
+    KernelNote &k = kernel_note(kernel, device);
+    if (k.max_dyn >= dyn) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, dyn);
+    if (e == hipSuccess) k.max_dyn = dyn;
+    return e;
+}
+// workgroups of `threads` threads and `dyn` bytes of dynamic LDS that one CU holds (0: the runtime would not say)
+static int resident_per_cu(const void *kernel, int device, int threads, size_t dyn)
+{
+    std::lock_guard<std::mutex> hold(g_kernel_notes_lock);
+    KernelNote &k = kernel_note(kernel, device);
+    if (k.occ_dyn == (int)dyn) return k.per_cu;
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, dyn) != hipSuccess || per_cu <= 0) { (void)hipGetLastError(); return 0; }
+    k.occ_dyn = (int)dyn; k.per_cu = per_cu;
+    return per_cu;
+}
+
 hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key,
                             int n_ranks, int rank_stride, int longest_list, const RankDesc *desc, CsFrame *cs, const CsHookArgs *hook, long long max_passes,
-                            int block, hipStream_t stream, const FrameQueueDev *fq, int n_open)
+                            int block, hipStream_t stream, const FrameQueueDev *fq, int n_open, const RankDeviceInfo *dev)
 {
     // block: 64, 128, 256 or 512 threads per list, + 1000 for the build with the fused pass
     const bool fuse = block >= 1000;
@@ -2666,15 +2710,14 @@ hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const H
             // runs the plan frame by frame (engine.hip, mcrat_hip_pool_run_frames)
             if (block != 256 || lds_slots <= 0) return;
             auto launch_q = [&](auto kernel) {
-                if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) { (void)hipGetLastError(); return; }
+                const int device = launch_device(dev);
+                if (allow_dynamic_lds(reinterpret_cast<const void *>(kernel), device, (int)dyn) != hipSuccess) { (void)hipGetLastError(); return; }
                 // persistent workgroups: as many as the device holds at once (they are dealt to the XCDs round-robin, an eighth each); more would only
                 // start, find their queue empty and leave
-                int per_cu = 0, cus = 256, dev = 0, grid = n_open;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(kernel), 256, dyn) == hipSuccess && per_cu > 0 &&
-                    hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
-                    grid = std::min(n_open, per_cu * cus);
-                else
-                    (void)hipGetLastError();
+                int cus = dev ? dev->cus : 0, grid = n_open;
+                const int per_cu = resident_per_cu(reinterpret_cast<const void *>(kernel), device, 256, dyn);
+                if (cus <= 0 && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) { (void)hipGetLastError(); cus = 0; }
+                if (per_cu > 0 && cus > 0) grid = std::min(n_open, per_cu * cus);
                 kernel<<<dim3(grid), dim3(256), dyn, stream>>>(ph, hy, states, key, lay, max_passes, lds_slots);
                 queue_launched = true;
             };
@@ -2690,8 +2733,7 @@ hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const H
             return;
         }
         auto launch = [&](auto kernel, auto kernel_global, int threads) {
-            if (lds_slots > 0 &&
-                hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) == hipSuccess) {
+            if (lds_slots > 0 && allow_dynamic_lds(reinterpret_cast<const void *>(kernel), launch_device(dev), (int)dyn) == hipSuccess) {
                 kernel<<<dim3(grid), dim3(threads), dyn, stream>>>(ph, hy, states, key, lay, max_passes, lds_slots);
             } else {
                 (void)hipGetLastError();

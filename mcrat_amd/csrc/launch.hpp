@@ -51,8 +51,31 @@ struct FrameItem {                   // list r in frame f: item f * n_ranks + r
     int open;                        // the list takes part in this frame (a rank joins at its injection frame, mcrat.c:566-700)
     int hydro;                       // which staged hydro frame of the launch it propagates through
 };
+// What a (frame, list) item leaves for the host: the members of LoopState that mcrat_hip_frame_stats shows (engine.hip, state_to_stats) and `done` -- not
+// the pending segments, the shortlist's estimates or the diagnostic stamps, which only the kernel reads (a stalled list resumes from states[rank], a full
+// LoopState).  One lane stores it when the item's frame ends, complete or at the launch's pass limit, and when a frame has no time left.
+// VALIDITY.  The records' buffer is never cleared, so a record means something only for an item the kernel is KNOWN to have written in this call, and the
+// host decides that from frames_done[list] alone (read back with the records): with d = frames_done & ~FRAME_STALLED, the list's open items of frames
+// < d are complete and their records written; with FRAME_STALLED set, so is the record of frame d (iterations > 0, done == 0: the frame goes on with
+// open = 2); every later item of the list gave up or was never drawn, wrote nothing, and its record holds whatever an earlier call left there.
+struct alignas(32) FrameRecord {
+    double remaining_time, time_now;
+    long long iterations;
+    int done;
+    int last_scattered_index;
+    double last_time_step, last_scattered_temp;
+    long long frame_scatt_cnt, n_relocated;
+    long long not_found, kn_rejections, rescans, slot_steps;
+    __host__ __device__ void from_state(const LoopState &s)
+    {
+        remaining_time = s.remaining_time; time_now = s.time_now; iterations = s.iterations; done = s.done; last_scattered_index = s.last_scattered_index;
+        last_time_step = s.last_time_step; last_scattered_temp = s.last_scattered_temp; frame_scatt_cnt = s.frame_scatt_cnt; n_relocated = s.n_relocated;
+        not_found = s.not_found; kn_rejections = s.kn_rejections; rescans = s.rescans; slot_steps = s.slot_steps;
+    }
+};
+static_assert(sizeof(FrameRecord) <= 128, "the frame record stays compact: at most half a LoopState");
 struct FrameQueueDev {
-    int n_frames;                    // 0: no queue -- one workgroup per list, one frame, as before
+    int n_frames;                  // 0: no queue -- one workgroup per list, one frame, as before
     int restore;                     // every frame starts from the context's snapshot (mcrat_hip_snapshot_photons; benchmarks: the same work every frame)
     int chain_clock;                 // a list's clock carries over from its previous frame of this launch (time_now of the LoopState it left)
     int pad;
@@ -62,16 +85,21 @@ struct FrameQueueDev {
     unsigned *frames_done;           // [n_ranks] f + 1 once item (f, r) is complete; FRAME_STALLED | f: frame f ran into the launch's pass limit
     const FrameItem *items;          // [n_frames * n_ranks]
     const HydroDev *hydro;           // [n_hydro] the staged hydro frames of the launch (FrameItem::hydro indexes it); read through the constant address space
-    LoopState *records;              // [n_frames * n_ranks] the LoopState every frame ended with
+    FrameRecord *records;            // [n_frames * n_ranks] what every frame ended with (see FrameRecord for which of them may be read)
     long long snap_delta;            // bytes from a column of the live lists to its copy in the snapshot (restore)
     long long capture_delta, capture_stride;   // != 0: at the end of frame f < n_frames - 1 the list's columns are copied to live + capture_delta + f * capture_stride
 };
 constexpr unsigned FRAME_STALLED = 0x80000000u;
 constexpr int FRAME_QUEUE_XCDS = 8, FRAME_TICKET_STRIDE = 16;     // (a ticket per XCD, each on a 64-B line of its own)
+// What a context knows about its device from its creation on, so that no launch has to ask again (nullptr: the launcher asks the runtime).
+struct RankDeviceInfo { int device, cus; };
 // `fq` (n_frames > 0, n_open items in fq->order) makes it a queue launch: one workgroup per open item
+// The launcher asks the runtime once per kernel: the dynamic-LDS limit it has set for a kernel and the occupancy it was told for a (kernel, LDS size)
+// are remembered (kernels.hip, KernelNote), so a second launch of the same form makes no hipFuncSetAttribute and no occupancy query.
 hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key,
                             int n_ranks, int rank_stride, int longest_list, const RankDesc *desc, struct CsFrame *cs, const struct CsHookArgs *hook,
-                            long long max_passes, int block, hipStream_t stream, const FrameQueueDev *fq = nullptr, int n_open = 0);
+                            long long max_passes, int block, hipStream_t stream, const FrameQueueDev *fq = nullptr, int n_open = 0,
+                            const RankDeviceInfo *dev = nullptr);
 // The tape build of the rank pool (mcrat_hip_pool_set_rng_tapes): every list of a pool that holds tapes goes through it, whatever choose_rank_block
 // would pick -- 256 threads per list, columns in HBM/L2, no fused pass, no frame queue.  A list with a tape takes its free-path draws and its events'
 // draws from it, in MCRaT's call order, as the one-list tape path does (launch_tape_pass); a list without one draws from its keyed streams exactly as

@@ -16,7 +16,7 @@ hipError_t launch_tape_pass(const KernelConfig &kc, const PhotonDev &ph, const H
                             Cand *block_min, int n_blocks, Shortlist *sl, hipStream_t stream);
 hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key,
                             int n_ranks, int rank_stride, int longest_list, const RankDesc *desc, CsFrame *cs, const CsHookArgs *hook, long long max_passes,
-                            int block, hipStream_t stream, const FrameQueueDev *fq, int n_open);
+                            int block, hipStream_t stream, const FrameQueueDev *fq, int n_open, const RankDeviceInfo *dev);
 hipError_t launch_rank_loop_tape(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, int n_ranks, int rank_stride,
                                  const RankDesc *desc, const double *u, TapeList *tapes, long long max_passes, hipStream_t stream);
 hipError_t launch_sc_propose(const KernelConfig &kc, bool force_relocate, const PhotonDev &ph, const HydroDev &hy, LoopState *st,
@@ -42,7 +42,7 @@ hipError_t launch_tape_pass(const KernelConfig &kc, const PhotonDev &ph, const H
                             Cand *block_min, int n_blocks, Shortlist *sl, hipStream_t stream);
 hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key,
                             int n_ranks, int rank_stride, int longest_list, const RankDesc *desc, CsFrame *cs, const CsHookArgs *hook, long long max_passes,
-                            int block, hipStream_t stream, const FrameQueueDev *fq, int n_open);
+                            int block, hipStream_t stream, const FrameQueueDev *fq, int n_open, const RankDeviceInfo *dev);
 hipError_t launch_rank_loop_tape(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, int n_ranks, int rank_stride,
                                  const RankDesc *desc, const double *u, TapeList *tapes, long long max_passes, hipStream_t stream);
 hipError_t launch_sc_propose(const KernelConfig &kc, bool force_relocate, const PhotonDev &ph, const HydroDev &hy, LoopState *st,
@@ -62,7 +62,7 @@ hipError_t launch_tape_pass(const KernelConfig &kc, const PhotonDev &ph, const H
                             Cand *block_min, int n_blocks, Shortlist *sl, hipStream_t stream);
 hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key,
                             int n_ranks, int rank_stride, int longest_list, const RankDesc *desc, CsFrame *cs, const CsHookArgs *hook, long long max_passes,
-                            int block, hipStream_t stream, const FrameQueueDev *fq, int n_open);
+                            int block, hipStream_t stream, const FrameQueueDev *fq, int n_open, const RankDeviceInfo *dev);
 hipError_t launch_rank_loop_tape(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, int n_ranks, int rank_stride,
                                  const RankDesc *desc, const double *u, TapeList *tapes, long long max_passes, hipStream_t stream);
 hipError_t launch_sc_propose(const KernelConfig &kc, bool force_relocate, const PhotonDev &ph, const HydroDev &hy, LoopState *st,
@@ -82,7 +82,7 @@ hipError_t launch_tape_pass(const KernelConfig &kc, const PhotonDev &ph, const H
                             Cand *block_min, int n_blocks, Shortlist *sl, hipStream_t stream);
 hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key,
                             int n_ranks, int rank_stride, int longest_list, const RankDesc *desc, CsFrame *cs, const CsHookArgs *hook, long long max_passes,
-                            int block, hipStream_t stream, const FrameQueueDev *fq, int n_open);
+                            int block, hipStream_t stream, const FrameQueueDev *fq, int n_open, const RankDeviceInfo *dev);
 hipError_t launch_rank_loop_tape(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, int n_ranks, int rank_stride,
                                  const RankDesc *desc, const double *u, TapeList *tapes, long long max_passes, hipStream_t stream);
 hipError_t launch_sc_propose(const KernelConfig &kc, bool force_relocate, const PhotonDev &ph, const HydroDev &hy, LoopState *st,
@@ -102,7 +102,7 @@ hipError_t launch_tape_pass(const KernelConfig &kc, const PhotonDev &ph, const H
                             Cand *block_min, int n_blocks, Shortlist *sl, hipStream_t stream);
 hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key,
                             int n_ranks, int rank_stride, int longest_list, const RankDesc *desc, CsFrame *cs, const CsHookArgs *hook, long long max_passes,
-                            int block, hipStream_t stream, const FrameQueueDev *fq, int n_open);
+                            int block, hipStream_t stream, const FrameQueueDev *fq, int n_open, const RankDeviceInfo *dev);
 hipError_t launch_rank_loop_tape(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, int n_ranks, int rank_stride,
                                  const RankDesc *desc, const double *u, TapeList *tapes, long long max_passes, hipStream_t stream);
 hipError_t launch_sc_propose(const KernelConfig &kc, bool force_relocate, const PhotonDev &ph, const HydroDev &hy, LoopState *st,
@@ -122,7 +122,7 @@ hipError_t launch_tape_pass(const KernelConfig &kc, const PhotonDev &ph, const H
                             Cand *block_min, int n_blocks, Shortlist *sl, hipStream_t stream);
 hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key,
                             int n_ranks, int rank_stride, int longest_list, const RankDesc *desc, CsFrame *cs, const CsHookArgs *hook, long long max_passes,
-                            int block, hipStream_t stream, const FrameQueueDev *fq, int n_open);
+                            int block, hipStream_t stream, const FrameQueueDev *fq, int n_open, const RankDeviceInfo *dev);
 hipError_t launch_rank_loop_tape(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, int n_ranks, int rank_stride,
                                  const RankDesc *desc, const double *u, TapeList *tapes, long long max_passes, hipStream_t stream);
 hipError_t launch_sc_propose(const KernelConfig &kc, bool force_relocate, const PhotonDev &ph, const HydroDev &hy, LoopState *st,
@@ -169,9 +169,9 @@ hipError_t launch_tape_pass(const KernelConfig &kc, const PhotonDev &ph, const H
 
 hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key,
                             int n_ranks, int rank_stride, int longest_list, const RankDesc *desc, CsFrame *cs, const CsHookArgs *hook, long long max_passes,
-                            int block, hipStream_t stream, const FrameQueueDev *fq, int n_open)
+                            int block, hipStream_t stream, const FrameQueueDev *fq, int n_open, const RankDeviceInfo *dev)
 {
-    MCRAT_ROUTE(launch_rank_loop, kc, ph, hy, states, key, n_ranks, rank_stride, longest_list, desc, cs, hook, max_passes, block, stream, fq, n_open);
+    MCRAT_ROUTE(launch_rank_loop, kc, ph, hy, states, key, n_ranks, rank_stride, longest_list, desc, cs, hook, max_passes, block, stream, fq, n_open, dev);
 }
 
 hipError_t launch_rank_loop_tape(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, int n_ranks, int rank_stride,
