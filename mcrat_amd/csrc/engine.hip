@@ -175,6 +175,7 @@ struct mcrat_hip_ctx {
     } while (0)
 
 static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+static bool env_flag(const char *name) { const char *e = getenv(name); return e && atoi(e) != 0; }      // an environment switch: set, and not to 0
 
 static void drop_graph(mcrat_hip_ctx *c)
 {
@@ -2418,7 +2419,7 @@ static void state_to_stats(const LoopState &h, long long slots, mcrat_hip_frame_
     s->time_now = h.time_now;
 }
 
-// the same from a frame queue's record (launch.hpp, FrameRecord)
+// the same from a frame queue's record (frame_queue.hpp, FrameRecord)
 static void record_to_stats(const FrameRecord &h, long long slots, mcrat_hip_frame_stats *s)
 {
     memset(s, 0, sizeof *s);
@@ -2879,6 +2880,30 @@ static int ensure_graph(mcrat_hip_ctx *c, int batch)
 
 static int ensure_events(mcrat_hip_ctx *c, size_t n);
 
+// cfg.profile: the duration of `launches` launches, between two events, added to prof_step_ms.  `launch` queues them; `wait`, if given, queues what
+// goes behind them and waits for the stream (so that the read-back is in flight before the host waits); either returns an MCRAT_HIP_ code.
+template <class Launch, class Wait>
+static int profiled(mcrat_hip_ctx *c, int launches, Launch &&launch, Wait &&wait)
+{
+    const bool on = c->cfg.profile != 0;
+    int rc = on ? ensure_events(c, 2) : MCRAT_HIP_OK;
+    if (rc) return rc;
+    if (on) HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
+    if ((rc = launch())) return rc;
+    if (on) HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
+    if ((rc = wait())) return rc;
+    if (on) {
+        float ms = 0;
+        HIPCHK(c, hipEventSynchronize(c->ev[1]));
+        HIPCHK(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+        c->prof_step_ms += ms;
+        c->prof_launches += launches;
+    }
+    return MCRAT_HIP_OK;
+}
+template <class Launch>
+static int profiled(mcrat_hip_ctx *c, int launches, Launch &&launch) { return profiled(c, launches, launch, [] { return MCRAT_HIP_OK; }); }
+
 // virtual-rank mode: every launch gives each unfinished list up to `per_launch` passes of its own loop
 // Threads per list (launch.hpp).  Lists per CU is what the virtual-rank kernel's throughput hangs on (kernels.hip), so many
 // lists get 128-thread workgroups, four to a CU -- unless there are too few lists to fill the device that way, or the lists
@@ -2925,6 +2950,25 @@ static void choose_rank_block(mcrat_hip_ctx *c)
     if (const char *e = getenv("MCRAT_HIP_RANK_FUSE")) c->rank_fuse = atoi(e) != 0;
 }
 
+// passes one list may take per launch: bounds one launch to a second or two even for the densest lists (4096: the first 60 frames of
+// tools/lundman_run.py, 9.3e6 scatterings in the first one, 9.3 -> 8.9 s)
+static long long rank_launch_cap()
+{
+    const char *e = getenv("MCRAT_HIP_RANK_LAUNCH_CAP");
+    return e && atoll(e) > 0 ? atoll(e) : 32768;
+}
+
+// a launch of the context's lists in the form chosen for them (choose_rank_block, or the cyclo-synchrotron pool's own choice)
+static RankLaunch rank_launch_of(const mcrat_hip_ctx *c, const RankDesc *desc, long long max_passes)
+{
+    RankLaunch rl;
+    rl.n_ranks = c->n_ranks; rl.rank_stride = c->rank_stride; rl.longest_list = longest_rank_list(c); rl.desc = desc;
+    rl.threads = c->rank_block; rl.fuse = c->rank_fuse;
+    rl.max_passes = max_passes;
+    rl.dev = device_info(c);
+    return rl;
+}
+
 // rank pool: what the kernel needs to know about every list, from its view
 static int pool_describe(mcrat_hip_ctx *c)
 {
@@ -2938,52 +2982,47 @@ static int pool_describe(mcrat_hip_ctx *c)
     return MCRAT_HIP_OK;
 }
 
+// Launch `rl` (its max_passes: the most one launch gives a list) through hydro frame `hy` until every open list is done -- of a pool: every window
+// with a list in it, h_desc[r].len > 0 --, or, with max_iterations > 0, until the lists have been given that many passes.  A pool that holds tapes runs
+// the tape build, whatever the form.  *all_done: every open list is done; h_rstates holds the lists' states either way.
+static int run_lists(mcrat_hip_ctx *c, const HydroDev &hy, RankLaunch rl, long long max_iterations, bool *all_done)
+{
+    const long long cap = rl.max_passes;
+    *all_done = false;
+    for (long long it = 0; !*all_done && (max_iterations <= 0 || it < max_iterations); it += rl.max_passes) {
+        rl.max_passes = (max_iterations > 0 && cap > max_iterations - it) ? max_iterations - it : cap;
+        int rc = profiled(c, 1, [&]() -> int {
+            if (c->d_pool_tapes)
+                HIPCHK(c, launch_rank_loop_tape(c->kc, c->ph, hy, c->d_rstates, c->key, c->n_ranks, c->rank_stride, c->d_desc, c->d_pool_tape, c->d_pool_tapes,
+                                                rl.max_passes, c->stream));
+            else
+                HIPCHK(c, launch_rank_loop(c->kc, c->ph, hy, c->d_rstates, c->key, rl, c->stream));
+            return MCRAT_HIP_OK;
+        }, [&]() -> int {
+            HIPCHK(c, hipMemcpyAsync(c->h_rstates, c->d_rstates, sizeof(LoopState) * (size_t)c->n_ranks, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            return MCRAT_HIP_OK;
+        });
+        if (rc) return rc;
+        *all_done = true;
+        for (int r = 0; r < c->n_ranks && *all_done; ++r) {
+            if (c->is_pool && c->h_desc[r].len <= 0) continue;     // a window without a list (or without a frame) has nothing to finish
+            *all_done = c->h_rstates[r].done != 0;
+        }
+    }
+    return MCRAT_HIP_OK;
+}
+
 static int run_ranks(mcrat_hip_ctx *c, long long max_iterations, mcrat_hip_frame_stats *stats)
 {
     if (c->is_pool) { int rc = pool_describe(c); if (rc) return rc; }
-    const int longest = longest_rank_list(c);
     if (!c->rank_block_fixed) { choose_rank_block(c); c->rank_block_fixed = true; }    // one choice per frame (begin_frame resets)
-    long long per_launch_cap = 32768;           // bounds one launch to a second or two even for the densest lists (4096: the first 60 frames of
-                                                // tools/lundman_run.py, 9.3e6 scatterings in the first one, 9.3 -> 8.9 s)
-    if (const char *e = getenv("MCRAT_HIP_RANK_LAUNCH_CAP")) per_launch_cap = atoll(e) > 0 ? atoll(e) : per_launch_cap;
-    long long it = 0;
-    while (max_iterations <= 0 || it < max_iterations) {
-        long long batch = per_launch_cap;
-        if (max_iterations > 0 && batch > max_iterations - it) batch = max_iterations - it;
-        if (c->cfg.profile) {
-            int rc = ensure_events(c, 2);
-            if (rc) return rc;
-            HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-        }
-        if (c->d_pool_tapes)                       // a pool that holds tapes: the tape build, whatever the choice above
-            HIPCHK(c, launch_rank_loop_tape(c->kc, c->ph, c->hy, c->d_rstates, c->key, c->n_ranks, c->rank_stride, c->d_desc, c->d_pool_tape, c->d_pool_tapes, batch,
-                                            c->stream));
-        else
-            HIPCHK(c, launch_rank_loop(c->kc, c->ph, c->hy, c->d_rstates, c->key, c->n_ranks, c->rank_stride, longest, c->is_pool ? c->d_desc : nullptr, nullptr, nullptr,
-                                       batch, c->rank_block + (c->rank_fuse ? 1000 : 0), c->stream, nullptr, 0, device_info(c)));
-        if (c->cfg.profile) {
-            HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-            HIPCHK(c, hipEventSynchronize(c->ev[1]));
-            float ms = 0;
-            HIPCHK(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-            c->prof_step_ms += ms;
-            c->prof_launches += 1;
-        }
-        it += batch;
-        HIPCHK(c, hipMemcpyAsync(c->h_rstates, c->d_rstates, sizeof(LoopState) * c->n_ranks, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        bool all_done = true;
-        for (int r = 0; r < c->n_ranks && all_done; ++r) {
-            if (c->is_pool && c->h_desc[r].len <= 0) continue;     // a window without a list (or without a frame) has nothing to finish
-            all_done = c->h_rstates[r].done != 0;
-        }
-        if (all_done) {
-            if (c->is_pool)
-                for (mcrat_hip_ctx *v : c->views)
-                    if (v && v->frame_open) v->rank_current = true;
-            break;
-        }
-    }
+    bool all_done = false;
+    int rc = run_lists(c, c->hy, rank_launch_of(c, c->is_pool ? c->d_desc : nullptr, rank_launch_cap()), max_iterations, &all_done);
+    if (rc) return rc;
+    if (all_done && c->is_pool)
+        for (mcrat_hip_ctx *v : c->views)
+            if (v && v->frame_open) v->rank_current = true;
     fill_rank_stats(c, stats);
     {   // what the next frame's choice of workgroup size looks at
         long long it_sum = 0;
@@ -2995,8 +3034,20 @@ static int run_ranks(mcrat_hip_ctx *c, long long max_iterations, mcrat_hip_frame
     return MCRAT_HIP_OK;
 }
 
-// The frame queue (launch.hpp, FrameQueueDev; kernels.hip, rank_loop_kernel): the pool's lists through several hydro frames in one launch.
-extern "C" int mcrat_hip_pool_run_frames(mcrat_hip_ctx *c, const mcrat_hip_frame_plan *p, mcrat_hip_frame_stats *stats)
+// ------------------------------------------------------------------ the frame queue's host side (mcrat_hip_pool_run_frames)
+// The call's scratch lives on the context (fq_*): no allocation per call once a plan of this size has been seen.
+
+// MCRAT_HIP_QUEUE_TIMING=1: where the call's host time goes, on stderr (development aid)
+struct QueueMarks {
+    double start, checked = 0, items = 0, chosen = 0, ordered = 0, launched = 0, synced = 0;      // us
+    size_t bytes_up = 0, bytes_down = 0;
+    static double now() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+    QueueMarks() : start(now()) {}
+};
+
+// The plan's arguments and the state it needs; the staged hydro frames of the plan into fq_hyv: index 0 the pool's own, then every other context named
+// in plan->hydro (it keeps its frame staged while the call runs; same switches as the pool -- its HydroDev is handed to the pool's kernels as it is)
+static int frames_check(mcrat_hip_ctx *c, const mcrat_hip_frame_plan *p, const mcrat_hip_frame_stats *stats)
 {
     if (!c || !p || !stats || p->n_frames <= 0 || !p->open || !p->seeds || !p->time_now || !p->remaining_time) return MCRAT_HIP_EINVAL;
     if (p->chain_clock && !p->frame_end) return MCRAT_HIP_EINVAL;
@@ -3008,15 +3059,11 @@ extern "C" int mcrat_hip_pool_run_frames(mcrat_hip_ctx *c, const mcrat_hip_frame
         c->last_error = "TAU_CALCULATION == TABLE needs mcrat_hip_set_hot_cross_section first";
         return MCRAT_HIP_ESTATE;
     }
-    // the staged hydro frames of the plan: index 0 the pool's own, then every other context named in plan->hydro (it keeps its frame staged while the
-    // call runs; same switches as the pool -- its HydroDev is handed to the pool's kernels as it is)
-    // (the call's scratch lives on the context: no allocation per call once a plan of this size has been seen)
     std::vector<HydroDev> &hyv = c->fq_hyv;
     std::vector<const mcrat_hip_ctx *> &hy_ctx = c->fq_hy_ctx;
-    std::vector<int> &hy_of_frame = c->fq_hy_of_frame;
     hyv.assign(1, c->hy);
     hy_ctx.assign(1, c);
-    hy_of_frame.assign((size_t)p->n_frames, 0);
+    c->fq_hy_of_frame.assign((size_t)p->n_frames, 0);
     if (p->hydro)
         for (int f = 0; f < p->n_frames; ++f) {
             const mcrat_hip_ctx *o = p->hydro[f];
@@ -3030,58 +3077,39 @@ extern "C" int mcrat_hip_pool_run_frames(mcrat_hip_ctx *c, const mcrat_hip_frame
             size_t k = 1;
             while (k < hy_ctx.size() && hy_ctx[k] != o) ++k;
             if (k == hy_ctx.size()) { hy_ctx.push_back(o); hyv.push_back(o->hy); }
-            hy_of_frame[(size_t)f] = (int)k;
+            c->fq_hy_of_frame[(size_t)f] = (int)k;
         }
+    if ((size_t)c->n_ranks * (size_t)p->n_frames > 0x7fffffffull) return MCRAT_HIP_EINVAL;
+    return MCRAT_HIP_OK;
+}
+
+static int frames_ensure_block(mcrat_hip_ctx *c, size_t bytes)
+{
+    if (c->fq_bytes >= bytes) return MCRAT_HIP_OK;
+    if (c->d_fq) { HIPCHK(c, hipFree(c->d_fq)); c->d_fq = nullptr; }
+    if (c->h_fq) { HIPCHK(c, hipHostFree(c->h_fq)); c->h_fq = nullptr; }
+    c->fq_bytes = 0;
+    HIPCHK(c, hipMalloc(&c->d_fq, bytes));
+    HIPCHK(c, hipHostMalloc(&c->h_fq, bytes, hipHostMallocDefault));
+    c->fq_bytes = bytes;
+    return MCRAT_HIP_OK;
+}
+
+// One pass over the plan into the pinned block: the items (every member written: nothing of the block is cleared but the ticket and frames_done words),
+// the lists that take part, each in one run of consecutive frames (fq_first, fq_last), their descriptions, and the hydro frames.
+static int frames_fill(mcrat_hip_ctx *c, const mcrat_hip_frame_plan *p, const FrameQueueLayout &lay)
+{
     const int R = c->n_ranks, F = p->n_frames;
-    const size_t N = (size_t)R * (size_t)F;
-    if (N > 0x7fffffffull) return MCRAT_HIP_EINVAL;
-    // MCRAT_HIP_QUEUE_TIMING=1: where the call's host time goes, on stderr (development aid)
-    static const bool timing = getenv("MCRAT_HIP_QUEUE_TIMING") && atoi(getenv("MCRAT_HIP_QUEUE_TIMING")) != 0;
-    // MCRAT_HIP_QUEUE_HOST_RECORDS=1 (A/B): the kernel stores the records straight into the pinned host block instead of device memory + one copy back
-    static const bool host_records = getenv("MCRAT_HIP_QUEUE_HOST_RECORDS") && atoi(getenv("MCRAT_HIP_QUEUE_HOST_RECORDS")) != 0;
-    auto clock_us = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double tq0 = clock_us();
-    double tq_filled = 0, tq_launched = 0, tq_synced = 0, tq_a = 0, tq_b = 0, tq_c = 0;
-    size_t bytes_up = 0, bytes_down = 0;
-    // The queue's block, device memory with a pinned mirror laid out alike: [order N | items N | hydro frames | list descriptions R] are only uploaded,
-    // [ticket | frames_done R] go both ways, [records N] only come back -- so one launch is ONE copy up ([0, off_rec)) and ONE copy down ([off_ticket, bytes)).
-    const size_t off_items = align_up(sizeof(int) * N, 64), off_hy = align_up(off_items + sizeof(FrameItem) * N, 256);
-    const size_t off_desc = align_up(off_hy + sizeof(HydroDev) * hyv.size(), 64), off_ticket = align_up(off_desc + sizeof(RankDesc) * (size_t)R, 256);
-    const size_t off_done = off_ticket + sizeof(unsigned) * FRAME_QUEUE_XCDS * FRAME_TICKET_STRIDE;
-    const size_t off_rec = align_up(off_done + sizeof(unsigned) * (size_t)R, 256), bytes = off_rec + sizeof(FrameRecord) * N;
-    if (c->fq_bytes < bytes) {
-        if (c->d_fq) { HIPCHK(c, hipFree(c->d_fq)); c->d_fq = nullptr; }
-        if (c->h_fq) { HIPCHK(c, hipHostFree(c->h_fq)); c->h_fq = nullptr; }
-        c->fq_bytes = 0;
-        HIPCHK(c, hipMalloc(&c->d_fq, bytes));
-        HIPCHK(c, hipHostMalloc(&c->h_fq, bytes, hipHostMallocDefault));
-        c->fq_bytes = bytes;
-    }
-    char *hb = static_cast<char *>(c->h_fq), *db = static_cast<char *>(c->d_fq);
-    unsigned *h_tickets = reinterpret_cast<unsigned *>(hb + off_ticket), *h_done = reinterpret_cast<unsigned *>(hb + off_done);
-    int *h_order = reinterpret_cast<int *>(hb);
-    FrameItem *h_items = reinterpret_cast<FrameItem *>(hb + off_items);
-    RankDesc *h_qdesc = reinterpret_cast<RankDesc *>(hb + off_desc);
-    FrameRecord *h_rec = reinterpret_cast<FrameRecord *>(hb + off_rec);
-    tq_a = clock_us();
-    // One pass over the plan: the lists that take part, each in one run of consecutive frames; the items (every member written: nothing of the staging
-    // block is cleared but the ticket and frames_done words); the open items per XCD.
-    // Which XCD a list belongs to: list r to XCD r % 8, where one launch per frame puts it too.  (Measured against contiguous eighths of the lists --
-    // neighbouring lists hold photons of neighbouring cells, so an XCD's L2 would have an eighth of the cells to hold: 0.567 against 0.52 ms per frame
-    // on the benchmark frame, the eighths differ in optical depth and the launch ends with the slowest XCD.)
-    auto list_class = [&](int r) { return r % FRAME_QUEUE_XCDS; };
-    int xcd_of_class[FRAME_QUEUE_XCDS];                      // which XCD's queue the lists of class k are in (identity unless an XCD turned out to start no workgroups)
-    for (int x = 0; x < FRAME_QUEUE_XCDS; ++x) xcd_of_class[x] = x;
-    int count[FRAME_QUEUE_XCDS] = {0};
+    FrameItem *items = lay.items(c->h_fq);
     std::vector<int> &first = c->fq_first, &last = c->fq_last;
     first.assign((size_t)R, -1);
     last.assign((size_t)R, -1);
     for (int f = 0; f < F; ++f) {
         const size_t t0 = (size_t)f * R;
-        const int hydro_f = hy_of_frame[(size_t)f];
+        const int hydro_f = c->fq_hy_of_frame[(size_t)f];
         for (int r = 0; r < R; ++r) {
             const size_t t = t0 + r;
-            FrameItem &it = h_items[t];
+            FrameItem &it = items[t];
             it.seed = p->seeds[t]; it.time_now = p->time_now[t]; it.remaining_time = p->remaining_time[t];
             it.frame_end = p->frame_end ? p->frame_end[t] : 0.0;
             it.open = p->open[t] ? 1 : 0;
@@ -3090,7 +3118,6 @@ extern "C" int mcrat_hip_pool_run_frames(mcrat_hip_ctx *c, const mcrat_hip_frame
             if (first[r] < 0) first[r] = f;
             else if (last[r] != f - 1) { c->last_error = "pool_run_frames: a list's open frames must be consecutive"; return MCRAT_HIP_EINVAL; }
             last[r] = f;
-            count[list_class(r)] += 1;
         }
     }
     for (int r = 0; r < R; ++r) {
@@ -3105,231 +3132,177 @@ extern "C" int mcrat_hip_pool_run_frames(mcrat_hip_ctx *c, const mcrat_hip_frame
                 return MCRAT_HIP_ESTATE;
             }
     }
+    RankDesc *qdesc = lay.desc(c->h_fq);
     for (int r = 0; r < R; ++r) {                            // (the queue's kernel reads the block's copy; the context's host copy is what the launch form is chosen from)
         const mcrat_hip_ctx *v = c->views[(size_t)r];
         RankDesc d{};
         if (first[r] >= 0) { d.len = v->ph.n; d.stream = v->key.stream; d.seed = p->seeds[(size_t)first[r] * R + r]; }
         c->h_desc[r] = d;
-        h_qdesc[r] = d;
+        qdesc[r] = d;
     }
-    memcpy(hb + off_hy, hyv.data(), sizeof(HydroDev) * hyv.size());
-    memset(hb + off_ticket, 0, off_rec - off_ticket);        // ticket, frames_done
-    tq_b = clock_us();
-    // TAU_CALCULATION == TABLE: a frame's off-table look-ups count on the context its hydro frame is staged on (HydroDev::table_fallbacks); every
-    // such counter starts the call from zero and the call reports their sum (DIRECT: no kernel touches the counters and nobody reads them)
-    if (c->kc.table) {
-        HIPCHK(c, hipMemsetAsync(c->d_table_fallbacks, 0, sizeof(int), c->stream));
-        for (const HydroDev &h : hyv)
-            if (h.table_fallbacks) HIPCHK(c, hipMemsetAsync(h.table_fallbacks, 0, sizeof(int), c->stream));
-    }
-    if (!c->rank_block_fixed) { choose_rank_block(c); c->rank_block_fixed = true; }
-    tq_c = clock_us();
-    FrameQueueDev fq{};
-    fq.n_frames = F; fq.restore = p->restore_each_frame ? 1 : 0; fq.chain_clock = p->chain_clock ? 1 : 0;
-    fq.ticket = reinterpret_cast<unsigned *>(db + off_ticket); fq.frames_done = reinterpret_cast<unsigned *>(db + off_done);
-    fq.order = reinterpret_cast<const int *>(db); fq.items = reinterpret_cast<const FrameItem *>(db + off_items);
-    fq.records = reinterpret_cast<FrameRecord *>(db + off_rec);
+    memcpy(lay.hydro(c->h_fq), c->fq_hyv.data(), sizeof(HydroDev) * c->fq_hyv.size());
+    memset(static_cast<char *>(c->h_fq) + lay.words.off, 0, lay.words.bytes);
+    return MCRAT_HIP_OK;
+}
+
+// The queue as the kernel gets it (all but the order's offsets), and the captures' buffer: with plan->capture_frames, the lists as every frame but the
+// last leaves them (the frame's outputs: mcrat.c:881-915)
+static int frames_queue_dev(mcrat_hip_ctx *c, const mcrat_hip_frame_plan *p, const FrameQueueLayout &lay, bool host_records, FrameQueueDev *fq)
+{
+    const int F = p->n_frames;
+    *fq = FrameQueueDev{};
+    fq->n_frames = F; fq->restore = p->restore_each_frame ? 1 : 0; fq->chain_clock = p->chain_clock ? 1 : 0;
+    fq->ticket = lay.ticket(c->d_fq); fq->frames_done = lay.frames_done(c->d_fq);
+    fq->order = lay.order(c->d_fq); fq->items = lay.items(c->d_fq); fq->hydro = lay.hydro(c->d_fq);
+    fq->records = lay.records(c->d_fq);
     if (host_records) {                                      // (the pinned block as the device sees it)
         void *mapped = nullptr;
         HIPCHK(c, hipHostGetDevicePointer(&mapped, c->h_fq, 0));
-        fq.records = reinterpret_cast<FrameRecord *>(static_cast<char *>(mapped) + off_rec);
+        fq->records = lay.records(mapped);
     }
-    fq.hydro = reinterpret_cast<const HydroDev *>(db + off_hy);
-    fq.snap_delta = p->restore_each_frame ? (long long)(static_cast<char *>(c->ph_snap) - static_cast<char *>(c->ph_buf)) : 0;
+    fq->snap_delta = p->restore_each_frame ? (long long)(static_cast<char *>(c->ph_snap) - static_cast<char *>(c->ph_buf)) : 0;
     c->cap_frames = 0;
-    if (p->capture_frames && F > 1) {                        // the lists as every frame but the last leaves them (the frame's outputs: mcrat.c:881-915)
+    if (p->capture_frames && F > 1) {
         const size_t need = c->ph_bytes * (size_t)(F - 1);
         if (c->ph_cap_bytes < need) {
             if (c->ph_cap) { HIPCHK(c, hipFree(c->ph_cap)); c->ph_cap = nullptr; c->ph_cap_bytes = 0; }
             HIPCHK(c, hipMalloc(&c->ph_cap, need));
             c->ph_cap_bytes = need;
         }
-        fq.capture_delta = (long long)(static_cast<char *>(c->ph_cap) - static_cast<char *>(c->ph_buf));
-        fq.capture_stride = (long long)c->ph_bytes;
+        fq->capture_delta = (long long)(static_cast<char *>(c->ph_cap) - static_cast<char *>(c->ph_buf));
+        fq->capture_stride = (long long)c->ph_bytes;
         c->cap_frames = F - 1;
         // a capture holds the slots [0, list_capacity) of the lists that were open in its frame; every other slot must read as the empty slot it is in
         // the live lists (printPhotons' compaction keeps weight != 0 over the whole pool): the weight column starts from zero
         for (int f = 0; f < F - 1; ++f)
-            HIPCHK(c, hipMemsetAsync(reinterpret_cast<char *>(c->ph.weight) + fq.capture_delta + (long long)f * fq.capture_stride, 0,
+            HIPCHK(c, hipMemsetAsync(reinterpret_cast<char *>(c->ph.weight) + fq->capture_delta + (long long)f * fq->capture_stride, 0,
                                      sizeof(double) * (size_t)c->ph.n, c->stream));
     }
-    long long per_frame_cap = 32768;             // passes one list may take per frame and launch (run_ranks' bound on a launch's duration)
-    if (const char *e = getenv("MCRAT_HIP_RANK_LAUNCH_CAP")) per_frame_cap = atoll(e) > 0 ? atoll(e) : per_frame_cap;
-    const int longest = longest_rank_list(c);
-    c->prof_step_ms = 0; c->prof_launches = 0;
-    bool one_by_one = getenv("MCRAT_HIP_NO_FRAME_QUEUE") && atoi(getenv("MCRAT_HIP_NO_FRAME_QUEUE")) != 0;      // (A/B: the plan frame by frame)
-    one_by_one = one_by_one || c->d_pool_tapes != nullptr;              // (a pool that holds tapes: the tape build has no queue form)
-    // the frame of each list that a launch of this call left at its pass limit (-1: none): the one frame in progress whose record may be read
-    // (FrameRecord's validity rule); it stays that until frames_done has moved past it
-    std::vector<int> &stalled = c->fq_stalled;
-    stalled.assign((size_t)R, -1);
-    for (int attempt = 0; !one_by_one; ++attempt) {
-        // the open items in the order they are taken: per XCD (list r belongs to XCD r % 8: a list never changes L2) frame-major; one workgroup per item,
-        // and as the hardware deals workgroups round-robin over the XCDs, eight times the longest XCD's list of them
-        int n_open = 0, longest_xcd = 0;
-        {
-            int fill[FRAME_QUEUE_XCDS];
-            if (attempt > 0) {                               // (a relaunch: what is still open, in the queues the XCDs that exist draw from)
-                for (int x = 0; x < FRAME_QUEUE_XCDS; ++x) count[x] = 0;
-                for (int f = 0; f < F; ++f)
-                    for (int r = 0; r < R; ++r)
-                        if (h_items[(size_t)f * R + r].open) count[xcd_of_class[list_class(r)]] += 1;
-            }
-            for (int x = 0; x < FRAME_QUEUE_XCDS; ++x) {
-                fq.order_off[x] = fill[x] = n_open;
-                n_open += count[x];
-                longest_xcd = std::max(longest_xcd, count[x]);
-            }
-            for (int f = 0; f < F; ++f)                      // frame-major within an XCD's queue
-                for (int r = 0; r < R; ++r)
-                    if (h_items[(size_t)f * R + r].open) h_order[fill[xcd_of_class[list_class(r)]]++] = f * R + r;
-        }
-        fq.order_off[FRAME_QUEUE_XCDS] = n_open;
-        const int n_groups = FRAME_QUEUE_XCDS * longest_xcd;
-        if (n_groups == 0) break;                            // (no list opens a frame: the call has only sized the queue's buffers)
-        tq_filled = clock_us();
-        HIPCHK(c, hipMemcpyAsync(db, hb, off_rec, hipMemcpyHostToDevice, c->stream));
-        bytes_up += off_rec;
-        if (c->cfg.profile) {
-            int rc = ensure_events(c, 2);
-            if (rc) return rc;
-            HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-        }
-        {
-            const hipError_t le = launch_rank_loop(c->kc, c->ph, c->hy, c->d_rstates, c->key, R, c->rank_stride, longest, reinterpret_cast<const RankDesc *>(db + off_desc),
-                                                   nullptr, nullptr, per_frame_cap, c->rank_block + (c->rank_fuse ? 1000 : 0), c->stream, &fq, n_groups, device_info(c));
-            if (le == hipErrorNotSupported && attempt == 0) { one_by_one = true; break; }      // no queue build of this launch form (kernels.hip)
+    return MCRAT_HIP_OK;
+}
+
+// Queue launches until every list is through its last frame: order the open items, one copy up, the launch, one copy down, and what the launch left
+// (frame_queue.hpp).  *unsupported: the launch form has no queue build (kernels.hip) and nothing has run.
+static int frames_run_queue(mcrat_hip_ctx *c, const FrameQueueLayout &lay, FrameQueueDev &fq, RankLaunch rl, bool host_records, QueueMarks &tm, bool *unsupported)
+{
+    const int R = c->n_ranks, F = fq.n_frames;
+    char *hb = static_cast<char *>(c->h_fq), *db = static_cast<char *>(c->d_fq);
+    int xcd_of_class[FRAME_QUEUE_XCDS];
+    for (int x = 0; x < FRAME_QUEUE_XCDS; ++x) xcd_of_class[x] = x;
+    c->fq_stalled.assign((size_t)R, -1);
+    rl.desc = lay.desc(c->d_fq);
+    rl.fq = &fq;
+    // (the records the kernel stored into the pinned block itself: tickets and frames_done alone come back)
+    const FrameQueueLayout::Range down = host_records ? lay.words : lay.down;
+    *unsupported = false;
+    constexpr int NO_QUEUE_BUILD = 1;                        // (beside the MCRAT_HIP_ codes, which are <= 0: nothing was launched)
+    for (int attempt = 0;; ++attempt) {
+        rl.n_open = frame_queue_groups(frame_queue_order(lay.items(hb), R, F, xcd_of_class, lay.order(hb), fq.order_off));
+        if (rl.n_open == 0) break;                           // (no list opens a frame: the call has only sized the queue's buffers)
+        tm.ordered = QueueMarks::now();
+        HIPCHK(c, hipMemcpyAsync(db + lay.up.off, hb + lay.up.off, lay.up.bytes, hipMemcpyHostToDevice, c->stream));
+        tm.bytes_up += lay.up.bytes;
+        int rc = profiled(c, 1, [&]() -> int {
+            const hipError_t le = launch_rank_loop(c->kc, c->ph, c->hy, c->d_rstates, c->key, rl, c->stream);
+            if (le == hipErrorNotSupported && attempt == 0) return NO_QUEUE_BUILD;
             HIPCHK(c, le);
-        }
-        if (c->cfg.profile) HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-        {   // tickets, frames_done and the records in one copy (records the kernel stored into the pinned block itself: the first two alone)
-            const size_t down = (host_records ? off_rec : bytes) - off_ticket;
-            HIPCHK(c, hipMemcpyAsync(hb + off_ticket, db + off_ticket, down, hipMemcpyDeviceToHost, c->stream));
-            bytes_down += down;
-        }
-        tq_launched = clock_us();
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        tq_synced = clock_us();
-        if (c->cfg.profile) {
-            float ms = 0;
-            HIPCHK(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-            c->prof_step_ms += ms;
-            c->prof_launches += 1;
-        }
-        bool all = true;
-        for (int r = 0; r < R; ++r) {
-            // (the frame that ran into the pass limit = the frames before it are through)
-            if (h_done[r] & FRAME_STALLED) { h_done[r] &= ~FRAME_STALLED; stalled[(size_t)r] = (int)h_done[r]; }
-            all = all && (first[r] < 0 || (int)h_done[r] == last[r] + 1);
-        }
-        if (all) break;
-        {   // a device whose workgroups report fewer XCDs than eight (another partition mode): the queues nobody drew from move to XCDs that exist
-            int alive[FRAME_QUEUE_XCDS], n_alive = 0;
-            for (int x = 0; x < FRAME_QUEUE_XCDS; ++x)
-                if (h_tickets[(size_t)x * FRAME_TICKET_STRIDE] > 0) alive[n_alive++] = x;
-            if (n_alive == 0) { c->last_error = "pool_run_frames: no workgroup drew an item"; return MCRAT_HIP_EHIP; }
-            for (int k = 0; k < FRAME_QUEUE_XCDS; ++k)
-                if (h_tickets[(size_t)xcd_of_class[k] * FRAME_TICKET_STRIDE] == 0) xcd_of_class[k] = alive[k % n_alive];
-        }
-        if (attempt >= 1 << 16) { c->last_error = "pool_run_frames: lists that make no progress"; return MCRAT_HIP_EHIP; }
-        // Lists whose frame ran into the launch's pass limit (and their later frames, whose workgroups gave up): their finished frames leave the queue, the
-        // frame in progress goes on from its LoopState (open = 2), the rest as planned -- with the clock the host now knows.
-        // Only records this call is known to have written are read (FrameRecord): the stalled frame's, and those of frames that are through.
-        memset(h_tickets, 0, sizeof(unsigned) * FRAME_QUEUE_XCDS * FRAME_TICKET_STRIDE);
-        for (int r = 0; r < R; ++r) {
-            if (first[r] < 0) continue;
-            const int nf = std::max((int)h_done[r], first[r]);                     // the first frame that is not complete
-            for (int f = first[r]; f <= last[r]; ++f) {
-                FrameItem &it = h_items[(size_t)f * R + r];
-                if (f < nf) { it.open = 0; continue; }
-                if (f > nf) continue;
-                const FrameRecord &rec = h_rec[(size_t)f * R + r];
-                if (stalled[(size_t)r] == nf && rec.iterations > 0 && !rec.done) it.open = 2;
-                else if (p->chain_clock && f > first[r]) {                         // (its previous frame has left the queue: the clock it would have read there)
-                    it.time_now = h_rec[(size_t)(f - 1) * R + r].time_now;
-                    it.remaining_time = it.frame_end - it.time_now;
-                }
-            }
-        }
-    }
-    if (one_by_one) {
-        // The plan one launch per frame: launch forms without a queue build (128- and 512-thread lists, lists whose columns stay in HBM/L2) -- the same
-        // frames, seeds and clocks, so the same photons; what is lost is only that a list need not wait for the others at a frame's end.
-        std::vector<double> t_now((size_t)R, 0.0), t_rem((size_t)R, 0.0);
-        std::vector<int> op((size_t)R, 0);
-        const size_t sb = (sizeof(int) + 2 * sizeof(double)) * (size_t)R;
-        int rc = ensure_aos(c, sb + 64);
+            return MCRAT_HIP_OK;
+        }, [&]() -> int {
+            HIPCHK(c, hipMemcpyAsync(hb + down.off, db + down.off, down.bytes, hipMemcpyDeviceToHost, c->stream));
+            tm.bytes_down += down.bytes;
+            tm.launched = QueueMarks::now();
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            tm.synced = QueueMarks::now();
+            return MCRAT_HIP_OK;
+        });
+        if (rc == NO_QUEUE_BUILD) { *unsupported = true; return MCRAT_HIP_OK; }
         if (rc) return rc;
-        double *d_t = static_cast<double *>(c->aos_buf), *d_rem = d_t + R;
-        int *d_open = reinterpret_cast<int *>(d_rem + R);
-        const long long snap = p->restore_each_frame ? (long long)(static_cast<char *>(c->ph_snap) - static_cast<char *>(c->ph_buf)) : 0;
-        for (int f = 0; f < F; ++f) {
-            bool any = false, all_lists = true;                               // (every list that exists takes part: the whole pool is restored in one copy)
-            for (int r = 0; r < R; ++r)
-                if (c->views[(size_t)r] && c->views[(size_t)r]->have_photons && !h_items[(size_t)f * R + r].open) all_lists = false;
-            if (p->restore_each_frame && all_lists) HIPCHK(c, hipMemcpyAsync(c->ph_buf, c->ph_snap, c->ph_bytes, hipMemcpyDeviceToDevice, c->stream));
-            for (int r = 0; r < R; ++r) {
-                const size_t t = (size_t)f * R + r;
-                op[(size_t)r] = h_items[t].open ? 1 : 0;
-                if (!op[(size_t)r]) { c->h_desc[r].len = 0; continue; }
-                any = true;
-                const mcrat_hip_ctx *v = c->views[(size_t)r];
-                c->h_desc[r].len = v->ph.n; c->h_desc[r].stream = v->key.stream; c->h_desc[r].seed = h_items[t].seed;
-                t_now[(size_t)r] = h_items[t].time_now; t_rem[(size_t)r] = h_items[t].remaining_time;
-                if (p->chain_clock && f > first[r]) { t_now[(size_t)r] = h_rec[t - R].time_now; t_rem[(size_t)r] = h_items[t].frame_end - t_now[(size_t)r]; }
-                if (p->restore_each_frame && !all_lists) {                    // the list's window of every column back from the snapshot
-                    const size_t b0 = (size_t)r * (size_t)c->rank_stride, len = (size_t)v->ph.n;
-                    char *col0 = reinterpret_cast<char *>(c->ph.r0 + b0);
-                    HIPCHK(c, hipMemcpy2DAsync(col0, sizeof(double) * c->ph.col_stride, col0 + snap, sizeof(double) * c->ph.col_stride, sizeof(double) * len,
-                                               24, hipMemcpyDeviceToDevice, c->stream));
-                    HIPCHK(c, hipMemcpyAsync(c->ph.idx + b0, reinterpret_cast<char *>(c->ph.idx + b0) + snap, sizeof(int) * len, hipMemcpyDeviceToDevice, c->stream));
-                    HIPCHK(c, hipMemcpyAsync(c->ph.flags + b0, reinterpret_cast<char *>(c->ph.flags + b0) + snap, len, hipMemcpyDeviceToDevice, c->stream));
-                    HIPCHK(c, hipMemcpyAsync(c->ph.type + b0, reinterpret_cast<char *>(c->ph.type + b0) + snap, len, hipMemcpyDeviceToDevice, c->stream));
-                }
-            }
-            if (!any) continue;
-            HIPCHK(c, hipMemcpyAsync(d_t, t_now.data(), sizeof(double) * (size_t)R, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(d_rem, t_rem.data(), sizeof(double) * (size_t)R, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(d_open, op.data(), sizeof(int) * (size_t)R, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(c->d_desc, c->h_desc, sizeof(RankDesc) * (size_t)R, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, launch_init_states_multi(c->d_rstates, R, d_open, d_t, d_rem, c->stream));
-            for (;;) {
-                if (c->cfg.profile) { rc = ensure_events(c, 2); if (rc) return rc; HIPCHK(c, hipEventRecord(c->ev[0], c->stream)); }
-                if (c->d_pool_tapes)                  // (each frame reads on from each list's position)
-                    HIPCHK(c, launch_rank_loop_tape(c->kc, c->ph, hyv[(size_t)hy_of_frame[(size_t)f]], c->d_rstates, c->key, R, c->rank_stride, c->d_desc, c->d_pool_tape,
-                                                    c->d_pool_tapes, per_frame_cap, c->stream));
-                else
-                    HIPCHK(c, launch_rank_loop(c->kc, c->ph, hyv[(size_t)hy_of_frame[(size_t)f]], c->d_rstates, c->key, R, c->rank_stride, longest, c->d_desc, nullptr,
-                                               nullptr, per_frame_cap, c->rank_block + (c->rank_fuse ? 1000 : 0), c->stream, nullptr, 0, device_info(c)));
-                if (c->cfg.profile) HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-                HIPCHK(c, hipMemcpyAsync(c->h_rstates, c->d_rstates, sizeof(LoopState) * (size_t)R, hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                if (c->cfg.profile) { float ms = 0; HIPCHK(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1])); c->prof_step_ms += ms; c->prof_launches += 1; }
-                bool done = true;
-                for (int r = 0; r < R && done; ++r) done = !op[(size_t)r] || c->h_rstates[r].done != 0;
-                if (done) break;
-            }
-            for (int r = 0; r < R; ++r)
-                if (op[(size_t)r]) h_rec[(size_t)f * R + r].from_state(c->h_rstates[r]);
-            if (c->cap_frames > 0 && f < F - 1)               // the pool as frame f leaves it
-                HIPCHK(c, hipMemcpyAsync(static_cast<char *>(c->ph_cap) + (size_t)f * c->ph_bytes, c->ph_buf, c->ph_bytes, hipMemcpyDeviceToDevice, c->stream));
-        }
-        // the lists' descriptions as a queue launch leaves them: every list of the plan with its length, also one that sat the last frame out
-        // (mcrat_hip_rank_stats prices a list's passes with it)
-        for (int r = 0; r < R; ++r) c->h_desc[r] = h_qdesc[r];
+        const FrameQueueNext next = frame_queue_after_launch(lay.frames_done(hb), lay.ticket(hb), lay.records(hb), lay.items(hb), R, c->fq_first.data(),
+                                                             c->fq_last.data(), fq.chain_clock != 0, c->fq_stalled.data(), xcd_of_class);
+        if (next == FRAME_QUEUE_DONE) break;
+        if (next == FRAME_QUEUE_NO_DRAW) { c->last_error = "pool_run_frames: no workgroup drew an item"; return MCRAT_HIP_EHIP; }
+        if (attempt >= 1 << 16) { c->last_error = "pool_run_frames: lists that make no progress"; return MCRAT_HIP_EHIP; }
     }
+    return MCRAT_HIP_OK;
+}
+
+// The plan one launch per frame: launch forms without a queue build (128- and 512-thread lists, lists whose columns stay in HBM/L2, the tape build) --
+// the same frames, seeds and clocks, so the same photons; what is lost is only that a list need not wait for the others at a frame's end.
+static int frames_run_one_by_one(mcrat_hip_ctx *c, const mcrat_hip_frame_plan *p, const FrameQueueLayout &lay, RankLaunch rl)
+{
+    const int R = c->n_ranks, F = p->n_frames;
+    const FrameItem *items = lay.items(c->h_fq);
+    FrameRecord *rec = lay.records(c->h_fq);
+    const std::vector<int> &first = c->fq_first;
+    std::vector<double> t_now((size_t)R, 0.0), t_rem((size_t)R, 0.0);
+    std::vector<int> op((size_t)R, 0);
+    const size_t sb = (sizeof(int) + 2 * sizeof(double)) * (size_t)R;
+    int rc = ensure_aos(c, sb + 64);
+    if (rc) return rc;
+    double *d_t = static_cast<double *>(c->aos_buf), *d_rem = d_t + R;
+    int *d_open = reinterpret_cast<int *>(d_rem + R);
+    const long long snap = p->restore_each_frame ? (long long)(static_cast<char *>(c->ph_snap) - static_cast<char *>(c->ph_buf)) : 0;
+    rl.desc = c->d_desc;
+    for (int f = 0; f < F; ++f) {
+        bool any = false, all_lists = true;                               // (every list that exists takes part: the whole pool is restored in one copy)
+        for (int r = 0; r < R; ++r)
+            if (c->views[(size_t)r] && c->views[(size_t)r]->have_photons && !items[(size_t)f * R + r].open) all_lists = false;
+        if (p->restore_each_frame && all_lists) HIPCHK(c, hipMemcpyAsync(c->ph_buf, c->ph_snap, c->ph_bytes, hipMemcpyDeviceToDevice, c->stream));
+        for (int r = 0; r < R; ++r) {
+            const size_t t = (size_t)f * R + r;
+            op[(size_t)r] = items[t].open ? 1 : 0;
+            if (!op[(size_t)r]) { c->h_desc[r].len = 0; continue; }
+            any = true;
+            const mcrat_hip_ctx *v = c->views[(size_t)r];
+            c->h_desc[r].len = v->ph.n; c->h_desc[r].stream = v->key.stream; c->h_desc[r].seed = items[t].seed;
+            t_now[(size_t)r] = items[t].time_now; t_rem[(size_t)r] = items[t].remaining_time;
+            if (p->chain_clock && f > first[r]) { t_now[(size_t)r] = rec[t - R].time_now; t_rem[(size_t)r] = items[t].frame_end - t_now[(size_t)r]; }
+            if (p->restore_each_frame && !all_lists) {                    // the list's window of every column back from the snapshot
+                const size_t b0 = (size_t)r * (size_t)c->rank_stride, len = (size_t)v->ph.n;
+                char *col0 = reinterpret_cast<char *>(c->ph.r0 + b0);
+                HIPCHK(c, hipMemcpy2DAsync(col0, sizeof(double) * c->ph.col_stride, col0 + snap, sizeof(double) * c->ph.col_stride, sizeof(double) * len,
+                                           24, hipMemcpyDeviceToDevice, c->stream));
+                HIPCHK(c, hipMemcpyAsync(c->ph.idx + b0, reinterpret_cast<char *>(c->ph.idx + b0) + snap, sizeof(int) * len, hipMemcpyDeviceToDevice, c->stream));
+                HIPCHK(c, hipMemcpyAsync(c->ph.flags + b0, reinterpret_cast<char *>(c->ph.flags + b0) + snap, len, hipMemcpyDeviceToDevice, c->stream));
+                HIPCHK(c, hipMemcpyAsync(c->ph.type + b0, reinterpret_cast<char *>(c->ph.type + b0) + snap, len, hipMemcpyDeviceToDevice, c->stream));
+            }
+        }
+        if (!any) continue;
+        HIPCHK(c, hipMemcpyAsync(d_t, t_now.data(), sizeof(double) * (size_t)R, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_rem, t_rem.data(), sizeof(double) * (size_t)R, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_open, op.data(), sizeof(int) * (size_t)R, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->d_desc, c->h_desc, sizeof(RankDesc) * (size_t)R, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, launch_init_states_multi(c->d_rstates, R, d_open, d_t, d_rem, c->stream));
+        bool all_done = false;                                            // (a pool that holds tapes: each frame reads on from each list's position)
+        if ((rc = run_lists(c, c->fq_hyv[(size_t)c->fq_hy_of_frame[(size_t)f]], rl, 0, &all_done))) return rc;
+        for (int r = 0; r < R; ++r)
+            if (op[(size_t)r]) rec[(size_t)f * R + r].from_state(c->h_rstates[r]);
+        if (c->cap_frames > 0 && f < F - 1)               // the pool as frame f leaves it
+            HIPCHK(c, hipMemcpyAsync(static_cast<char *>(c->ph_cap) + (size_t)f * c->ph_bytes, c->ph_buf, c->ph_bytes, hipMemcpyDeviceToDevice, c->stream));
+    }
+    // the lists' descriptions as a queue launch leaves them: every list of the plan with its length, also one that sat the last frame out
+    // (mcrat_hip_rank_stats prices a list's passes with it)
+    const RankDesc *qdesc = lay.desc(c->h_fq);
+    for (int r = 0; r < R; ++r) c->h_desc[r] = qdesc[r];
+    return MCRAT_HIP_OK;
+}
+
+// The records as the call's statistics, and the pool as after the last frame's mcrat_hip_run
+static void frames_publish(mcrat_hip_ctx *c, const mcrat_hip_frame_plan *p, const FrameRecord *rec, mcrat_hip_frame_stats *stats)
+{
+    const int R = c->n_ranks;
+    const size_t N = (size_t)R * (size_t)p->n_frames;
     for (size_t t = 0; t < N; ++t) {
         const int r = (int)(t % (size_t)R);
-        if (p->open[t]) record_to_stats(h_rec[t], c->views[(size_t)r]->ph.n, &stats[t]);
+        if (p->open[t]) record_to_stats(rec[t], c->views[(size_t)r]->ph.n, &stats[t]);
         else memset(&stats[t], 0, sizeof stats[t]);
     }
-    // the pool as after the last frame's mcrat_hip_run
     long long it_sum = 0;
     int lists = 0;
     for (int r = 0; r < R; ++r) {
-        if (first[r] < 0) continue;
+        if (c->fq_first[(size_t)r] < 0) continue;
         mcrat_hip_ctx *v = c->views[(size_t)r];
-        const size_t t = (size_t)last[r] * R + r;
+        const size_t t = (size_t)c->fq_last[(size_t)r] * R + r;
         if (v->graph_exec && v->key.seed != p->seeds[t]) drop_graph(v);
         v->key.seed = p->seeds[t];
         v->find_switch = 1;
@@ -3338,8 +3311,8 @@ extern "C" int mcrat_hip_pool_run_frames(mcrat_hip_ctx *c, const mcrat_hip_frame
         v->frame_open = true;
         v->prof_step_ms = v->prof_event_ms = 0;
         v->prof_launches = 0;
-        record_to_state(h_rec[t], &c->h_rstates[r]);          // (the host's copy of the list's state: what the statistics and `done` are read from)
-        it_sum += h_rec[t].iterations;
+        record_to_state(rec[t], &c->h_rstates[r]);            // (the host's copy of the list's state: what the statistics and `done` are read from)
+        it_sum += rec[t].iterations;
         lists += 1;
     }
     if (lists > 0) { c->rank_passes_per_list = (double)it_sum / lists; c->frame_open = true; }
@@ -3347,6 +3320,7 @@ extern "C" int mcrat_hip_pool_run_frames(mcrat_hip_ctx *c, const mcrat_hip_frame
     stats[0].step_kernel_ms = c->prof_step_ms;               // (profile = 1: the launch's duration, on the first item)
     stats[0].step_kernel_launches = c->prof_launches;
     if (c->kc.table) {                                       // (the call's off-table look-ups, over every staged frame's counter)
+        const std::vector<HydroDev> &hyv = c->fq_hyv;
         long long fallbacks = 0;
         for (size_t k = 0; k < hyv.size(); ++k) {
             const HydroDev &h = hyv[k];
@@ -3359,10 +3333,47 @@ extern "C" int mcrat_hip_pool_run_frames(mcrat_hip_ctx *c, const mcrat_hip_frame
         }
         stats[0].table_fallbacks = fallbacks;
     }
+}
+
+// The frame queue (frame_queue.hpp; kernels.hip, rank_loop_kernel): the pool's lists through several hydro frames in one launch.
+extern "C" int mcrat_hip_pool_run_frames(mcrat_hip_ctx *c, const mcrat_hip_frame_plan *p, mcrat_hip_frame_stats *stats)
+{
+    static const bool timing = env_flag("MCRAT_HIP_QUEUE_TIMING");
+    // MCRAT_HIP_QUEUE_HOST_RECORDS=1 (A/B): the kernel stores the records straight into the pinned host block instead of device memory + one copy back
+    static const bool host_records = env_flag("MCRAT_HIP_QUEUE_HOST_RECORDS");
+    QueueMarks tm;
+    int rc = frames_check(c, p, stats);
+    if (rc) return rc;
+    const int R = c->n_ranks, F = p->n_frames;
+    const FrameQueueLayout lay(R, F, c->fq_hyv.size());
+    if ((rc = frames_ensure_block(c, lay.bytes))) return rc;
+    tm.checked = QueueMarks::now();
+    if ((rc = frames_fill(c, p, lay))) return rc;
+    tm.items = QueueMarks::now();
+    // TAU_CALCULATION == TABLE: a frame's off-table look-ups count on the context its hydro frame is staged on (HydroDev::table_fallbacks); every
+    // such counter starts the call from zero and the call reports their sum (DIRECT: no kernel touches the counters and nobody reads them)
+    if (c->kc.table) {
+        HIPCHK(c, hipMemsetAsync(c->d_table_fallbacks, 0, sizeof(int), c->stream));
+        for (const HydroDev &h : c->fq_hyv)
+            if (h.table_fallbacks) HIPCHK(c, hipMemsetAsync(h.table_fallbacks, 0, sizeof(int), c->stream));
+    }
+    if (!c->rank_block_fixed) { choose_rank_block(c); c->rank_block_fixed = true; }
+    tm.chosen = QueueMarks::now();
+    FrameQueueDev fq;
+    if ((rc = frames_queue_dev(c, p, lay, host_records, &fq))) return rc;
+    // passes one list may take per frame and launch (run_ranks' bound on a launch's duration)
+    const RankLaunch rl = rank_launch_of(c, nullptr, rank_launch_cap());
+    c->prof_step_ms = 0; c->prof_launches = 0;
+    // (MCRAT_HIP_NO_FRAME_QUEUE=1, A/B: the plan frame by frame; a pool that holds tapes: the tape build has no queue form)
+    bool one_by_one = env_flag("MCRAT_HIP_NO_FRAME_QUEUE") || c->d_pool_tapes != nullptr;
+    if (!one_by_one && (rc = frames_run_queue(c, lay, fq, rl, host_records, tm, &one_by_one))) return rc;
+    if (one_by_one && (rc = frames_run_one_by_one(c, p, lay, rl))) return rc;
+    frames_publish(c, p, lay.records(c->h_fq), stats);
     if (timing)
         fprintf(stderr, "pool_run_frames: %d frames x %d lists: plan -> queue %.0f us (checks %.0f, items %.0f, memsets + block choice %.0f, order %.0f), upload + launch calls %.0f us, waiting for the device %.0f us (kernel %.0f us), records -> stats %.0f us; %zu B up, %zu B down in %lld launch(es)%s\n",
-                F, R, tq_filled - tq0, tq_a - tq0, tq_b - tq_a, tq_c - tq_b, tq_filled - tq_c, tq_launched - tq_filled, tq_synced - tq_launched, 1e3 * c->prof_step_ms, clock_us() - tq_synced,
-                bytes_up, bytes_down, c->prof_launches, host_records ? ", records stored into the pinned block" : "");
+                F, R, tm.ordered - tm.start, tm.checked - tm.start, tm.items - tm.checked, tm.chosen - tm.items, tm.ordered - tm.chosen, tm.launched - tm.ordered,
+                tm.synced - tm.launched, 1e3 * c->prof_step_ms, QueueMarks::now() - tm.synced, tm.bytes_up, tm.bytes_down, c->prof_launches,
+                host_records ? ", records stored into the pinned block" : "");
     return MCRAT_HIP_OK;
 }
 
@@ -3933,14 +3944,14 @@ extern "C" int mcrat_hip_pool_scatter_frames_cyclosynch(mcrat_hip_ctx *c, const 
         c->rank_block = R > 2 * cus ? 128 : 256;
         // ... and with eight and more per CU one wavefront per list (eight on a CU): no wave ever waits at a barrier for the one that walks
         // the event (cfg5: 250 -> 230 ms per frame); only with the hook inside the loop (the hook kernel is written for 128 threads and more)
-        if (R > 8 * cus && !(getenv("MCRAT_HIP_CS_HOOK_KERNEL") && atoi(getenv("MCRAT_HIP_CS_HOOK_KERNEL")) != 0)) c->rank_block = 64;
+        if (R > 8 * cus && !env_flag("MCRAT_HIP_CS_HOOK_KERNEL")) c->rank_block = 64;
         c->rank_fuse = false;
         if (const char *e = getenv("MCRAT_HIP_RANK_BLOCK")) c->rank_block = (atoi(e) == 64) ? 64 : (atoi(e) == 128) ? 128 : 256;
     }
     // The hook runs inside rank_loop_kernel (its CSH build: cs_hook_body right after the pass, the list goes on in the same launch); with
     // MCRAT_HIP_CS_HOOK_KERNEL=1 the lists park after such a pass instead and cs_replace_pool_kernel runs it between two launches (the
     // first form of this driver, kept for the A/B).  Either way a list only stays parked for the host when it has to be rebinned.
-    const bool hook_kernel = getenv("MCRAT_HIP_CS_HOOK_KERNEL") && atoi(getenv("MCRAT_HIP_CS_HOOK_KERNEL")) != 0;
+    const bool hook_kernel = env_flag("MCRAT_HIP_CS_HOOK_KERNEL");
     if (!c->d_cs_args) HIPCHK(c, hipMalloc(&c->d_cs_args, sizeof(CsHookArgs)));
     {
         CsHookArgs ha;
@@ -3950,24 +3961,18 @@ extern "C" int mcrat_hip_pool_scatter_frames_cyclosynch(mcrat_hip_ctx *c, const 
     }
     const CsHookArgs *d_args = hook_kernel ? nullptr : static_cast<const CsHookArgs *>(c->d_cs_args);
     const int pairs_per_sync = hook_kernel ? 8 : 2;
+    // (lists that change length: their columns stay in HBM/L2)
+    RankLaunch rl = rank_launch_of(c, c->d_desc, 4096);
+    rl.longest_list = RANK_COLUMNS_GLOBAL; rl.cs = d_cf; rl.hook = d_args;
     for (;;) {
-        if (c->cfg.profile) {                                    // the loop's launches between events (bench.py: cfg5's loop-only roofline)
-            if ((rc = ensure_events(c, 2))) return rc;
-            HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-        }
-        for (int k = 0; k < pairs_per_sync; ++k) {
-            HIPCHK(c, launch_rank_loop(c->kc, c->ph, c->hy, c->d_rstates, c->key, R, c->rank_stride, 1 << 30, c->d_desc, d_cf, d_args, 4096, c->rank_block,
-                                       c->stream, nullptr, 0, device_info(c)));
-            if (hook_kernel) HIPCHK(c, launch_cs_replace_pool(p, c->hy, c->hcol, c->d_rstates, c->ph, c->rank_stride, R, c->d_desc, d_cf, c->stream));
-        }
-        if (c->cfg.profile) {
-            HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-            HIPCHK(c, hipEventSynchronize(c->ev[1]));
-            float ms = 0;
-            HIPCHK(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-            c->prof_step_ms += ms;
-            c->prof_launches += pairs_per_sync;
-        }
+        rc = profiled(c, pairs_per_sync, [&]() -> int {         // the loop's launches between events (bench.py: cfg5's loop-only roofline)
+            for (int k = 0; k < pairs_per_sync; ++k) {
+                HIPCHK(c, launch_rank_loop(c->kc, c->ph, c->hy, c->d_rstates, c->key, rl, c->stream));
+                if (hook_kernel) HIPCHK(c, launch_cs_replace_pool(p, c->hy, c->hcol, c->d_rstates, c->ph, c->rank_stride, R, c->d_desc, d_cf, c->stream));
+            }
+            return MCRAT_HIP_OK;
+        });
+        if (rc) return rc;
         HIPCHK(c, hipMemcpyAsync(c->h_rstates, c->d_rstates, sizeof(LoopState) * (size_t)R, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(cf.data(), d_cf, sizeof(CsFrame) * (size_t)R, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(c->h_desc, c->d_desc, sizeof(RankDesc) * (size_t)R, hipMemcpyDeviceToHost, c->stream));

@@ -2664,109 +2664,107 @@ static int resident_per_cu(const void *kernel, int device, int threads, size_t d
     return per_cu;
 }
 
-hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key,
-                            int n_ranks, int rank_stride, int longest_list, const RankDesc *desc, CsFrame *cs, const CsHookArgs *hook, long long max_passes,
-                            int block, hipStream_t stream, const FrameQueueDev *fq, int n_open, const RankDeviceInfo *dev)
+// Which builds of rank_loop_kernel exist -- per (DIMS, GEOM, STOKES) of this translation unit -- and why not the others (about 420 instantiations,
+// 53 MB of device code, minutes per translation unit; every form costs 36 of them):
+//   tape     256 threads, columns in HBM/L2, no fused pass, no hook, no queue: a validation mode, one launch form for every list length.
+//   hook     (CSH, the cyclo-synchrotron hook inside the loop) 64, RANK_SMALL or 256 threads; lists that change length: columns in HBM/L2, no fused
+//            pass, no queue (such lists go to the host between passes: one frame per launch).  64 threads -- one wavefront per list, eight lists per
+//            CU: every resident wave is always at work (no barrier waits) -- exist with the hook only.
+//   fused    where engine.hip's choose_rank_block can ask for it: DIRECT optical depths, not in spherical geometry (there it measured slower), 256 or
+//            512 threads (128: it measured no gain on thin frames, round 2).  Everything else has the queue form of a pass only.
+//   queue    256-thread lists with their columns in LDS, with or without the fused pass: carrying the queue's paths costs a build registers (see
+//            rank_loop_kernel); every other launch form runs a plan frame by frame (engine.hip, mcrat_hip_pool_run_frames).
+//   the rest RANK_SMALL, 256 or 512 threads, columns in LDS or in HBM/L2.
+template <int GEOM>
+constexpr bool rank_build_exists(bool resident, int threads, bool fuse, bool hook, bool queue, bool tape)
 {
-    // block: 64, 128, 256 or 512 threads per list, + 1000 for the build with the fused pass
-    const bool fuse = block >= 1000;
-    if (fuse) block -= 1000;
-    RankLayout lay = {n_ranks, rank_stride, ph.n, desc, cs, hook, FrameQueueDev{}};
-    const bool queued = fq && fq->n_frames > 0;
+    if (tape) return threads == 256 && !resident && !fuse && !hook && !queue;
+    if (hook) return (threads == 64 || threads == RANK_SMALL || threads == 256) && !resident && !fuse && !queue;
+    if (fuse && (TABLE_MODE || GEOM == GEOM_SPHERICAL || (threads != 256 && threads != 512))) return false;
+    if (queue) return threads == 256 && resident;
+    return threads == RANK_SMALL || threads == 256 || threads == 512;
+}
+// A launch's form: the template arguments of rank_loop_kernel that are chosen at run time.
+struct RankForm { bool stokes, resident; int threads; bool fuse, hook, queue; };
+// f(kernel) with the build of this form; false, and no call, if there is none.  This is the one place that names a keyed build of the kernel.
+template <int DIMS, int GEOM, class F>
+static bool with_rank_kernel(const RankForm &w, F &&f)
+{
+    bool found = false;
+    auto as_bool = [](bool v, auto &&g) { if (v) g(std::true_type{}); else g(std::false_type{}); };
+    auto as_threads = [](int t, auto &&g) {
+        if (t == 64) g(ic<64>{}); else if (t == RANK_SMALL) g(ic<RANK_SMALL>{}); else if (t == 256) g(ic<256>{}); else if (t == 512) g(ic<512>{});
+    };
+    as_bool(w.stokes, [&](auto S) { as_bool(w.resident, [&](auto R) { as_threads(w.threads, [&](auto T) {
+    as_bool(w.fuse, [&](auto FU) { as_bool(w.hook, [&](auto H) { as_bool(w.queue, [&](auto Q) {
+        constexpr bool SV = decltype(S)::value, RV = decltype(R)::value, FV = decltype(FU)::value, HV = decltype(H)::value, QV = decltype(Q)::value;
+        constexpr int TV = decltype(T)::value;
+        if constexpr (rank_build_exists<GEOM>(RV, TV, FV, HV, QV, false)) {
+            f(rank_loop_kernel<DIMS, GEOM, SV, RV, TV, FV, HV, QV>);
+            found = true;
+        }
+    }); }); }); }); }); });
+    return found;
+}
+
+hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, const RankLaunch &rl,
+                            hipStream_t stream)
+{
+    RankLayout lay = {rl.n_ranks, rl.rank_stride, ph.n, rl.desc, rl.cs, rl.hook, FrameQueueDev{}};
+    const bool queued = rl.fq && rl.fq->n_frames > 0;
     if (queued) {
-        if (cs || n_open <= 0) return hipErrorInvalidValue;   // (cyclo-synchrotron lists go to the host between passes: one frame per launch)
-        lay.fq = *fq;
+        if (rl.cs || rl.n_open <= 0) return hipErrorInvalidValue;   // (cyclo-synchrotron lists go to the host between passes: one frame per launch)
+        lay.fq = *rl.fq;
     }
-    if (cs && hook && desc) {                      // cyclo-synchrotron lists with the hook inside the loop: columns in HBM/L2, no fused pass
-        return dispatch(kc, [&](auto D, auto G) {
-            constexpr int DV = decltype(D)::value, GV = decltype(G)::value;
-            if (block == 64) {                     // one wavefront per list, eight lists per CU: every resident wave is always at work (no barrier waits)
-                if (kc.stokes) rank_loop_kernel<DV, GV, true, false, 64, false, true><<<dim3(n_ranks), dim3(64), 0, stream>>>(ph, hy, states, key, lay, max_passes, 0);
-                else rank_loop_kernel<DV, GV, false, false, 64, false, true><<<dim3(n_ranks), dim3(64), 0, stream>>>(ph, hy, states, key, lay, max_passes, 0);
-            } else if (block == 128) {
-                if (kc.stokes) rank_loop_kernel<DV, GV, true, false, RANK_SMALL, false, true><<<dim3(n_ranks), dim3(RANK_SMALL), 0, stream>>>(ph, hy, states, key, lay, max_passes, 0);
-                else rank_loop_kernel<DV, GV, false, false, RANK_SMALL, false, true><<<dim3(n_ranks), dim3(RANK_SMALL), 0, stream>>>(ph, hy, states, key, lay, max_passes, 0);
-            } else {
-                if (kc.stokes) rank_loop_kernel<DV, GV, true, false, 256, false, true><<<dim3(n_ranks), dim3(256), 0, stream>>>(ph, hy, states, key, lay, max_passes, 0);
-                else rank_loop_kernel<DV, GV, false, false, 256, false, true><<<dim3(n_ranks), dim3(256), 0, stream>>>(ph, hy, states, key, lay, max_passes, 0);
-            }
-        });
-    }
-    // per-pass columns in LDS (32 B per slot with 128 threads, 61 B with 256: rank_loop_kernel) for lists of up to 1024 photons
+    RankForm form{kc.stokes != 0, false, 256, false, rl.cs && rl.hook && rl.desc, queued};
+    // threads per list: an unknown count runs 256 (64 is known with the hook only, 512 without it only)
+    const int block = (rl.threads == 128 || (rl.threads == 64 && form.hook) || (rl.threads == 512 && !form.hook)) ? rl.threads : 256;
+    form.threads = block == 128 ? RANK_SMALL : block;
     int lds_slots = 0;
-    // (two 256-thread lists per CU: 13 KB of static LDS and 61 B per slot each within 160 KB -> 1088 slots; four 128-thread ones at 32 B: 1024)
-    // (512 threads -- lists of thousands of photons, one list per CU: 27 KB of static LDS and 32 B per slot within 160 KB -> 4096 slots)
-    const int lds_limit = (block == 128) ? 1024 : (block == 512 ? 4096 : 1088);
-    if (!getenv("MCRAT_HIP_NO_LDS_LISTS") && longest_list <= lds_limit) lds_slots = (longest_list + 15) & ~15;
-    size_t dyn = (size_t)lds_slots * rank_lds_bytes_per_slot(block == 128 ? 128 : (block == 512 ? 512 : 256));
-    bool queue_launched = false;
-    const hipError_t launched = dispatch(kc, [&](auto D, auto G) {
+    if (!form.hook) {
+        // per-pass columns in LDS (32 B per slot with 128 threads, 61 B with 256: rank_loop_kernel) for lists of up to 1024 photons
+        // (two 256-thread lists per CU: 13 KB of static LDS and 61 B per slot each within 160 KB -> 1088 slots; four 128-thread ones at 32 B: 1024)
+        // (512 threads -- lists of thousands of photons, one list per CU: 27 KB of static LDS and 32 B per slot within 160 KB -> 4096 slots)
+        const int lds_limit = (block == 128) ? 1024 : (block == 512 ? 4096 : 1088);
+        if (!getenv("MCRAT_HIP_NO_LDS_LISTS") && rl.longest_list <= lds_limit) lds_slots = (rl.longest_list + 15) & ~15;
+        form.resident = lds_slots > 0;
+    }
+    const size_t dyn = (size_t)lds_slots * rank_lds_bytes_per_slot(block);
+    bool launched = false;
+    const hipError_t e = dispatch(kc, [&](auto D, auto G) {
         constexpr int DV = decltype(D)::value, GV = decltype(G)::value;
-        // static + dynamic LDS may exceed the 64 KiB default: the kernel must be told, and if the runtime refuses
-        // the list simply stays in global memory (lds_slots = 0)
-        const int grid = queued ? n_open : n_ranks;          // a queue launch: one workgroup per open (frame, list) item
-        if (queued) {
-            // the queue builds: 256-thread lists with their columns in LDS, with or without the fused pass; anything else is refused and the caller
-            // runs the plan frame by frame (engine.hip, mcrat_hip_pool_run_frames)
-            if (block != 256 || lds_slots <= 0) return;
-            auto launch_q = [&](auto kernel) {
-                const int device = launch_device(dev);
-                if (allow_dynamic_lds(reinterpret_cast<const void *>(kernel), device, (int)dyn) != hipSuccess) { (void)hipGetLastError(); return; }
+        // a fused request where no fused build exists runs unfused
+        form.fuse = rl.fuse && rank_build_exists<GV>(form.resident, form.threads, true, form.hook, form.queue, false);
+        const int device = form.resident ? launch_device(rl.dev) : 0;
+        // static + dynamic LDS may exceed the 64 KiB default: the kernel must be told
+        bool lds_refused = false;
+        launched = with_rank_kernel<DV, GV>(form, [&](auto kernel) {
+            int grid = rl.n_ranks;
+            if (form.resident && allow_dynamic_lds(reinterpret_cast<const void *>(kernel), device, (int)dyn) != hipSuccess) {
+                (void)hipGetLastError();
+                lds_refused = true;
+                return;
+            }
+            if (queued) {
                 // persistent workgroups: as many as the device holds at once (they are dealt to the XCDs round-robin, an eighth each); more would only
                 // start, find their queue empty and leave
-                int cus = dev ? dev->cus : 0, grid = n_open;
-                const int per_cu = resident_per_cu(reinterpret_cast<const void *>(kernel), device, 256, dyn);
+                int cus = rl.dev ? rl.dev->cus : 0;
+                const int per_cu = resident_per_cu(reinterpret_cast<const void *>(kernel), device, form.threads, dyn);
                 if (cus <= 0 && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) { (void)hipGetLastError(); cus = 0; }
-                if (per_cu > 0 && cus > 0) grid = std::min(n_open, per_cu * cus);
-                kernel<<<dim3(grid), dim3(256), dyn, stream>>>(ph, hy, states, key, lay, max_passes, lds_slots);
-                queue_launched = true;
-            };
-            if constexpr (!TABLE_MODE && GV != GEOM_SPHERICAL) {
-                if (fuse) {
-                    if (kc.stokes) launch_q(rank_loop_kernel<DV, GV, true, true, 256, true, false, true>);
-                    else launch_q(rank_loop_kernel<DV, GV, false, true, 256, true, false, true>);
-                    return;
-                }
+                grid = (per_cu > 0 && cus > 0) ? std::min(rl.n_open, per_cu * cus) : rl.n_open;
             }
-            if (kc.stokes) launch_q(rank_loop_kernel<DV, GV, true, true, 256, false, false, true>);
-            else launch_q(rank_loop_kernel<DV, GV, false, true, 256, false, false, true>);
-            return;
-        }
-        auto launch = [&](auto kernel, auto kernel_global, int threads) {
-            if (lds_slots > 0 && allow_dynamic_lds(reinterpret_cast<const void *>(kernel), launch_device(dev), (int)dyn) == hipSuccess) {
-                kernel<<<dim3(grid), dim3(threads), dyn, stream>>>(ph, hy, states, key, lay, max_passes, lds_slots);
-            } else {
-                (void)hipGetLastError();
-                kernel_global<<<dim3(grid), dim3(threads), 0, stream>>>(ph, hy, states, key, lay, max_passes, 0);
-            }
-        };
-        // The fused pass exists where engine.hip's choose_rank_block can ask for it: DIRECT optical depths, not in spherical geometry (there it
-        // measured slower), 256 or 512 threads.  Everything else has the queue form only -- a third of the instantiations less than building all.
-        if constexpr (!TABLE_MODE && GV != GEOM_SPHERICAL) {
-            if (fuse && block == 512) {
-                if (kc.stokes) launch(rank_loop_kernel<DV, GV, true, true, 512, true>, rank_loop_kernel<DV, GV, true, false, 512, true>, 512);
-                else launch(rank_loop_kernel<DV, GV, false, true, 512, true>, rank_loop_kernel<DV, GV, false, false, 512, true>, 512);
-                return;
-            }
-            if (fuse && block != 128) {
-                if (kc.stokes) launch(rank_loop_kernel<DV, GV, true, true, 256, true>, rank_loop_kernel<DV, GV, true, false, 256, true>, 256);
-                else launch(rank_loop_kernel<DV, GV, false, true, 256, true>, rank_loop_kernel<DV, GV, false, false, 256, true>, 256);
-                return;
-            }
-        }
-        if (block == 512) {
-            if (kc.stokes) launch(rank_loop_kernel<DV, GV, true, true, 512, false>, rank_loop_kernel<DV, GV, true, false, 512, false>, 512);
-            else launch(rank_loop_kernel<DV, GV, false, true, 512, false>, rank_loop_kernel<DV, GV, false, false, 512, false>, 512);
-        } else if (block == 128) {                 // (no fused build at 128 threads: it measured no gain on thin frames, round 2, and was 36 instantiations)
-            if (kc.stokes) launch(rank_loop_kernel<DV, GV, true, true, RANK_SMALL, false>, rank_loop_kernel<DV, GV, true, false, RANK_SMALL, false>, RANK_SMALL);
-            else launch(rank_loop_kernel<DV, GV, false, true, RANK_SMALL, false>, rank_loop_kernel<DV, GV, false, false, RANK_SMALL, false>, RANK_SMALL);
-        } else {
-            if (kc.stokes) launch(rank_loop_kernel<DV, GV, true, true, 256, false>, rank_loop_kernel<DV, GV, true, false, 256, false>, 256);
-            else launch(rank_loop_kernel<DV, GV, false, true, 256, false>, rank_loop_kernel<DV, GV, false, false, 256, false>, 256);
+            kernel<<<dim3(grid), dim3(form.threads), dyn, stream>>>(ph, hy, states, key, lay, rl.max_passes, lds_slots);
+        });
+        if (lds_refused) {             // the runtime refuses the LDS: the lists simply stay in global memory (a queue launch has no such build)
+            RankForm global = form;
+            global.resident = false;
+            launched = with_rank_kernel<DV, GV>(global, [&](auto kernel) {
+                kernel<<<dim3(rl.n_ranks), dim3(form.threads), 0, stream>>>(ph, hy, states, key, lay, rl.max_passes, 0);
+            });
         }
     });
-    if (queued && !queue_launched && launched == hipSuccess) return hipErrorNotSupported;      // no queue build of this launch form: frame by frame then
-    return launched;
+    if (queued && !launched && e == hipSuccess) return hipErrorNotSupported;      // no queue build of this launch form: frame by frame then
+    return e;
 }
 
 // the tape build: one launch form for every list length (256 threads, columns in HBM/L2, no fused pass)
@@ -2780,6 +2778,7 @@ hipError_t launch_rank_loop_tape(const KernelConfig &kc, const PhotonDev &ph, co
     lay.tapes = tapes;
     return dispatch(kc, [&](auto D, auto G) {
         constexpr int DV = decltype(D)::value, GV = decltype(G)::value;
+        static_assert(rank_build_exists<GV>(false, 256, false, false, false, true), "the tape build");
         if (kc.stokes) rank_loop_kernel<DV, GV, true, false, 256, false, false, false, true><<<dim3(n_ranks), dim3(256), 0, stream>>>(ph, hy, states, key, lay, max_passes, 0);
         else rank_loop_kernel<DV, GV, false, false, 256, false, false, false, true><<<dim3(n_ranks), dim3(256), 0, stream>>>(ph, hy, states, key, lay, max_passes, 0);
     });

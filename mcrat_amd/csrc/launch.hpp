@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "device_types.hpp"
+#include "frame_queue.hpp"
 
 namespace mcrat {
 
@@ -32,74 +33,32 @@ hipError_t launch_event(const KernelConfig &kc, const PhotonDev &ph, const Hydro
 struct TapeDev;
 hipError_t launch_tape_pass(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, RngKey key, const TapeDev &tape,
                             Cand *block_min, int n_blocks, Shortlist *sl, hipStream_t stream);
-// virtual ranks: every workgroup (of `block` = 128 or 256 threads) runs the whole loop of one independent photon list: the slots
+// virtual ranks: every workgroup (of RankLaunch::threads threads) runs the whole loop of one independent photon list: the slots
 // [r * rank_stride, ...) -- rank_stride of them, or desc[r].len with the list's own seed and stream (rank pool); longest_list sizes the LDS copy
 // hook: (device memory) what the cyclo-synchrotron hook needs -- then lists with `cs` run it inside the loop instead of parking for
 // cs_replace_pool_kernel after every pass it has to look at
-// The frame queue (round 4): ONE launch takes every list through SEVERAL hydro frames.  The reference's ranks are asynchronous processes, each in
-// its own frame loop (mcrat.c:457-479, :566-934); a launch per hydro frame makes them wait for each other at every frame's end.  A queue launch has
-// as many persistent workgroups as the device holds; each draws (frame, list) items from the queue of the XCD it runs on until that is empty, the k-th
-// draw on an XCD getting the k-th open item of that XCD's lists in frame-major order (`order`, `ticket`): a list that is through frame f starts f + 1 as
-// soon as a workgroup is free, while other lists are still in f.  The item of a list whose previous frame is still running waits for it (frames_done;
-// that item was drawn earlier, by a workgroup that is running and depends on nothing later, so this cannot deadlock).  Every list sees exactly the frames it would have seen one launch at a time: the same seeds, clocks, passes and photons
-// (tests/test_gpu_frame_queue.py).
-struct FrameItem {                   // list r in frame f: item f * n_ranks + r
-    unsigned long long seed;         // the list's seed of this frame (gsl_rng_get, mcrat.c:701)
-    double time_now;                 // its clock at the start of the frame ...
-    double remaining_time;           // ... and the time left in it (mcrat.c:757), unless the clock is chained (below)
-    double frame_end;                // (scatt_frame + increment_scatt_frame) / fps: a chained list gets frame_end - its own time_now, the host's expression
-    int open;                        // the list takes part in this frame (a rank joins at its injection frame, mcrat.c:566-700)
-    int hydro;                       // which staged hydro frame of the launch it propagates through
-};
-// What a (frame, list) item leaves for the host: the members of LoopState that mcrat_hip_frame_stats shows (engine.hip, state_to_stats) and `done` -- not
-// the pending segments, the shortlist's estimates or the diagnostic stamps, which only the kernel reads (a stalled list resumes from states[rank], a full
-// LoopState).  One lane stores it when the item's frame ends, complete or at the launch's pass limit, and when a frame has no time left.
-// VALIDITY.  The records' buffer is never cleared, so a record means something only for an item the kernel is KNOWN to have written in this call, and the
-// host decides that from frames_done[list] alone (read back with the records): with d = frames_done & ~FRAME_STALLED, the list's open items of frames
-// < d are complete and their records written; with FRAME_STALLED set, so is the record of frame d (iterations > 0, done == 0: the frame goes on with
-// open = 2); every later item of the list gave up or was never drawn, wrote nothing, and its record holds whatever an earlier call left there.
-struct alignas(32) FrameRecord {
-    double remaining_time, time_now;
-    long long iterations;
-    int done;
-    int last_scattered_index;
-    double last_time_step, last_scattered_temp;
-    long long frame_scatt_cnt, n_relocated;
-    long long not_found, kn_rejections, rescans, slot_steps;
-    __host__ __device__ void from_state(const LoopState &s)
-    {
-        remaining_time = s.remaining_time; time_now = s.time_now; iterations = s.iterations; done = s.done; last_scattered_index = s.last_scattered_index;
-        last_time_step = s.last_time_step; last_scattered_temp = s.last_scattered_temp; frame_scatt_cnt = s.frame_scatt_cnt; n_relocated = s.n_relocated;
-        not_found = s.not_found; kn_rejections = s.kn_rejections; rescans = s.rescans; slot_steps = s.slot_steps;
-    }
-};
-static_assert(sizeof(FrameRecord) <= 128, "the frame record stays compact: at most half a LoopState");
-struct FrameQueueDev {
-    int n_frames;                  // 0: no queue -- one workgroup per list, one frame, as before
-    int restore;                     // every frame starts from the context's snapshot (mcrat_hip_snapshot_photons; benchmarks: the same work every frame)
-    int chain_clock;                 // a list's clock carries over from its previous frame of this launch (time_now of the LoopState it left)
-    int pad;
-    unsigned *ticket;                // [FRAME_QUEUE_XCDS * FRAME_TICKET_STRIDE] per XCD: workgroups that have started there
-    const int *order;                // [open items] per XCD (order_off[x] .. order_off[x + 1]) its lists' items in the order they are taken: frame-major
-    int order_off[9];
-    unsigned *frames_done;           // [n_ranks] f + 1 once item (f, r) is complete; FRAME_STALLED | f: frame f ran into the launch's pass limit
-    const FrameItem *items;          // [n_frames * n_ranks]
-    const HydroDev *hydro;           // [n_hydro] the staged hydro frames of the launch (FrameItem::hydro indexes it); read through the constant address space
-    FrameRecord *records;            // [n_frames * n_ranks] what every frame ended with (see FrameRecord for which of them may be read)
-    long long snap_delta;            // bytes from a column of the live lists to its copy in the snapshot (restore)
-    long long capture_delta, capture_stride;   // != 0: at the end of frame f < n_frames - 1 the list's columns are copied to live + capture_delta + f * capture_stride
-};
-constexpr unsigned FRAME_STALLED = 0x80000000u;
-constexpr int FRAME_QUEUE_XCDS = 8, FRAME_TICKET_STRIDE = 16;     // (a ticket per XCD, each on a 64-B line of its own)
+// The frame queue -- ONE launch takes every list through SEVERAL hydro frames -- is frame_queue.hpp: FrameQueueDev, its items and records.
 // What a context knows about its device from its creation on, so that no launch has to ask again (nullptr: the launcher asks the runtime).
 struct RankDeviceInfo { int device, cus; };
-// `fq` (n_frames > 0, n_open items in fq->order) makes it a queue launch: one workgroup per open item
+// One launch of the rank loop: the lists, the form they run in, and what goes with them.
+struct RankLaunch {
+    int n_ranks = 0, rank_stride = 0;    // the lists: [r * rank_stride, ...), as above
+    int longest_list = 0;                // sizes the LDS copy of the per-pass columns; RANK_COLUMNS_GLOBAL: the columns stay in HBM/L2
+    const RankDesc *desc = nullptr;
+    int threads = 256;                   // per list: 64 (with the hook only), 128, 256 or 512; anything else runs 256
+    bool fuse = false;                   // the build with the fused pass, where one exists (kernels.hip, rank_build_exists); unfused where not
+    long long max_passes = 0;            // per list and launch
+    struct CsFrame *cs = nullptr;        // cyclo-synchrotron lists ...
+    const struct CsHookArgs *hook = nullptr;   // ... and the hook inside the loop (above)
+    const FrameQueueDev *fq = nullptr;   // n_frames > 0 makes it a queue launch: persistent workgroups, at most one per open item: n_open of them for
+    int n_open = 0;                      //   the items in fq->order.  A form without a queue build: hipErrorNotSupported, and nothing is launched
+    const RankDeviceInfo *dev = nullptr;
+};
+constexpr int RANK_COLUMNS_GLOBAL = 1 << 30;      // RankLaunch::longest_list of lists that change length: no list is short enough for LDS
 // The launcher asks the runtime once per kernel: the dynamic-LDS limit it has set for a kernel and the occupancy it was told for a (kernel, LDS size)
 // are remembered (kernels.hip, KernelNote), so a second launch of the same form makes no hipFuncSetAttribute and no occupancy query.
-hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key,
-                            int n_ranks, int rank_stride, int longest_list, const RankDesc *desc, struct CsFrame *cs, const struct CsHookArgs *hook,
-                            long long max_passes, int block, hipStream_t stream, const FrameQueueDev *fq = nullptr, int n_open = 0,
-                            const RankDeviceInfo *dev = nullptr);
+hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, const RankLaunch &rl,
+                            hipStream_t stream);
 // The tape build of the rank pool (mcrat_hip_pool_set_rng_tapes): every list of a pool that holds tapes goes through it, whatever choose_rank_block
 // would pick -- 256 threads per list, columns in HBM/L2, no fused pass, no frame queue.  A list with a tape takes its free-path draws and its events'
 // draws from it, in MCRaT's call order, as the one-list tape path does (launch_tape_pass); a list without one draws from its keyed streams exactly as

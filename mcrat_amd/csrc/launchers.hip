@@ -7,24 +7,27 @@
 
 namespace mcrat {
 
-namespace tau_direct_d0 {
-hipError_t launch_step(const KernelConfig &kc, bool force_relocate, const PhotonDev &ph, const HydroDev &hy,
-                       LoopState *st, RngKey key, Cand *block_min, int blocks, Shortlist *sl, hipStream_t stream);
-hipError_t launch_event(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, RngKey key,
-                        const Cand *block_min, int n_blocks, Shortlist *sl, hipStream_t stream);
-hipError_t launch_tape_pass(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, RngKey key, const TapeDev &tape,
-                            Cand *block_min, int n_blocks, Shortlist *sl, hipStream_t stream);
-hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key,
-                            int n_ranks, int rank_stride, int longest_list, const RankDesc *desc, CsFrame *cs, const CsHookArgs *hook, long long max_passes,
-                            int block, hipStream_t stream, const FrameQueueDev *fq, int n_open, const RankDeviceInfo *dev);
-hipError_t launch_rank_loop_tape(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, int n_ranks, int rank_stride,
-                                 const RankDesc *desc, const double *u, TapeList *tapes, long long max_passes, hipStream_t stream);
-hipError_t launch_sc_propose(const KernelConfig &kc, bool force_relocate, const PhotonDev &ph, const HydroDev &hy, LoopState *st,
-                             ScState *sc, RngKey key, Cand *block_min, int blocks, Shortlist *sl, ScProposal *out, const ScFold &fold, hipStream_t stream);
-hipError_t launch_sc_resolve(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, ScState *sc, RngKey key,
-                             const ScProposal *all, int world, const ScFold &fold, hipStream_t stream);
-hipError_t launch_fast_frame(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, RngKey key, double remaining_time, int windows,
+// the launchers every kernels translation unit defines in its namespace (kernels.hip, MCRAT_TU_NS)
+#define MCRAT_TU_LAUNCHERS                                                                                                                                      \
+hipError_t launch_step(const KernelConfig &kc, bool force_relocate, const PhotonDev &ph, const HydroDev &hy,                                                    \
+                       LoopState *st, RngKey key, Cand *block_min, int blocks, Shortlist *sl, hipStream_t stream);                                              \
+hipError_t launch_event(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, RngKey key,                                             \
+                        const Cand *block_min, int n_blocks, Shortlist *sl, hipStream_t stream);                                                                \
+hipError_t launch_tape_pass(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, RngKey key, const TapeDev &tape,                    \
+                            Cand *block_min, int n_blocks, Shortlist *sl, hipStream_t stream);                                                                  \
+hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, const RankLaunch &rl,               \
+                            hipStream_t stream);                                                                                                                \
+hipError_t launch_rank_loop_tape(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, int n_ranks, int rank_stride,  \
+                                 const RankDesc *desc, const double *u, TapeList *tapes, long long max_passes, hipStream_t stream);                             \
+hipError_t launch_sc_propose(const KernelConfig &kc, bool force_relocate, const PhotonDev &ph, const HydroDev &hy, LoopState *st,                               \
+                             ScState *sc, RngKey key, Cand *block_min, int blocks, Shortlist *sl, ScProposal *out, const ScFold &fold, hipStream_t stream);     \
+hipError_t launch_sc_resolve(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, ScState *sc, RngKey key,                           \
+                             const ScProposal *all, int world, const ScFold &fold, hipStream_t stream);                                                         \
+hipError_t launch_fast_frame(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, RngKey key, double remaining_time, int windows,                   \
                              int max_passes, FastCounts *counts, const FastLists &lists, hipStream_t stream);
+
+namespace tau_direct_d0 {
+MCRAT_TU_LAUNCHERS
 int step_grid_blocks(int n_pad);
 hipError_t launch_flush(const PhotonDev &ph, LoopState *st, int blocks, hipStream_t stream);
 hipError_t launch_k2e(const double *temp, double *k2e, int M, hipStream_t stream);
@@ -32,106 +35,11 @@ hipError_t launch_reduce(const PhotonDev &ph, ReducePartial *out, int blocks, hi
 hipError_t launch_lookup(const KernelConfig &kc, const HydroDev &hy, int n, const double *a0, const double *a1, const double *a2, int *out,
                          hipStream_t stream);
 }  // namespace tau_direct_d0
-
-namespace tau_direct_d1 {
-hipError_t launch_step(const KernelConfig &kc, bool force_relocate, const PhotonDev &ph, const HydroDev &hy,
-                       LoopState *st, RngKey key, Cand *block_min, int blocks, Shortlist *sl, hipStream_t stream);
-hipError_t launch_event(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, RngKey key,
-                        const Cand *block_min, int n_blocks, Shortlist *sl, hipStream_t stream);
-hipError_t launch_tape_pass(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, RngKey key, const TapeDev &tape,
-                            Cand *block_min, int n_blocks, Shortlist *sl, hipStream_t stream);
-hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key,
-                            int n_ranks, int rank_stride, int longest_list, const RankDesc *desc, CsFrame *cs, const CsHookArgs *hook, long long max_passes,
-                            int block, hipStream_t stream, const FrameQueueDev *fq, int n_open, const RankDeviceInfo *dev);
-hipError_t launch_rank_loop_tape(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, int n_ranks, int rank_stride,
-                                 const RankDesc *desc, const double *u, TapeList *tapes, long long max_passes, hipStream_t stream);
-hipError_t launch_sc_propose(const KernelConfig &kc, bool force_relocate, const PhotonDev &ph, const HydroDev &hy, LoopState *st,
-                             ScState *sc, RngKey key, Cand *block_min, int blocks, Shortlist *sl, ScProposal *out, const ScFold &fold, hipStream_t stream);
-hipError_t launch_sc_resolve(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, ScState *sc, RngKey key,
-                             const ScProposal *all, int world, const ScFold &fold, hipStream_t stream);
-hipError_t launch_fast_frame(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, RngKey key, double remaining_time, int windows,
-                             int max_passes, FastCounts *counts, const FastLists &lists, hipStream_t stream);
-}  // namespace tau_direct_d1
-
-namespace tau_direct_d2 {
-hipError_t launch_step(const KernelConfig &kc, bool force_relocate, const PhotonDev &ph, const HydroDev &hy,
-                       LoopState *st, RngKey key, Cand *block_min, int blocks, Shortlist *sl, hipStream_t stream);
-hipError_t launch_event(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, RngKey key,
-                        const Cand *block_min, int n_blocks, Shortlist *sl, hipStream_t stream);
-hipError_t launch_tape_pass(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, RngKey key, const TapeDev &tape,
-                            Cand *block_min, int n_blocks, Shortlist *sl, hipStream_t stream);
-hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key,
-                            int n_ranks, int rank_stride, int longest_list, const RankDesc *desc, CsFrame *cs, const CsHookArgs *hook, long long max_passes,
-                            int block, hipStream_t stream, const FrameQueueDev *fq, int n_open, const RankDeviceInfo *dev);
-hipError_t launch_rank_loop_tape(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, int n_ranks, int rank_stride,
-                                 const RankDesc *desc, const double *u, TapeList *tapes, long long max_passes, hipStream_t stream);
-hipError_t launch_sc_propose(const KernelConfig &kc, bool force_relocate, const PhotonDev &ph, const HydroDev &hy, LoopState *st,
-                             ScState *sc, RngKey key, Cand *block_min, int blocks, Shortlist *sl, ScProposal *out, const ScFold &fold, hipStream_t stream);
-hipError_t launch_sc_resolve(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, ScState *sc, RngKey key,
-                             const ScProposal *all, int world, const ScFold &fold, hipStream_t stream);
-hipError_t launch_fast_frame(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, RngKey key, double remaining_time, int windows,
-                             int max_passes, FastCounts *counts, const FastLists &lists, hipStream_t stream);
-}  // namespace tau_direct_d2
-
-namespace tau_table_d0 {
-hipError_t launch_step(const KernelConfig &kc, bool force_relocate, const PhotonDev &ph, const HydroDev &hy,
-                       LoopState *st, RngKey key, Cand *block_min, int blocks, Shortlist *sl, hipStream_t stream);
-hipError_t launch_event(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, RngKey key,
-                        const Cand *block_min, int n_blocks, Shortlist *sl, hipStream_t stream);
-hipError_t launch_tape_pass(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, RngKey key, const TapeDev &tape,
-                            Cand *block_min, int n_blocks, Shortlist *sl, hipStream_t stream);
-hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key,
-                            int n_ranks, int rank_stride, int longest_list, const RankDesc *desc, CsFrame *cs, const CsHookArgs *hook, long long max_passes,
-                            int block, hipStream_t stream, const FrameQueueDev *fq, int n_open, const RankDeviceInfo *dev);
-hipError_t launch_rank_loop_tape(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, int n_ranks, int rank_stride,
-                                 const RankDesc *desc, const double *u, TapeList *tapes, long long max_passes, hipStream_t stream);
-hipError_t launch_sc_propose(const KernelConfig &kc, bool force_relocate, const PhotonDev &ph, const HydroDev &hy, LoopState *st,
-                             ScState *sc, RngKey key, Cand *block_min, int blocks, Shortlist *sl, ScProposal *out, const ScFold &fold, hipStream_t stream);
-hipError_t launch_sc_resolve(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, ScState *sc, RngKey key,
-                             const ScProposal *all, int world, const ScFold &fold, hipStream_t stream);
-hipError_t launch_fast_frame(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, RngKey key, double remaining_time, int windows,
-                             int max_passes, FastCounts *counts, const FastLists &lists, hipStream_t stream);
-}  // namespace tau_table_d0
-
-namespace tau_table_d1 {
-hipError_t launch_step(const KernelConfig &kc, bool force_relocate, const PhotonDev &ph, const HydroDev &hy,
-                       LoopState *st, RngKey key, Cand *block_min, int blocks, Shortlist *sl, hipStream_t stream);
-hipError_t launch_event(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, RngKey key,
-                        const Cand *block_min, int n_blocks, Shortlist *sl, hipStream_t stream);
-hipError_t launch_tape_pass(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, RngKey key, const TapeDev &tape,
-                            Cand *block_min, int n_blocks, Shortlist *sl, hipStream_t stream);
-hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key,
-                            int n_ranks, int rank_stride, int longest_list, const RankDesc *desc, CsFrame *cs, const CsHookArgs *hook, long long max_passes,
-                            int block, hipStream_t stream, const FrameQueueDev *fq, int n_open, const RankDeviceInfo *dev);
-hipError_t launch_rank_loop_tape(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, int n_ranks, int rank_stride,
-                                 const RankDesc *desc, const double *u, TapeList *tapes, long long max_passes, hipStream_t stream);
-hipError_t launch_sc_propose(const KernelConfig &kc, bool force_relocate, const PhotonDev &ph, const HydroDev &hy, LoopState *st,
-                             ScState *sc, RngKey key, Cand *block_min, int blocks, Shortlist *sl, ScProposal *out, const ScFold &fold, hipStream_t stream);
-hipError_t launch_sc_resolve(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, ScState *sc, RngKey key,
-                             const ScProposal *all, int world, const ScFold &fold, hipStream_t stream);
-hipError_t launch_fast_frame(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, RngKey key, double remaining_time, int windows,
-                             int max_passes, FastCounts *counts, const FastLists &lists, hipStream_t stream);
-}  // namespace tau_table_d1
-
-namespace tau_table_d2 {
-hipError_t launch_step(const KernelConfig &kc, bool force_relocate, const PhotonDev &ph, const HydroDev &hy,
-                       LoopState *st, RngKey key, Cand *block_min, int blocks, Shortlist *sl, hipStream_t stream);
-hipError_t launch_event(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, RngKey key,
-                        const Cand *block_min, int n_blocks, Shortlist *sl, hipStream_t stream);
-hipError_t launch_tape_pass(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, RngKey key, const TapeDev &tape,
-                            Cand *block_min, int n_blocks, Shortlist *sl, hipStream_t stream);
-hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key,
-                            int n_ranks, int rank_stride, int longest_list, const RankDesc *desc, CsFrame *cs, const CsHookArgs *hook, long long max_passes,
-                            int block, hipStream_t stream, const FrameQueueDev *fq, int n_open, const RankDeviceInfo *dev);
-hipError_t launch_rank_loop_tape(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, int n_ranks, int rank_stride,
-                                 const RankDesc *desc, const double *u, TapeList *tapes, long long max_passes, hipStream_t stream);
-hipError_t launch_sc_propose(const KernelConfig &kc, bool force_relocate, const PhotonDev &ph, const HydroDev &hy, LoopState *st,
-                             ScState *sc, RngKey key, Cand *block_min, int blocks, Shortlist *sl, ScProposal *out, const ScFold &fold, hipStream_t stream);
-hipError_t launch_sc_resolve(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, ScState *sc, RngKey key,
-                             const ScProposal *all, int world, const ScFold &fold, hipStream_t stream);
-hipError_t launch_fast_frame(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, RngKey key, double remaining_time, int windows,
-                             int max_passes, FastCounts *counts, const FastLists &lists, hipStream_t stream);
-}  // namespace tau_table_d2
+namespace tau_direct_d1 { MCRAT_TU_LAUNCHERS }
+namespace tau_direct_d2 { MCRAT_TU_LAUNCHERS }
+namespace tau_table_d0 { MCRAT_TU_LAUNCHERS }
+namespace tau_table_d1 { MCRAT_TU_LAUNCHERS }
+namespace tau_table_d2 { MCRAT_TU_LAUNCHERS }
 
 #define MCRAT_ROUTE(fn, ...)                                                                     \
     do {                                                                                         \
@@ -167,11 +75,10 @@ hipError_t launch_tape_pass(const KernelConfig &kc, const PhotonDev &ph, const H
     MCRAT_ROUTE(launch_tape_pass, kc, ph, hy, st, key, tape, block_min, n_blocks, sl, stream);
 }
 
-hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key,
-                            int n_ranks, int rank_stride, int longest_list, const RankDesc *desc, CsFrame *cs, const CsHookArgs *hook, long long max_passes,
-                            int block, hipStream_t stream, const FrameQueueDev *fq, int n_open, const RankDeviceInfo *dev)
+hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, const RankLaunch &rl,
+                            hipStream_t stream)
 {
-    MCRAT_ROUTE(launch_rank_loop, kc, ph, hy, states, key, n_ranks, rank_stride, longest_list, desc, cs, hook, max_passes, block, stream, fq, n_open, dev);
+    MCRAT_ROUTE(launch_rank_loop, kc, ph, hy, states, key, rl, stream);
 }
 
 hipError_t launch_rank_loop_tape(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, int n_ranks, int rank_stride,

@@ -1,5 +1,5 @@
 """The frame queue's host path (mcrat_hip_pool_run_frames): what comes back from a queue launch is one compact record per (frame, list) item
-(launch.hpp, FrameRecord) in a buffer that is never cleared, read back with the tickets and frames_done in one copy; the host may read a record
+(frame_queue.hpp, FrameRecord) in a buffer that is never cleared, read back with the tickets and frames_done in one copy; the host may read a record
 only where frames_done says the kernel wrote it in this call.  None of that may show: every case runs a plan through the queue and through the
 same call with MCRAT_HIP_NO_FRAME_QUEUE=1 (one launch per frame, a full LoopState read back per launch) on a second pool, and every field of
 every item's mcrat_hip_frame_stats and every photon column must be the same bit for bit -- closed items all zero.  The shapes are the smallest
