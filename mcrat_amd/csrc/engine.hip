@@ -19,6 +19,7 @@
 #include "../../include/mcrat_hip.h"
 #include "device_types.hpp"
 #include "launch.hpp"
+#include "photon_cols.hpp"
 #include "rng.hpp"
 
 using namespace mcrat;
@@ -176,6 +177,31 @@ struct mcrat_hip_ctx {
 
 static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 static bool env_flag(const char *name) { const char *e = getenv(name); return e && atoi(e) != 0; }      // an environment switch: set, and not to 0
+
+// a temporary device array of one call: freed where its scope ends, whichever way the call leaves it
+template <class T>
+struct DeviceTemp {
+    T *p = nullptr;
+    size_t cap = 0;
+    DeviceTemp() = default;
+    DeviceTemp(const DeviceTemp &) = delete;
+    ~DeviceTemp() { (void)hipFree(p); }
+    hipError_t alloc(size_t count) { cap = count; return hipMalloc((void **)&p, sizeof(T) * count); }       // once
+    // room for `count`: a larger array when there is not (the contents go)
+    hipError_t reserve(size_t count) { if (count <= cap) return hipSuccess; (void)hipFree(p); p = nullptr; return alloc(count); }
+    operator T *() const { return p; }
+};
+
+static InjectParams inject_params(const mcrat_hip_ctx *c, const Region &slab)
+{
+    return InjectParams{c->kc.dimensions, c->kc.geometry, slab.rmin, slab.rmax, slab.tmin, slab.tmax, inject_num_dens_coeff(slab.wien != 0), slab.wien};
+}
+// what the emission kernels and the hook are given; the shell is left empty (the hook has none: emit_into)
+static CsEmitParams cs_emit_params(const mcrat_hip_ctx *c, const mcrat_hip_cyclosynch *cs)
+{
+    return CsEmitParams{c->kc.dimensions, c->kc.geometry, cs->b_field_calc, cs->epsilon_b, 0.0, 0.0, 0.0, 0.0};
+}
+static void emit_into(CsEmitParams &p, const Region &shell) { p.rmin = shell.rmin; p.rmax = shell.rmax; p.theta_min = shell.tmin; p.theta_max = shell.tmax; }
 
 static void drop_graph(mcrat_hip_ctx *c)
 {
@@ -1585,30 +1611,23 @@ extern "C" int mcrat_hip_inject_photons(mcrat_hip_ctx *c, double r_inj, double p
     if (!c || !(ph_weight > 0) || !(fps > 0) || min_photons < 0 || max_photons < min_photons || (spect != 'b' && spect != 'w')) return MCRAT_HIP_EINVAL;
     if (!c->have_hydro) return MCRAT_HIP_ESTATE;
     const int M = c->hy.M;
-    InjectParams p;
-    p.dimensions = c->kc.dimensions; p.geometry = c->kc.geometry;
-    p.rmin = r_inj - 0.5 * C_LIGHT / fps;                      // mclib.c:34-35
-    p.rmax = r_inj + 0.5 * C_LIGHT / fps;
-    p.theta_min = theta_min; p.theta_max = theta_max;
-    p.num_dens_coeff = (spect == 'w') ? (double)8.44f : (double)20.29f;   // a float in the reference, mclib.c:17,23-32
-    p.wien = spect == 'w';
+    const RadialRange slab = inject_slab_radii(r_inj, fps);
+    const InjectParams p = inject_params(c, Region{slab.rmin, slab.rmax, theta_min, theta_max, spect == 'w'});
     RngKey key = c->key;
     key.seed = seed;
     { int rc_ = ensure_counts(c, (size_t)M); if (rc_) return rc_; }
-    // mclib.c:87-136: draw the per-cell counts; too many photons -> weight x 10, too few -> weight x 0.5, draw again
+    // mclib.c:87-136: draw the per-cell counts until the weight fits (weight_search_step)
     double weight = ph_weight;
     unsigned long long total = 0;
     bool ok = false;
-    for (unsigned long long attempt = 0; attempt <= 200; ++attempt) {
+    for (unsigned long long attempt = 0; attempt <= 200 && !ok; ++attempt) {
         HIPCHK(c, launch_inject_count(p, c->hy, weight, attempt, key, c->grid_count, c->d_grid_total, c->stream));
         HIPCHK(c, hipMemcpyAsync(&total, c->d_grid_total, sizeof total, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (total > (unsigned long long)max_photons) weight *= 10;
-        else if (total < (unsigned long long)min_photons) weight *= 0.5;
-        else { ok = true; break; }
+        ok = weight_search_step(total, min_photons, (double)max_photons, &weight);
     }
-    if (!ok) { c->last_error = "photon injection: no weight puts the photon count between min_photons and max_photons"; return MCRAT_HIP_EINVAL; }
-    if (total == 0) { c->last_error = "photon injection: no photons (no cell of the frame touches the injection slab?)"; return MCRAT_HIP_EINVAL; }
+    if (!ok) { c->last_error = list_refusal_text(INJECT_NO_WEIGHT); return MCRAT_HIP_EINVAL; }
+    if (total == 0) { c->last_error = list_refusal_text(INJECT_NO_PHOTONS); return MCRAT_HIP_EINVAL; }
     const int n = (int)total;
     int rc = alloc_photons(c, n);
     if (rc) return rc;
@@ -1636,8 +1655,8 @@ extern "C" int mcrat_hip_pool_inject_photons(mcrat_hip_ctx *c, double fps, mcrat
     if (!c->is_pool) return MCRAT_HIP_ESTATE;
     if (!c->have_hydro) return MCRAT_HIP_ESTATE;
     const int R = c->n_ranks, M = c->hy.M;
-    struct Slab { double rmin, rmax, tmin, tmax; int wien; };
-    std::vector<Slab> slabs;
+    std::vector<Region> slabs((size_t)R);                   // the lists grouped by their slab
+    int n_slabs = 0;
     std::vector<PoolInject> pi((size_t)R);
     bool any = false;
     int rc;
@@ -1660,46 +1679,33 @@ extern "C" int mcrat_hip_pool_inject_photons(mcrat_hip_ctx *c, double fps, mcrat
         mcrat_hip_ctx *v = c->views[r];
         if ((rc = alloc_view_photons(v, 0))) { c->last_error = v->last_error; return rc; }      // the window cleared, the view's columns in place
         v->have_photons = false;
-        Slab sl{q.r_inj - 0.5 * C_LIGHT / fps, q.r_inj + 0.5 * C_LIGHT / fps, q.theta_min, q.theta_max, q.spect == 'w'};   // mclib.c:34-35
-        int g = -1;
-        for (size_t k = 0; k < slabs.size(); ++k)
-            if (slabs[k].rmin == sl.rmin && slabs[k].rmax == sl.rmax && slabs[k].tmin == sl.tmin && slabs[k].tmax == sl.tmax && slabs[k].wien == sl.wien) { g = (int)k; break; }
-        if (g < 0) { g = (int)slabs.size(); slabs.push_back(sl); }
+        const RadialRange slab = inject_slab_radii(q.r_inj, fps);
         PoolInject &e = pi[(size_t)r];
-        e.inject = 1; e.group = g; e.seed = q.seed; e.stream = v->key.stream; e.weight_in = q.ph_weight; e.min_photons = q.min_photons; e.max_photons = q.max_photons;
+        e.inject = 1; e.group = region_group(slabs.data(), &n_slabs, Region{slab.rmin, slab.rmax, q.theta_min, q.theta_max, q.spect == 'w'});
+        e.seed = q.seed; e.stream = v->key.stream; e.weight_in = q.ph_weight; e.min_photons = q.min_photons; e.max_photons = q.max_photons;
         any = true;
     }
     if (!any) return MCRAT_HIP_OK;
     if ((rc = ensure_counts(c, (size_t)M + 8))) return rc;
-    const size_t scan_ints = (size_t)M + 1 + grid_scan_scratch_ints(M);
-    int *d_start = nullptr;
-    PoolInject *d_pi = nullptr;
-    InjectSlabCell *d_slab = nullptr;
-    size_t slab_cap = 0;
-    auto done = [&](int code) { (void)hipFree(d_start); (void)hipFree(d_pi); (void)hipFree(d_slab); return code; };
-    if (hipMalloc((void **)&d_start, sizeof(int) * scan_ints) != hipSuccess || hipMalloc((void **)&d_pi, sizeof(PoolInject) * (size_t)R) != hipSuccess)
-        return done(MCRAT_HIP_ENOMEM);
-    if (hipMemcpyAsync(d_pi, pi.data(), sizeof(PoolInject) * (size_t)R, hipMemcpyHostToDevice, c->stream) != hipSuccess) return done(MCRAT_HIP_EHIP);
-    for (size_t g = 0; g < slabs.size(); ++g) {
-        InjectParams p;
-        p.dimensions = c->kc.dimensions; p.geometry = c->kc.geometry;
-        p.rmin = slabs[g].rmin; p.rmax = slabs[g].rmax; p.theta_min = slabs[g].tmin; p.theta_max = slabs[g].tmax;
-        p.num_dens_coeff = slabs[g].wien ? (double)8.44f : (double)20.29f;   // a float in the reference, mclib.c:17,23-32
-        p.wien = slabs[g].wien;
-        int n_slab = 0;
-        if (launch_inject_slab_flag(p, c->hy, c->grid_count, c->d_grid_total, &n_slab, c->stream) != hipSuccess) return done(MCRAT_HIP_EHIP);
-        if ((size_t)n_slab > slab_cap) {
-            (void)hipFree(d_slab); d_slab = nullptr;
-            if (hipMalloc((void **)&d_slab, sizeof(InjectSlabCell) * (size_t)n_slab) != hipSuccess) return done(MCRAT_HIP_ENOMEM);
-            slab_cap = (size_t)n_slab;
+    {                                                       // (the temporaries go before the lists are committed: a list may take the one-list path below)
+        const size_t scan_ints = (size_t)M + 1 + grid_scan_scratch_ints(M);
+        DeviceTemp<int> d_start;
+        DeviceTemp<PoolInject> d_pi;
+        DeviceTemp<InjectSlabCell> d_slab;
+        if (d_start.alloc(scan_ints) != hipSuccess || d_pi.alloc((size_t)R) != hipSuccess) return MCRAT_HIP_ENOMEM;
+        if (hipMemcpyAsync(d_pi, pi.data(), sizeof(PoolInject) * (size_t)R, hipMemcpyHostToDevice, c->stream) != hipSuccess) return MCRAT_HIP_EHIP;
+        for (int g = 0; g < n_slabs; ++g) {
+            const InjectParams p = inject_params(c, slabs[(size_t)g]);
+            int n_slab = 0;
+            if (launch_inject_slab_flag(p, c->hy, c->grid_count, c->d_grid_total, &n_slab, c->stream) != hipSuccess) return MCRAT_HIP_EHIP;
+            if (d_slab.reserve((size_t)n_slab) != hipSuccess) return MCRAT_HIP_ENOMEM;
+            if (n_slab > 0 && launch_inject_slab_write(p, c->hy, c->grid_count, n_slab, d_start, d_start + M + 1, d_slab, c->stream) != hipSuccess) return MCRAT_HIP_EHIP;
+            if (launch_inject_pool(p, c->hy, c->ph, c->rank_stride, R, d_slab, n_slab, d_pi, g, c->stream) != hipSuccess ||
+                hipStreamSynchronize(c->stream) != hipSuccess) { c->last_error = "photon injection of the pool's lists failed"; return MCRAT_HIP_EHIP; }
         }
-        if (n_slab > 0 && launch_inject_slab_write(p, c->hy, c->grid_count, n_slab, d_start, d_start + M + 1, d_slab, c->stream) != hipSuccess) return done(MCRAT_HIP_EHIP);
-        if (launch_inject_pool(p, c->hy, c->ph, c->rank_stride, R, d_slab, n_slab, d_pi, (int)g, c->stream) != hipSuccess ||
-            hipStreamSynchronize(c->stream) != hipSuccess) { c->last_error = "photon injection of the pool's lists failed"; return done(MCRAT_HIP_EHIP); }
+        if (hipMemcpyAsync(pi.data(), d_pi, sizeof(PoolInject) * (size_t)R, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess) return MCRAT_HIP_EHIP;
     }
-    if (hipMemcpyAsync(pi.data(), d_pi, sizeof(PoolInject) * (size_t)R, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess) return done(MCRAT_HIP_EHIP);
-    (void)done(0);
     // every list that was injected is committed; a list that failed says so in its own status (its window stays empty) and the call returns
     // the first such code after all lists have been looked at
     int first_error = MCRAT_HIP_OK;
@@ -1720,8 +1726,7 @@ extern "C" int mcrat_hip_pool_inject_photons(mcrat_hip_ctx *c, double fps, mcrat
             q.status = MCRAT_HIP_EINVAL; q.num_photons = 0;
             if (!first_error) {
                 first_error = MCRAT_HIP_EINVAL;
-                c->last_error = e.error == 1 ? "photon injection: no weight puts the photon count between min_photons and max_photons"
-                                             : "photon injection: no photons (no cell of the frame touches the injection slab?)";
+                c->last_error = list_refusal_text(e.error == 1 ? INJECT_NO_WEIGHT : INJECT_NO_PHOTONS);
             }
             continue;
         }
@@ -1754,11 +1759,9 @@ static int grow_photons(mcrat_hip_ctx *c, int new_n)
     c->ph_buf = nullptr; c->ph_bytes = 0;                     // a fresh, zeroed allocation
     int rc = alloc_photons(c, new_n);
     if (rc) { if (c->ph_buf) (void)hipFree(c->ph_buf); c->ph_buf = old_buf; c->ph = old; return rc; }
-    const double *src[24] = {old.r0, old.r1, old.r2, old.p0, old.p1, old.p2, old.p3, old.c0, old.c1, old.c2, old.c3, old.s0, old.s1, old.s2, old.s3,
-                             old.num_scatt, old.weight, old.tau, old.tts, old.u0, old.u1, old.u2, old.ntau, old.tau_next};
-    double *dst[24] = {c->ph.r0, c->ph.r1, c->ph.r2, c->ph.p0, c->ph.p1, c->ph.p2, c->ph.p3, c->ph.c0, c->ph.c1, c->ph.c2, c->ph.c3, c->ph.s0, c->ph.s1,
-                       c->ph.s2, c->ph.s3, c->ph.num_scatt, c->ph.weight, c->ph.tau, c->ph.tts, c->ph.u0, c->ph.u1, c->ph.u2, c->ph.ntau, c->ph.tau_next};
-    for (int k = 0; k < 24; ++k) HIPCHK(c, hipMemcpyAsync(dst[k], src[k], sizeof(double) * (size_t)old_n, hipMemcpyDeviceToDevice, c->stream));
+#define MCRAT_X(name, K) HIPCHK(c, hipMemcpyAsync(c->ph.name, old.name, sizeof(double) * (size_t)old_n, hipMemcpyDeviceToDevice, c->stream));
+    MCRAT_DOUBLE_COLS(MCRAT_X)
+#undef MCRAT_X
     HIPCHK(c, hipMemcpyAsync(c->ph.idx, old.idx, sizeof(int) * (size_t)old_n, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->ph.flags, old.flags, (size_t)old_n, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->ph.type, old.type, (size_t)old_n, hipMemcpyDeviceToDevice, c->stream));
@@ -1766,6 +1769,31 @@ static int grow_photons(mcrat_hip_ctx *c, int new_n)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipFree(old_buf));
     if (c->ph_snap) { HIPCHK(c, hipFree(c->ph_snap)); c->ph_snap = nullptr; c->ph_snap_bytes = 0; }     // a snapshot of the smaller list
+    return MCRAT_HIP_OK;
+}
+
+// gsl_integration_qags (:1276) ran past the device's interval limit in `cells` cells (inject.hip, qags_planck): refused, and why
+static int emit_not_converged(mcrat_hip_ctx *c, unsigned cells)
+{
+    char text[192];
+    return c->last_error = emit_not_converged_text(text, sizeof text, cells), MCRAT_HIP_EREFUSED;
+}
+
+// The list's null slots in ascending order (addToPhotonList's null_ph_indexes, photons.c:181-189), in two halves because the host has to know
+// their number before it can give them room.  First the count per 256 slots into block_count[0 .. (n + 255) / 256), its total on its way to
+// *n_null: good once the caller has waited for the stream ...
+static int null_slots_count(mcrat_hip_ctx *c, unsigned *block_count, unsigned long long *n_null)
+{
+    HIPCHK(c, launch_null_count(c->ph, block_count, c->d_grid_total, c->stream));
+    HIPCHK(c, hipMemcpyAsync(n_null, c->d_grid_total, sizeof *n_null, hipMemcpyDeviceToHost, c->stream));
+    return MCRAT_HIP_OK;
+}
+// ... then the slots themselves into null_slots[0 .. n_null); block_start: nblk + 1 + grid_scan_scratch_ints(nblk) ints, nblk = (n + 255) / 256
+static int null_slots_write(mcrat_hip_ctx *c, const unsigned *block_count, unsigned long long n_null, int *block_start, int *null_slots)
+{
+    const long long nblk = (c->ph.n + 255) / 256;
+    HIPCHK(c, launch_exclusive_scan(block_count, nblk, block_start, block_start + nblk + 1, (long long)n_null, c->stream));
+    HIPCHK(c, launch_null_write(c->ph, block_start, null_slots, c->stream));
     return MCRAT_HIP_OK;
 }
 
@@ -1778,18 +1806,15 @@ extern "C" int mcrat_hip_emit_cyclosynch_pool(mcrat_hip_ctx *c, const mcrat_hip_
     int rc = flush_pending(c);
     if (rc) return rc;
     const int M = c->hy.M;
-    CsEmitParams p{};
-    p.dimensions = c->kc.dimensions; p.geometry = c->kc.geometry; p.b_field_calc = cs->b_field_calc; p.epsilon_b = cs->epsilon_b;
-    p.rmin = r_inj + (C_LIGHT * (cs->scatt_frame_number - cs->inj_frame_number) / fps - 0.5 * C_LIGHT / fps);      // calcCyclosynchRLimits :225-244
-    p.rmax = r_inj + (C_LIGHT * (cs->scatt_frame_number - cs->inj_frame_number) / fps + 0.5 * C_LIGHT / fps);
-    p.theta_min = theta_min; p.theta_max = theta_max;
+    const RadialRange shell = emit_shell_radii(r_inj, cs->scatt_frame_number, cs->inj_frame_number, fps);
+    CsEmitParams p = cs_emit_params(c, cs);
+    emit_into(p, Region{shell.rmin, shell.rmax, theta_min, theta_max, 0});
     RngKey key = c->key;
     key.seed = seed;
     const size_t need_counts = (size_t)std::max(M, (c->ph.n + 255) / 256 + 8);
     { int rc_ = ensure_counts(c, need_counts); if (rc_) return rc_; }
-    unsigned *d_flags = nullptr;
-    HIPCHK(c, hipMalloc((void **)&d_flags, 4 * sizeof(unsigned)));
-    auto fail = [&](int code) { (void)hipFree(d_flags); return code; };
+    DeviceTemp<unsigned> d_flags;
+    HIPCHK(c, d_flags.alloc(4));
     // :1244-1296: the weight loop on the device's totals
     const double max_photons = cs->rebin_e_perc * maximum_photons;
     double weight = ph_weight;
@@ -1797,66 +1822,55 @@ extern "C" int mcrat_hip_emit_cyclosynch_pool(mcrat_hip_ctx *c, const mcrat_hip_
     unsigned flags[4] = {0, 0, 0, 0}, cells_in_shell = 0;
     bool ok = false;
     for (unsigned long long attempt = 0; attempt <= 400 && !ok; ++attempt) {
-        if (hipMemsetAsync(d_flags, 0, 4 * sizeof(unsigned), c->stream) != hipSuccess) return fail(MCRAT_HIP_EHIP);
+        if (hipMemsetAsync(d_flags, 0, 4 * sizeof(unsigned), c->stream) != hipSuccess) return MCRAT_HIP_EHIP;
         if (launch_cs_emit_count(p, c->hy, c->hcol, weight, attempt, key, c->grid_count, c->d_grid_total, d_flags, c->stream) != hipSuccess ||
             hipMemcpyAsync(&total, c->d_grid_total, sizeof total, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
             hipMemcpyAsync(flags, d_flags, sizeof flags, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-            hipStreamSynchronize(c->stream) != hipSuccess) { c->last_error = "cyclo-synchrotron emission: count pass failed"; return fail(MCRAT_HIP_EHIP); }
+            hipStreamSynchronize(c->stream) != hipSuccess) { c->last_error = "cyclo-synchrotron emission: count pass failed"; return MCRAT_HIP_EHIP; }
         if (attempt == 0) cells_in_shell = flags[1];                                // (the kernel counts them on its first pass only)
         if (flags[0] != 0) {  // gsl_integration_qags (:1276) past its first rule AND past the device's bisection (inject.hip, qags_planck): not a result to go on with
             if (integrals_not_converged) *integrals_not_converged = (int)flags[0];
-            c->last_error = "cyclo-synchrotron emission: the photon-density integral of " + std::to_string(flags[0]) + " cell(s) did not converge within the device's interval limit";
-            return fail(MCRAT_HIP_EREFUSED);
+            return emit_not_converged(c, flags[0]);
         }
         const int min_photons = cells_in_shell ? 1 : 0;                             // no cell in the shell: nothing to emit (:1236-1239)
-        if ((double)total > max_photons) weight *= 10;
-        else if ((long long)total < min_photons) weight *= 0.5;
-        else ok = true;
+        ok = weight_search_step(total, min_photons, max_photons, &weight);
     }
-    if (!ok) { c->last_error = "cyclo-synchrotron emission: no weight gives between 1 and rebin_e_perc * maximum_photons photons"; return fail(MCRAT_HIP_EINVAL); }
+    if (!ok) { c->last_error = list_refusal_text(EMIT_NO_WEIGHT); return MCRAT_HIP_EINVAL; }
     const int n_emit = (int)total;
     if (num_emitted) *num_emitted = n_emit;
     if (ph_weight_adjusted) *ph_weight_adjusted = weight;
     if (integrals_not_converged) *integrals_not_converged = (int)flags[0];
-    if (n_emit == 0) return fail(MCRAT_HIP_OK);
+    if (n_emit == 0) return MCRAT_HIP_OK;
     // cell -> first pool photon (the counts live in grid_count[0..M)); keep them while the list may be re-allocated
     const size_t scan_ints = (size_t)M + 1 + grid_scan_scratch_ints(M);
-    int *d_start = nullptr;
-    if (hipMalloc((void **)&d_start, sizeof(int) * scan_ints) != hipSuccess) return fail(MCRAT_HIP_ENOMEM);
-    auto fail2 = [&](int code) { (void)hipFree(d_start); return fail(code); };
-    if (launch_exclusive_scan(c->grid_count, M, d_start, d_start + M + 1, (long long)total, c->stream) != hipSuccess) return fail2(MCRAT_HIP_EHIP);
+    DeviceTemp<int> d_start;
+    if (d_start.alloc(scan_ints) != hipSuccess) return MCRAT_HIP_ENOMEM;
+    if (launch_exclusive_scan(c->grid_count, M, d_start, d_start + M + 1, (long long)total, c->stream) != hipSuccess) return MCRAT_HIP_EHIP;
     // addToPhotonList (photons.c:108-208): the null slots, the list doubled first when it has none
     unsigned long long n_null = 0;
     auto count_nulls = [&]() -> int {
-        if (launch_null_count(c->ph, c->grid_count, c->d_grid_total, c->stream) != hipSuccess ||
-            hipMemcpyAsync(&n_null, c->d_grid_total, sizeof n_null, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-            hipStreamSynchronize(c->stream) != hipSuccess) return MCRAT_HIP_EHIP;
+        if (null_slots_count(c, c->grid_count, &n_null) || hipStreamSynchronize(c->stream) != hipSuccess) return MCRAT_HIP_EHIP;
         return MCRAT_HIP_OK;
     };
-    if ((rc = count_nulls())) return fail2(rc);
+    if ((rc = count_nulls())) return rc;
     if (n_null == 0) {                                                              // num_photons >= list_capacity && num_null_photons <= num (:112)
-        const long long cap = c->ph.n;
-        const long long new_cap = (cap * 2 > cap + n_emit) ? cap * 2 : cap * (n_emit / cap);
-        if (new_cap > 0x7fffffffLL) return fail2(MCRAT_HIP_EINVAL);
-        if ((rc = grow_photons(c, (int)new_cap))) return fail2(rc);
-        if ((rc = ensure_counts(c, (size_t)((c->ph.n + 255) / 256 + 8)))) return fail2(rc);
-        if ((rc = count_nulls())) return fail2(rc);
+        const long long new_cap = list_capacity_grown(c->ph.n, n_emit);
+        if (new_cap > 0x7fffffffLL) return MCRAT_HIP_EINVAL;
+        if ((rc = grow_photons(c, (int)new_cap))) return rc;
+        if ((rc = ensure_counts(c, (size_t)((c->ph.n + 255) / 256 + 8)))) return rc;
+        if ((rc = count_nulls())) return rc;
     }
-    if ((unsigned long long)n_emit > n_null) {
-        c->last_error = "cyclo-synchrotron emission: fewer null slots than photons to add (the reference exits with \"Adding to the photon list has failed\")";
-        return fail2(MCRAT_HIP_EINVAL);
-    }
+    if ((unsigned long long)n_emit > n_null) { c->last_error = list_refusal_text(EMIT_NO_NULL_SLOTS); return MCRAT_HIP_EINVAL; }
     const long long nblk = (c->ph.n + 255) / 256;
-    const size_t null_bytes = sizeof(int) * ((size_t)nblk + 1 + grid_scan_scratch_ints(nblk) + (size_t)n_null);
-    if ((rc = ensure_aos(c, null_bytes))) return fail2(rc);
-    int *blk_start = static_cast<int *>(c->aos_buf), *scratch = blk_start + nblk + 1, *null_slots = scratch + grid_scan_scratch_ints(nblk);
-    if (launch_exclusive_scan(c->grid_count, nblk, blk_start, scratch, (long long)n_null, c->stream) != hipSuccess ||
-        launch_null_write(c->ph, blk_start, null_slots, c->stream) != hipSuccess ||
+    const size_t start_ints = (size_t)nblk + 1 + grid_scan_scratch_ints(nblk);
+    if ((rc = ensure_aos(c, sizeof(int) * (start_ints + (size_t)n_null)))) return rc;
+    int *blk_start = static_cast<int *>(c->aos_buf), *null_slots = blk_start + start_ints;
+    if (null_slots_write(c, c->grid_count, n_null, blk_start, null_slots) ||
         launch_cs_emit_generate(p, c->hy, c->hcol, weight, key, d_start, n_emit, null_slots, c->ph, c->stream) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess) { c->last_error = "cyclo-synchrotron emission: generate pass failed"; return fail2(MCRAT_HIP_EHIP); }
+        hipStreamSynchronize(c->stream) != hipSuccess) { c->last_error = "cyclo-synchrotron emission: generate pass failed"; return MCRAT_HIP_EHIP; }
     c->frame_open = false;
     drop_graph(c);
-    return fail2(MCRAT_HIP_OK);
+    return MCRAT_HIP_OK;
 }
 
 extern "C" int mcrat_hip_set_photons_soa(mcrat_hip_ctx *c, const mcrat_hip_photon_soa *s)
@@ -1882,9 +1896,7 @@ extern "C" int mcrat_hip_snapshot_photons(mcrat_hip_ctx *c)
     if (!c) return MCRAT_HIP_EINVAL;
     if (!c->have_photons) return MCRAT_HIP_ESTATE;
     if (c->parent) { c->last_error = "snapshot the pool, not one of its views"; return MCRAT_HIP_ESTATE; }
-    int rc = MCRAT_HIP_OK;
     if (c->frame_open && c->n_ranks == 0) { HIPCHK(c, launch_flush(c->ph, c->d_state, c->step_blocks, c->stream)); }
-    (void)rc;
     if (c->ph_snap && c->ph_snap_bytes < c->ph_bytes) { HIPCHK(c, hipFree(c->ph_snap)); c->ph_snap = nullptr; }
     if (!c->ph_snap) { HIPCHK(c, hipMalloc(&c->ph_snap, c->ph_bytes)); c->ph_snap_bytes = c->ph_bytes; }
     HIPCHK(c, hipMemcpyAsync(c->ph_snap, c->ph_buf, c->ph_bytes, hipMemcpyDeviceToDevice, c->stream));
@@ -1924,28 +1936,11 @@ extern "C" int mcrat_hip_rebin_cyclosynch(mcrat_hip_ctx *c, const mcrat_hip_cycl
     std::vector<RebinRange> part((size_t)rblk);
     HIPCHK(c, hipMemcpyAsync(part.data(), c->aos_buf, sizeof(RebinRange) * (size_t)rblk, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    RebinRange q = part[0];
-    for (int k = 1; k < rblk; ++k) {
-        q.p0_min = std::fmin(q.p0_min, part[k].p0_min); q.p0_max = std::fmax(q.p0_max, part[k].p0_max);
-        q.theta_min = std::fmin(q.theta_min, part[k].theta_min); q.theta_max = std::fmax(q.theta_max, part[k].theta_max);
-        q.phi_min = std::fmin(q.phi_min, part[k].phi_min); q.phi_max = std::fmax(q.phi_max, part[k].phi_max);
-        q.valid += part[k].valid; q.synch += part[k].synch;
-    }
-    if (q.valid == 0) { c->last_error = "rebinning: no valid photons found for rebinning"; return MCRAT_HIP_EREFUSED; }
-    const double log_p0_min = (q.p0_min > 0 && q.p0_max > 0) ? std::log10(q.p0_min) : 0.0, log_p0_max = (q.p0_min > 0 && q.p0_max > 0) ? std::log10(q.p0_max) : 1.0;
+    const RebinRange q = rebin_range_merge(part.data(), rblk);
     // calculate_binning_params :324-347, allocate_histograms :351-391
-    RebinAxes ax{};
-    ax.three = three;
-    ax.num_bins = (int)(cs->rebin_e_perc * max_photons);
-    ax.num_bins_theta = (int)std::ceil((q.theta_max - q.theta_min) / (cs->rebin_ang * (M_PI / 180.0)));
-    ax.num_bins_phi = three ? (int)std::ceil((q.phi_max - q.phi_min) / cs->rebin_ang_phi) : 1;
-    const long long total_ll = (long long)ax.num_bins_theta * ax.num_bins * (three ? ax.num_bins_phi : 1);
-    if (total_ll > max_photons) { c->last_error = "rebinning would create more photons than max_photons"; return MCRAT_HIP_EREFUSED; }
-    if (ax.num_bins <= 0 || ax.num_bins_theta <= 0 || ax.num_bins_phi <= 0) { c->last_error = "rebinning: invalid histogram dimensions"; return MCRAT_HIP_EREFUSED; }
-    ax.total_bins = (int)total_ll;
-    ax.e_lo = log_p0_min; ax.e_hi = log_p0_max + (log_p0_max - log_p0_min) * 1e-6;
-    ax.t_lo = q.theta_min; ax.t_hi = q.theta_max + (q.theta_max - q.theta_min) * 1e-6;
-    ax.p_lo = q.phi_min; ax.p_hi = q.phi_max + (q.phi_max - q.phi_min) * 1e-6;
+    auto refuse = [&](ListRefusal why) { c->last_error = list_refusal_text(why); return MCRAT_HIP_EREFUSED; };
+    RebinAxes ax;
+    if (const ListRefusal why = rebin_axes(q, cs->rebin_e_perc, cs->rebin_ang, cs->rebin_ang_phi, max_photons, three, &ax)) return refuse(why);
     // scratch: bin of every slot, per-bin counts / cursors / starts, the member lists, the records, the null-slot list
     const int B = ax.total_bins;
     const long long nblk = (n + 255) / 256;
@@ -1973,41 +1968,34 @@ extern "C" int mcrat_hip_rebin_cyclosynch(mcrat_hip_ctx *c, const mcrat_hip_cycl
     HIPCHK(c, hipStreamSynchronize(c->stream));
     long long members_total = 0;
     for (int k = 0; k < B; ++k) members_total += h_cnt[(size_t)k];
-    if (h_cnt[(size_t)B + 1] != 0) { c->last_error = "rebinning: a photon maps to an invalid bin index (the reference exits)"; return MCRAT_HIP_EREFUSED; }
+    if (h_cnt[(size_t)B + 1] != 0) return refuse(REBIN_BIN_OUT_OF_RANGE);
     HIPCHK(c, launch_exclusive_scan(bin_count, B, bin_start, bin_start + B + 1, members_total, c->stream));
     HIPCHK(c, launch_rebin_fill(c->ph, bin_of, bin_start, cursor, members, c->stream));
     HIPCHK(c, launch_rebin_create(c->ph, ax, bin_start, members, recs, empty, c->stream));
     HIPCHK(c, launch_rebin_nullify(c->ph, c->stream));                                            // :573-581
     // addToPhotonList(rebin_ph, total_bins), photons.c:108-208
     unsigned long long n_null = 0;
-    HIPCHK(c, launch_null_count(c->ph, null_cnt, c->d_grid_total, c->stream));
     unsigned h_empty[2] = {0, 0};
-    HIPCHK(c, hipMemcpyAsync(&n_null, c->d_grid_total, sizeof n_null, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = null_slots_count(c, null_cnt, &n_null))) return rc;
     HIPCHK(c, hipMemcpyAsync(h_empty, empty, sizeof h_empty, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if ((unsigned long long)B > n_null) {
-        c->last_error = "rebinning: fewer null slots than rebinned photons (the reference exits with \"Adding to the photon list has failed\")";
-        return MCRAT_HIP_EREFUSED;
-    }
-    HIPCHK(c, launch_exclusive_scan(null_cnt, nblk, null_start, null_start + nblk + 1, (long long)n_null, c->stream));
-    HIPCHK(c, launch_null_write(c->ph, null_start, null_slots, c->stream));
+    if ((unsigned long long)B > n_null) return refuse(REBIN_NO_NULL_SLOTS);
+    if ((rc = null_slots_write(c, null_cnt, n_null, null_start, null_slots))) return rc;
     HIPCHK(c, launch_rebin_place(c->ph, recs, B, null_slots, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    const int null_count = (int)h_empty[0];
-    if ((long long)n - (long long)n_null + (B - null_count) < B) {                                // :676-681
-        c->last_error = "rebinning: fewer photons in the list than bins after the rebinning";
-        return MCRAT_HIP_EREFUSED;
-    }
-    if (empty_bins_out) *empty_bins_out = null_count;
-    if (scatt_cyclosynch_num_ph) *scatt_cyclosynch_num_ph = B - null_count;                       // :689-690
-    if (num_cyclosynch_ph_emit) *num_cyclosynch_ph_emit = B + q.synch - null_count;
+    RebinCounts after;
+    if (const ListRefusal why = rebin_after(n, (long long)n_null, B, (int)h_empty[0], q.synch, &after)) return refuse(why);
+    if (empty_bins_out) *empty_bins_out = after.empty_bins;
+    if (scatt_cyclosynch_num_ph) *scatt_cyclosynch_num_ph = after.scatt_cyclosynch_num_ph;
+    if (num_cyclosynch_ph_emit) *num_cyclosynch_ph_emit = after.num_cyclosynch_ph_emit;
     drop_graph(c);
     return MCRAT_HIP_OK;
 }
 
 // rebinCyclosynchCompPhotons (mc_cyclosynch.c:610-710) for the lists `ids` of a rank pool at once: two launches (one workgroup per list) and two
 // host round trips for all of them, against a dozen launches and four round trips per list through mcrat_hip_rebin_cyclosynch on the views.
-// The host's part in between -- the histograms' axes from the ranges (:324-391) -- is the same code, so a list comes out bit for bit the same.
+// The host's part in between -- the histograms' axes from the ranges (:324-391) -- is the same function (rebin_axes, list_plan.hpp), so a list comes
+// out bit for bit the same.
 // rc[j]: MCRAT_HIP_OK, or MCRAT_HIP_EREFUSED where the reference would refuse or exit (the view's last_error says why); empty / emit / scatt as
 // mcrat_hip_rebin_cyclosynch returns them.  Returns the first hard error.
 struct PoolRebinResult { int rc, empty_bins, num_cyclosynch_ph_emit, scatt_cyclosynch_num_ph; };
@@ -2037,32 +2025,16 @@ static int pool_rebin_lists(mcrat_hip_ctx *c, const mcrat_hip_cyclosynch *cs, in
     HIPCHK(c, hipMemcpyAsync(range.data(), b + o_range, sizeof(RebinRange) * (size_t)L, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     // the host's part, list by list: calculate_binning_params :324-347, allocate_histograms :351-391
+    auto refuse = [&](int j, ListRefusal why) { c->views[ids[(size_t)j]]->last_error = list_refusal_text(why); res[(size_t)j].rc = MCRAT_HIP_EREFUSED; };
     std::vector<RebinPoolList> go;
     std::vector<int> go_j;
     size_t scratch = 0;
     for (int j = 0; j < L; ++j) {
-        mcrat_hip_ctx *v = c->views[ids[(size_t)j]];
-        const RebinRange &q = range[(size_t)j];
-        auto refuse = [&](const char *why) { v->last_error = why; res[(size_t)j].rc = MCRAT_HIP_EREFUSED; };
-        if (q.valid == 0) { refuse("rebinning: no valid photons found for rebinning"); continue; }
-        const double log_p0_min = (q.p0_min > 0 && q.p0_max > 0) ? std::log10(q.p0_min) : 0.0, log_p0_max = (q.p0_min > 0 && q.p0_max > 0) ? std::log10(q.p0_max) : 1.0;
-        RebinAxes ax{};
-        ax.three = three;
-        ax.num_bins = (int)(cs->rebin_e_perc * max_photons);
-        ax.num_bins_theta = (int)std::ceil((q.theta_max - q.theta_min) / (cs->rebin_ang * (M_PI / 180.0)));
-        ax.num_bins_phi = three ? (int)std::ceil((q.phi_max - q.phi_min) / cs->rebin_ang_phi) : 1;
-        const long long total_ll = (long long)ax.num_bins_theta * ax.num_bins * (three ? ax.num_bins_phi : 1);
-        if (total_ll > max_photons) { refuse("rebinning would create more photons than max_photons"); continue; }
-        if (ax.num_bins <= 0 || ax.num_bins_theta <= 0 || ax.num_bins_phi <= 0) { refuse("rebinning: invalid histogram dimensions"); continue; }
-        ax.total_bins = (int)total_ll;
-        ax.e_lo = log_p0_min; ax.e_hi = log_p0_max + (log_p0_max - log_p0_min) * 1e-6;
-        ax.t_lo = q.theta_min; ax.t_hi = q.theta_max + (q.theta_max - q.theta_min) * 1e-6;
-        ax.p_lo = q.phi_min; ax.p_hi = q.phi_max + (q.phi_max - q.phi_min) * 1e-6;
         RebinPoolList l = h[(size_t)j];
-        l.ax = ax;
+        if (const ListRefusal why = rebin_axes(range[(size_t)j], cs->rebin_e_perc, cs->rebin_ang, cs->rebin_ang_phi, max_photons, three, &l.ax)) { refuse(j, why); continue; }
         l.scratch = scratch;
         l.status = -1;
-        scratch += rebin_pool_scratch_bytes(l.n, ax.total_bins);
+        scratch += rebin_pool_scratch_bytes(l.n, l.ax.total_bins);
         go.push_back(l);
         go_j.push_back(j);
     }
@@ -2080,23 +2052,15 @@ static int pool_rebin_lists(mcrat_hip_ctx *c, const mcrat_hip_cyclosynch *cs, in
         const int j = go_j[(size_t)g];
         mcrat_hip_ctx *v = c->views[ids[(size_t)j]];
         const RebinPoolList &l = go[(size_t)g];
-        const int B = l.ax.total_bins;
         drop_graph(v);
-        if (l.status == 1) { v->last_error = "rebinning: a photon maps to an invalid bin index (the reference exits)"; res[(size_t)j].rc = MCRAT_HIP_EREFUSED; continue; }
-        if (l.status == 2) {
-            v->last_error = "rebinning: fewer null slots than rebinned photons (the reference exits with \"Adding to the photon list has failed\")";
-            res[(size_t)j].rc = MCRAT_HIP_EREFUSED;
-            continue;
-        }
-        if (l.status != 0) { c->last_error = "rebinning: the pool kernel left a list without a status"; return MCRAT_HIP_EHIP; }
-        if ((long long)l.n - (long long)l.n_null + (B - l.empty_bins) < B) {                          // :676-681
-            v->last_error = "rebinning: fewer photons in the list than bins after the rebinning";
-            res[(size_t)j].rc = MCRAT_HIP_EREFUSED;
-            continue;
-        }
-        res[(size_t)j].empty_bins = l.empty_bins;
-        res[(size_t)j].scatt_cyclosynch_num_ph = B - l.empty_bins;                                    // :689-690
-        res[(size_t)j].num_cyclosynch_ph_emit = B + range[(size_t)j].synch - l.empty_bins;
+        if (l.status != 0 && l.status != 1 && l.status != 2) { c->last_error = "rebinning: the pool kernel left a list without a status"; return MCRAT_HIP_EHIP; }
+        RebinCounts after{0, 0, 0};
+        const ListRefusal why = l.status == 1 ? REBIN_BIN_OUT_OF_RANGE : l.status == 2 ? REBIN_NO_NULL_SLOTS
+                                : rebin_after(l.n, l.n_null, l.ax.total_bins, l.empty_bins, range[(size_t)j].synch, &after);
+        if (why) { refuse(j, why); continue; }
+        res[(size_t)j].empty_bins = after.empty_bins;
+        res[(size_t)j].scatt_cyclosynch_num_ph = after.scatt_cyclosynch_num_ph;
+        res[(size_t)j].num_cyclosynch_ph_emit = after.num_cyclosynch_ph_emit;
     }
     return MCRAT_HIP_OK;
 }
@@ -3652,6 +3616,32 @@ extern "C" int mcrat_hip_propagate_frame_mode(mcrat_hip_ctx *c, double *time_now
     return MCRAT_HIP_OK;
 }
 
+// ---- the hook's state of a list (CsFrame, launch.hpp) as the host keeps it through a scatter frame: what the one-list frame and the pool's frame share
+// at the start of a frame; carried: main()'s scatt_cyclosynch_num_ph of the frame before (mcrat.c:873,921)
+static CsFrame cs_frame_begin(int max_photons, int carried) { CsFrame f{}; f.max_photons = max_photons; f.last_iteration = ~0ull; f.scatt_num = carried; return f; }
+// a parked list goes on: the loop's `done` gets back what the pass left (the hook saved it).  The host's copies here; send_done and a copy of the
+// CsFrame take them to the device.
+static void cs_frame_release(CsFrame &f, LoopState *h_state) { f.halt = 0; h_state->done = f.saved_done; }
+static hipError_t send_done(const LoopState *h_state, LoopState *d_state, hipStream_t stream)
+{
+    return hipMemcpyAsync(reinterpret_cast<char *>(d_state) + offsetof(LoopState, done), &h_state->done, sizeof(int), hipMemcpyHostToDevice, stream);
+}
+// the list was rebinned inside the loop (:797-808): the rebinning's two counters replace the frame's
+static void cs_frame_rebinned(CsFrame &f, mcrat_hip_cyclosynch_counts &cnt, int &emit_base, int num_cyclosynch_ph_emit, int scatt_cyclosynch_num_ph)
+{
+    cnt.rebins += 1;
+    emit_base = num_cyclosynch_ph_emit; f.emitted = 0;       // num_cyclosynch_ph_emit = emit_base + replacements since (the rebinning overwrites it)
+    f.scatt_num = scatt_cyclosynch_num_ph;
+}
+// the loop is over: the frame's counters from the hook's state
+static void cs_frame_close(const CsFrame &f, int emit_base, mcrat_hip_cyclosynch_counts &cnt)
+{
+    cnt.num_cyclosynch_ph_emit = emit_base + f.emitted; cnt.scatt_cyclosynch_num_ph = f.scatt_num; cnt.n_comptonized = f.n_comptonized;
+}
+// the end of the frame, mcrat.c:853-878: rebin a list that holds more comptonised photons than max_photons, then absorb if anything was emitted
+static bool cs_end_rebin_due(int emit_pool, const mcrat_hip_cyclosynch_counts &cnt, int max_photons) { return emit_pool && cnt.scatt_cyclosynch_num_ph > max_photons; }
+static bool cs_end_absorb_due(int emit_pool, const mcrat_hip_cyclosynch_counts &cnt) { return emit_pool && cnt.num_cyclosynch_ph_emit > 0; }
+
 // The scatter-frame body of main() with CYCLOSYNCHROTRON_SWITCH on (mcrat.c:706-878, between getHydroData and saveCheckpoint): pool
 // emission, the loop with the replacement of scattered pool photons (:786-795) and the rebinning trigger (:797-808), the rebinning
 // and absorption at the end of the frame (:853-878).  The hook needs the list current after every pass, so a pass here is
@@ -3677,18 +3667,13 @@ extern "C" int mcrat_hip_scatter_frame_cyclosynch(mcrat_hip_ctx *c, const mcrat_
         cnt->integrals_not_converged = bad;
     }
     if ((rc = mcrat_hip_begin_frame(c, seed, *time_now, remaining_time))) return rc;
-    CsEmitParams p{};
-    p.dimensions = c->kc.dimensions; p.geometry = c->kc.geometry; p.b_field_calc = cs->b_field_calc; p.epsilon_b = cs->epsilon_b;
+    const CsEmitParams p = cs_emit_params(c, cs);
     if (!c->d_cs_hook) HIPCHK(c, hipMalloc((void **)&c->d_cs_hook, sizeof(CsFrame)));
     CsFrame *d_cf = static_cast<CsFrame *>(c->d_cs_hook);
-    CsFrame cf{};
-    cf.max_photons = max_photons;
-    cf.last_iteration = ~0ull;
-    cf.scatt_num = carried;
+    CsFrame cf = cs_frame_begin(max_photons, carried);
     HIPCHK(c, hipMemcpyAsync(d_cf, &cf, sizeof cf, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));                                                  // cf is on the stack
-    const int emit_pool_count = cnt->num_cyclosynch_ph_emit;
-    int emit_base = emit_pool_count;               // num_cyclosynch_ph_emit = emit_base + replacements since (the rebinning overwrites it)
+    int emit_base = cnt->num_cyclosynch_ph_emit;
     const long long per_sync = 32;                 // passes queued per read-back; a parked loop makes the rest of a batch no-ops
     while (!c->h_state->done && (max_iterations <= 0 || c->h_state->iterations < max_iterations)) {   // :761-851
         long long batch = per_sync;
@@ -3709,11 +3694,9 @@ extern "C" int mcrat_hip_scatter_frame_cyclosynch(mcrat_hip_ctx *c, const mcrat_
         HIPCHK(c, hipStreamSynchronize(c->stream));
         while (cf.halt) {                          // the loop is parked: do what the hook asked for, then let it go on
             const int why = cf.halt;
-            cf.halt = 0;
-            c->h_state->done = cf.saved_done;
-            HIPCHK(c, hipMemcpyAsync(reinterpret_cast<char *>(c->d_state) + offsetof(LoopState, done), &cf.saved_done, sizeof(int), hipMemcpyHostToDevice,
-                                     c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));          // cf lives on the stack and changes below: the copy must have read it
+            cs_frame_release(cf, c->h_state);
+            HIPCHK(c, send_done(c->h_state, c->d_state, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
             if (why == CS_HALT_GROW) {                                                            // photons.c:112-121: the list doubles
                 if (c->ph.n > 0x3fffffff) { c->last_error = "photon list too long to double"; return MCRAT_HIP_ENOMEM; }
                 HIPCHK(c, hipMemcpyAsync(d_cf, &cf, sizeof cf, hipMemcpyHostToDevice, c->stream));
@@ -3727,35 +3710,25 @@ extern "C" int mcrat_hip_scatter_frame_cyclosynch(mcrat_hip_ctx *c, const mcrat_
             } else {                                                                              // :797-808
                 int empty = 0, emit_total = emit_base + cf.emitted, scatt = cf.scatt_num;
                 rc = mcrat_hip_rebin_cyclosynch(c, cs, max_photons, &empty, &emit_total, &scatt);
-                if (rc == MCRAT_HIP_OK) {
-                    cnt->rebins += 1;
-                    emit_base = emit_total;
-                    cf.emitted = 0;
-                    cf.scatt_num = scatt;
-                } else if (rc != MCRAT_HIP_EREFUSED) {
-                    return rc;                     // EREFUSED: one of the reference's refusals, the list is as it was
-                }
+                if (rc == MCRAT_HIP_OK) cs_frame_rebinned(cf, *cnt, emit_base, emit_total, scatt);
+                else if (rc != MCRAT_HIP_EREFUSED) return rc;      // EREFUSED: one of the reference's refusals, the list is as it was
                 HIPCHK(c, hipMemcpyAsync(d_cf, &cf, sizeof cf, hipMemcpyHostToDevice, c->stream));
                 HIPCHK(c, hipStreamSynchronize(c->stream));
             }
         }
     }
-    cnt->num_cyclosynch_ph_emit = emit_base + cf.emitted;
-    cnt->scatt_cyclosynch_num_ph = cf.scatt_num;
-    cnt->n_comptonized = cf.n_comptonized;
+    cs_frame_close(cf, emit_base, *cnt);
     c->pending_applied = false;
-    if (emit_pool) {                                                                              // :853-878
-        if (cnt->scatt_cyclosynch_num_ph > max_photons) {
-            int empty = 0;
-            rc = mcrat_hip_rebin_cyclosynch(c, cs, max_photons, &empty, &cnt->num_cyclosynch_ph_emit, &cnt->scatt_cyclosynch_num_ph);
-            if (rc == MCRAT_HIP_OK) cnt->rebins += 1;
-            else if (rc != MCRAT_HIP_EREFUSED) return rc;
-        }
-        if (cnt->num_cyclosynch_ph_emit > 0) {
-            double w = 0;
-            if ((rc = mcrat_hip_absorb_cyclosynch(c, cs, &cnt->frame_abs_cnt, &cnt->scatt_cyclosynch_num_ph, &w))) return rc;
-            cnt->n_comptonized -= w;
-        }
+    if (cs_end_rebin_due(emit_pool, *cnt, max_photons)) {                                         // :853-878
+        int empty = 0;
+        rc = mcrat_hip_rebin_cyclosynch(c, cs, max_photons, &empty, &cnt->num_cyclosynch_ph_emit, &cnt->scatt_cyclosynch_num_ph);
+        if (rc == MCRAT_HIP_OK) cnt->rebins += 1;
+        else if (rc != MCRAT_HIP_EREFUSED) return rc;
+    }
+    if (cs_end_absorb_due(emit_pool, *cnt)) {
+        double w = 0;
+        if ((rc = mcrat_hip_absorb_cyclosynch(c, cs, &cnt->frame_abs_cnt, &cnt->scatt_cyclosynch_num_ph, &w))) return rc;
+        cnt->n_comptonized -= w;
     }
     HIPCHK(c, hipMemcpyAsync(c->h_state, c->d_state, sizeof(LoopState), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3764,16 +3737,39 @@ extern "C" int mcrat_hip_scatter_frame_cyclosynch(mcrat_hip_ctx *c, const mcrat_
     return MCRAT_HIP_OK;
 }
 
+// One call of mcrat_hip_pool_scatter_frames_cyclosynch: its arguments, what it keeps per list, and what its steps hand on.
+struct PoolCsFrames {
+    mcrat_hip_ctx *c;
+    const mcrat_hip_cyclosynch *cs;
+    int max_photons, R;
+    double fps;
+    const mcrat_hip_pool_cs_list *lists;
+    mcrat_hip_frame_stats *stats;                // may be null
+    mcrat_hip_cyclosynch_counts *counts;
+    bool hook_kernel;                            // MCRAT_HIP_CS_HOOK_KERNEL=1: the hook as a kernel between two launches of the loop (the first form, kept for the A/B)
+    // per list: what mcrat_hip_pool_begin_frames takes; cs with the list's own frame numbers; the counter main() carries from the previous frame
+    // (mcrat.c:873,921); num_cyclosynch_ph_emit = emit_base + replacements since (the rebinning overwrites it)
+    std::vector<int> open, carried, emit_base;
+    std::vector<uint64_t> seeds;
+    std::vector<double> t_now, t_rem;
+    std::vector<mcrat_hip_cyclosynch> csr;
+    std::vector<CsFrame> cf;                     // the hooks' state, the host's copy
+    CsFrame *d_cf = nullptr;                     // ... and the device's (the context's d_cs_hook)
+    CsEmitParams p;                              // what the hook is given
+    bool emits(int r) const { return open[(size_t)r] && lists[r].emit_pool; }
+};
+
 // photonEmitCyclosynch (mc_cyclosynch.c:1219-1460, inject_single_switch = 0) for the lists of a rank pool that ask for it: the emission
 // shell of each group of lists that share one (same radii and angles) is found and integrated once, then one workgroup per list runs the
 // list's weight loop and places its photons (inject.hip).  A list with more photons than that kernel's tables hold takes the one-list
 // path (mcrat_hip_emit_cyclosynch_pool on its view); both give the same photons.
-static int pool_emit_cyclosynch(mcrat_hip_ctx *c, const mcrat_hip_cyclosynch *cs, const std::vector<mcrat_hip_cyclosynch> &csr, int max_photons, double fps,
-                                const mcrat_hip_pool_cs_list *lists, mcrat_hip_cyclosynch_counts *counts, std::vector<int> &emit_base)
+static int pool_emit_cyclosynch(PoolCsFrames &F)
 {
-    const int R = c->n_ranks, M = c->hy.M;
-    struct Shell { double rmin, rmax, tmin, tmax; };
-    std::vector<Shell> shells;
+    mcrat_hip_ctx *c = F.c;
+    const mcrat_hip_pool_cs_list *lists = F.lists;
+    const int R = F.R, M = c->hy.M;
+    std::vector<Region> shells((size_t)R);                  // the lists grouped by their shell
+    int n_shells = 0;
     std::vector<CsPoolEmit> pe((size_t)R);
     bool any = false;
     int rc;
@@ -3784,89 +3780,66 @@ static int pool_emit_cyclosynch(mcrat_hip_ctx *c, const mcrat_hip_cyclosynch *cs
         if (!(lists[r].ph_weight_suggest > 0)) return MCRAT_HIP_EINVAL;
         mcrat_hip_ctx *v = c->views[r];
         if ((rc = flush_pending(v))) return rc;
-        const mcrat_hip_cyclosynch &q = csr[(size_t)r];
-        Shell sh;
-        sh.rmin = lists[r].r_inj + (C_LIGHT * (q.scatt_frame_number - q.inj_frame_number) / fps - 0.5 * C_LIGHT / fps);    // calcCyclosynchRLimits :225-244
-        sh.rmax = lists[r].r_inj + (C_LIGHT * (q.scatt_frame_number - q.inj_frame_number) / fps + 0.5 * C_LIGHT / fps);
-        sh.tmin = lists[r].theta_min; sh.tmax = lists[r].theta_max;
-        int g = -1;
-        for (size_t k = 0; k < shells.size(); ++k)
-            if (shells[k].rmin == sh.rmin && shells[k].rmax == sh.rmax && shells[k].tmin == sh.tmin && shells[k].tmax == sh.tmax) { g = (int)k; break; }
-        if (g < 0) { g = (int)shells.size(); shells.push_back(sh); }
+        const RadialRange sh = emit_shell_radii(lists[r].r_inj, F.csr[(size_t)r].scatt_frame_number, F.csr[(size_t)r].inj_frame_number, F.fps);
         CsPoolEmit &e = pe[(size_t)r];
-        e.open = 1; e.group = g; e.seed = lists[r].seed; e.weight_in = lists[r].ph_weight_suggest; e.max_photons = cs->rebin_e_perc * max_photons;
+        e.open = 1; e.group = region_group(shells.data(), &n_shells, Region{sh.rmin, sh.rmax, lists[r].theta_min, lists[r].theta_max, 0});
+        e.seed = lists[r].seed; e.weight_in = lists[r].ph_weight_suggest; e.max_photons = F.cs->rebin_e_perc * F.max_photons;
         c->h_desc[r].len = v->ph.n; c->h_desc[r].stream = v->key.stream; c->h_desc[r].seed = lists[r].seed;
         any = true;
     }
     if (!any) return MCRAT_HIP_OK;
     if ((rc = ensure_counts(c, (size_t)M + 8))) return rc;
-    const size_t scan_ints = (size_t)M + 1 + grid_scan_scratch_ints(M);
-    int *d_start = nullptr;
-    CsPoolEmit *d_pe = nullptr;
-    CsShellCell *d_shell = nullptr;
-    unsigned *d_bad = nullptr;
-    size_t shell_cap = 0;
-    auto done = [&](int code) { (void)hipFree(d_start); (void)hipFree(d_pe); (void)hipFree(d_shell); (void)hipFree(d_bad); return code; };
-    if (hipMalloc((void **)&d_start, sizeof(int) * scan_ints) != hipSuccess || hipMalloc((void **)&d_pe, sizeof(CsPoolEmit) * (size_t)R) != hipSuccess ||
-        hipMalloc((void **)&d_bad, sizeof(unsigned)) != hipSuccess) return done(MCRAT_HIP_ENOMEM);
-    if (hipMemcpyAsync(d_pe, pe.data(), sizeof(CsPoolEmit) * (size_t)R, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-        hipMemcpyAsync(c->d_desc, c->h_desc, sizeof(RankDesc) * (size_t)R, hipMemcpyHostToDevice, c->stream) != hipSuccess) return done(MCRAT_HIP_EHIP);
-    CsEmitParams p{};
-    p.dimensions = c->kc.dimensions; p.geometry = c->kc.geometry; p.b_field_calc = cs->b_field_calc; p.epsilon_b = cs->epsilon_b;
-    std::vector<unsigned> bad(shells.size(), 0);
-    for (size_t g = 0; g < shells.size(); ++g) {
-        p.rmin = shells[g].rmin; p.rmax = shells[g].rmax; p.theta_min = shells[g].tmin; p.theta_max = shells[g].tmax;
-        int n_shell = 0;
-        if (launch_cs_shell_flag(p, c->hy, c->grid_count, c->d_grid_total, &n_shell, c->stream) != hipSuccess) return done(MCRAT_HIP_EHIP);
-        if ((size_t)n_shell > shell_cap) {
-            (void)hipFree(d_shell); d_shell = nullptr;
-            if (hipMalloc((void **)&d_shell, sizeof(CsShellCell) * (size_t)n_shell) != hipSuccess) return done(MCRAT_HIP_ENOMEM);
-            shell_cap = (size_t)n_shell;
+    std::vector<unsigned> bad((size_t)n_shells, 0);
+    {                                                       // (the temporaries go before the lists are looked at: a list may take the one-list path below)
+        const size_t scan_ints = (size_t)M + 1 + grid_scan_scratch_ints(M);
+        DeviceTemp<int> d_start;
+        DeviceTemp<CsPoolEmit> d_pe;
+        DeviceTemp<CsShellCell> d_shell;
+        DeviceTemp<unsigned> d_bad;
+        if (d_start.alloc(scan_ints) != hipSuccess || d_pe.alloc((size_t)R) != hipSuccess || d_bad.alloc(1) != hipSuccess) return MCRAT_HIP_ENOMEM;
+        if (hipMemcpyAsync(d_pe, pe.data(), sizeof(CsPoolEmit) * (size_t)R, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+            hipMemcpyAsync(c->d_desc, c->h_desc, sizeof(RankDesc) * (size_t)R, hipMemcpyHostToDevice, c->stream) != hipSuccess) return MCRAT_HIP_EHIP;
+        CsEmitParams p = cs_emit_params(c, F.cs);
+        for (int g = 0; g < n_shells; ++g) {
+            emit_into(p, shells[(size_t)g]);
+            int n_shell = 0;
+            if (launch_cs_shell_flag(p, c->hy, c->grid_count, c->d_grid_total, &n_shell, c->stream) != hipSuccess) return MCRAT_HIP_EHIP;
+            if (d_shell.reserve((size_t)n_shell) != hipSuccess) return MCRAT_HIP_ENOMEM;
+            if (n_shell > 0 && launch_cs_shell_write(p, c->hy, c->hcol, c->grid_count, n_shell, d_start, d_start + M + 1, d_shell, d_bad, c->stream) != hipSuccess)
+                return MCRAT_HIP_EHIP;
+            if (n_shell == 0 && hipMemsetAsync(d_bad, 0, sizeof(unsigned), c->stream) != hipSuccess) return MCRAT_HIP_EHIP;
+            if (launch_cs_emit_pool(p, c->hy, c->hcol, c->ph, c->rank_stride, R, c->d_desc, d_shell, n_shell, d_pe, g, c->stream) != hipSuccess ||
+                hipMemcpyAsync(&bad[g], d_bad, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+                hipStreamSynchronize(c->stream) != hipSuccess) { c->last_error = "cyclo-synchrotron emission of the pool's lists failed"; return MCRAT_HIP_EHIP; }
         }
-        if (n_shell > 0 && launch_cs_shell_write(p, c->hy, c->hcol, c->grid_count, n_shell, d_start, d_start + M + 1, d_shell, d_bad, c->stream) != hipSuccess)
-            return done(MCRAT_HIP_EHIP);
-        if (n_shell == 0 && hipMemsetAsync(d_bad, 0, sizeof(unsigned), c->stream) != hipSuccess) return done(MCRAT_HIP_EHIP);
-        if (launch_cs_emit_pool(p, c->hy, c->hcol, c->ph, c->rank_stride, R, c->d_desc, d_shell, n_shell, d_pe, (int)g, c->stream) != hipSuccess ||
-            hipMemcpyAsync(&bad[g], d_bad, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-            hipStreamSynchronize(c->stream) != hipSuccess) { c->last_error = "cyclo-synchrotron emission of the pool's lists failed"; return done(MCRAT_HIP_EHIP); }
+        if (hipMemcpyAsync(pe.data(), d_pe, sizeof(CsPoolEmit) * (size_t)R, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+            hipMemcpyAsync(c->h_desc, c->d_desc, sizeof(RankDesc) * (size_t)R, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess) return MCRAT_HIP_EHIP;
     }
-    if (hipMemcpyAsync(pe.data(), d_pe, sizeof(CsPoolEmit) * (size_t)R, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipMemcpyAsync(c->h_desc, c->d_desc, sizeof(RankDesc) * (size_t)R, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess) return done(MCRAT_HIP_EHIP);
-    (void)done(0);
     for (int r = 0; r < R; ++r) {
         const CsPoolEmit &e = pe[(size_t)r];
         if (!e.open) continue;
         mcrat_hip_ctx *v = c->views[r];
         int n = e.n_emit, nbad = (int)bad[(size_t)e.group];
         double w = e.weight_out;
-        if (nbad > 0) {       // (as mcrat_hip_emit_cyclosynch_pool: inject.hip, qags_planck ran out of intervals)
-            c->last_error = "cyclo-synchrotron emission: the photon-density integral of " + std::to_string(nbad) + " cell(s) did not converge within the device's interval limit";
-            return MCRAT_HIP_EREFUSED;
-        }
+        if (nbad > 0) return emit_not_converged(c, (unsigned)nbad);       // (as mcrat_hip_emit_cyclosynch_pool)
         switch (e.error) {
         case 0:
             v->ph.n = c->h_desc[r].len;                                                           // the list may have grown inside its window
             if (n > 0) { v->frame_open = false; drop_graph(v); }
             break;
         case 4:                                                                                   // more photons than the kernel's tables hold
-            if ((rc = mcrat_hip_emit_cyclosynch_pool(v, &csr[(size_t)r], lists[r].r_inj, lists[r].ph_weight_suggest, max_photons, lists[r].theta_min,
-                                                     lists[r].theta_max, fps, lists[r].seed, &n, &w, &nbad))) { c->last_error = v->last_error; return rc; }
+            if ((rc = mcrat_hip_emit_cyclosynch_pool(v, &F.csr[(size_t)r], lists[r].r_inj, lists[r].ph_weight_suggest, F.max_photons, lists[r].theta_min,
+                                                     lists[r].theta_max, F.fps, lists[r].seed, &n, &w, &nbad))) { c->last_error = v->last_error; return rc; }
             break;
-        case 1:
-            c->last_error = "cyclo-synchrotron emission: no weight gives between 1 and rebin_e_perc * maximum_photons photons";
-            return MCRAT_HIP_EINVAL;
-        case 2:
-            c->last_error = "cyclo-synchrotron emission: fewer null slots than photons to add (the reference exits with \"Adding to the photon list has failed\")";
-            return MCRAT_HIP_EINVAL;
-        default:
-            c->last_error = "the list is longer than the pool's slots per rank (mcrat_hip_pool_create)";
-            return MCRAT_HIP_ENOMEM;
+        case 1: c->last_error = list_refusal_text(EMIT_NO_WEIGHT); return MCRAT_HIP_EINVAL;
+        case 2: c->last_error = list_refusal_text(EMIT_NO_NULL_SLOTS); return MCRAT_HIP_EINVAL;
+        default: c->last_error = "the list is longer than the pool's slots per rank (mcrat_hip_pool_create)"; return MCRAT_HIP_ENOMEM;
         }
-        counts[r].num_cyclosynch_ph_emit = n;
-        counts[r].pool_weight = w;
-        counts[r].integrals_not_converged = nbad;
-        emit_base[(size_t)r] = n;
+        F.counts[r].num_cyclosynch_ph_emit = n;
+        F.counts[r].pool_weight = w;
+        F.counts[r].integrals_not_converged = nbad;
+        F.emit_base[(size_t)r] = n;
     }
     return MCRAT_HIP_OK;
 }
@@ -3875,8 +3848,7 @@ static int pool_emit_cyclosynch(mcrat_hip_ctx *c, const mcrat_hip_cyclosynch *cs
 // the equality test -- list by list through the views
 static int pool_rebin(mcrat_hip_ctx *c, const mcrat_hip_cyclosynch *cs, int max_photons, const std::vector<int> &ids, std::vector<PoolRebinResult> &res)
 {
-    const char *e = getenv("MCRAT_HIP_POOL_REBIN_EACH");
-    if (!(e && atoi(e) != 0)) return pool_rebin_lists(c, cs, max_photons, ids, res);
+    if (!env_flag("MCRAT_HIP_POOL_REBIN_EACH")) return pool_rebin_lists(c, cs, max_photons, ids, res);
     res.assign(ids.size(), PoolRebinResult{MCRAT_HIP_OK, 0, 0, 0});
     for (size_t j = 0; j < ids.size(); ++j) {
         mcrat_hip_ctx *v = c->views[ids[j]];
@@ -3887,13 +3859,191 @@ static int pool_rebin(mcrat_hip_ctx *c, const mcrat_hip_cyclosynch *cs, int max_
     return MCRAT_HIP_OK;
 }
 
+// ---- the steps of mcrat_hip_pool_scatter_frames_cyclosynch, in the order it takes them
+// 1. the open lists and their arguments; every list's counters start from zero
+static int pcs_collect(PoolCsFrames &F)
+{
+    mcrat_hip_ctx *c = F.c;
+    const size_t R = (size_t)F.R;
+    F.open.assign(R, 0); F.emit_base.assign(R, 0); F.carried.assign(R, 0); F.seeds.assign(R, 0);
+    F.t_now.assign(R, 0.0); F.t_rem.assign(R, 0.0); F.csr.assign(R, *F.cs);
+    for (int r = 0; r < F.R; ++r) {
+        F.carried[(size_t)r] = F.counts[r].scatt_cyclosynch_num_ph;
+        memset(&F.counts[r], 0, sizeof F.counts[r]);
+        const mcrat_hip_pool_cs_list &l = F.lists[r];
+        if (!l.open) continue;
+        mcrat_hip_ctx *v = c->views[r];
+        if (!v || !v->have_photons) { c->last_error = "pool_scatter_frames_cyclosynch: an open list does not exist"; return MCRAT_HIP_ESTATE; }
+        F.open[(size_t)r] = 1;
+        F.seeds[(size_t)r] = l.seed; F.t_now[(size_t)r] = l.time_now; F.t_rem[(size_t)r] = l.remaining_time;
+        F.csr[(size_t)r].scatt_frame_number = l.scatt_frame_number;
+        F.csr[(size_t)r].inj_frame_number = l.inj_frame_number;
+    }
+    return MCRAT_HIP_OK;
+}
+// 4. the hooks' state, one CsFrame per list, the lists' descriptions, and what the hook is given
+static int pcs_upload_hooks(PoolCsFrames &F)
+{
+    mcrat_hip_ctx *c = F.c;
+    const size_t R = (size_t)F.R;
+    if (c->d_cs_hook) { HIPCHK(c, hipFree(c->d_cs_hook)); c->d_cs_hook = nullptr; }
+    HIPCHK(c, hipMalloc((void **)&c->d_cs_hook, sizeof(CsFrame) * R));
+    F.d_cf = static_cast<CsFrame *>(c->d_cs_hook);
+    F.cf.resize(R);
+    for (size_t r = 0; r < R; ++r) F.cf[r] = cs_frame_begin(F.max_photons, F.carried[r]);
+    HIPCHK(c, hipMemcpyAsync(F.d_cf, F.cf.data(), sizeof(CsFrame) * R, hipMemcpyHostToDevice, c->stream));
+    int rc = pool_describe(c);
+    if (rc) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    F.p = cs_emit_params(c, F.cs);
+    if (!c->d_cs_args) HIPCHK(c, hipMalloc(&c->d_cs_args, sizeof(CsHookArgs)));
+    CsHookArgs ha;
+    ha.p = F.p; ha.h = c->hcol;
+    HIPCHK(c, hipMemcpyAsync(c->d_cs_args, &ha, sizeof ha, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MCRAT_HIP_OK;
+}
+// 5. lists that change length: columns stay in HBM/L2 (longest = the window), so LDS does not limit the lists per CU; with more than
+// two lists per CU the 128-thread workgroups put four on one (cfg5 at 1e7 photons: 420 -> 380 ms per frame)
+static void pcs_choose_block(PoolCsFrames &F)
+{
+    mcrat_hip_ctx *c = F.c;
+    const int cus = device_cus(c);
+    c->rank_block = F.R > 2 * cus ? 128 : 256;
+    // ... and with eight and more per CU one wavefront per list (eight on a CU): no wave ever waits at a barrier for the one that walks
+    // the event (cfg5: 250 -> 230 ms per frame); only with the hook inside the loop (the hook kernel is written for 128 threads and more)
+    if (F.R > 8 * cus && !F.hook_kernel) c->rank_block = 64;
+    c->rank_fuse = false;
+    if (const char *e = getenv("MCRAT_HIP_RANK_BLOCK")) c->rank_block = (atoi(e) == 64) ? 64 : (atoi(e) == 128) ? 128 : 256;
+}
+// 6. the loop.  The hook runs inside rank_loop_kernel (its CSH build: cs_hook_body right after the pass, the list goes on in the same launch); with
+// hook_kernel the lists park after such a pass instead and cs_replace_pool_kernel runs it between two launches.  Either way a list only stays
+// parked for the host when it has to be rebinned (:797-808): all parked lists in the same two launches, then they go on.
+static int pcs_loop(PoolCsFrames &F)
+{
+    mcrat_hip_ctx *c = F.c;
+    const int R = F.R;
+    int rc;
+    const int pairs_per_sync = F.hook_kernel ? 8 : 2;
+    RankLaunch rl = rank_launch_of(c, c->d_desc, 4096);
+    rl.longest_list = RANK_COLUMNS_GLOBAL;           // (lists that change length: their columns stay in HBM/L2)
+    rl.cs = F.d_cf;
+    rl.hook = F.hook_kernel ? nullptr : static_cast<const CsHookArgs *>(c->d_cs_args);
+    for (;;) {
+        rc = profiled(c, pairs_per_sync, [&]() -> int {         // the loop's launches between events (bench.py: cfg5's loop-only roofline)
+            for (int k = 0; k < pairs_per_sync; ++k) {
+                HIPCHK(c, launch_rank_loop(c->kc, c->ph, c->hy, c->d_rstates, c->key, rl, c->stream));
+                if (F.hook_kernel) HIPCHK(c, launch_cs_replace_pool(F.p, c->hy, c->hcol, c->d_rstates, c->ph, c->rank_stride, R, c->d_desc, F.d_cf, c->stream));
+            }
+            return MCRAT_HIP_OK;
+        });
+        if (rc) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->h_rstates, c->d_rstates, sizeof(LoopState) * (size_t)R, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(F.cf.data(), F.d_cf, sizeof(CsFrame) * (size_t)R, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->h_desc, c->d_desc, sizeof(RankDesc) * (size_t)R, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        std::vector<int> parked;                                                                  // lists waiting for rebinCyclosynchCompPhotons
+        for (int r = 0; r < R; ++r) {
+            if (!F.open[(size_t)r]) continue;
+            c->views[r]->ph.n = c->h_desc[r].len;                                                 // the list may have doubled in the hook
+            if (F.cf[(size_t)r].halt == CS_HALT_GROW) {
+                c->last_error = "a cyclo-synchrotron list outgrew the pool's slots per rank (mcrat_hip_pool_create: allow for the doublings)";
+                return MCRAT_HIP_ENOMEM;
+            }
+            if (F.cf[(size_t)r].halt == CS_HALT_REBIN) parked.push_back(r);
+        }
+        if (!parked.empty()) {
+            std::vector<PoolRebinResult> res;
+            if ((rc = pool_rebin(c, F.cs, F.max_photons, parked, res))) return rc;
+            for (size_t j = 0; j < parked.size(); ++j) {
+                const int r = parked[j];
+                CsFrame &f = F.cf[(size_t)r];
+                if (res[j].rc == MCRAT_HIP_OK) cs_frame_rebinned(f, F.counts[r], F.emit_base[(size_t)r], res[j].num_cyclosynch_ph_emit, res[j].scatt_cyclosynch_num_ph);
+                cs_frame_release(f, &c->h_rstates[r]);
+                HIPCHK(c, hipMemcpyAsync(F.d_cf + r, &f, sizeof f, hipMemcpyHostToDevice, c->stream));
+                HIPCHK(c, send_done(&c->h_rstates[r], c->d_rstates + r, c->stream));
+            }
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        }
+        bool all_done = true;
+        for (int r = 0; r < R; ++r)
+            if (F.open[(size_t)r] && c->h_rstates[r].done != LOOP_DONE) all_done = false;
+        if (all_done) return MCRAT_HIP_OK;
+    }
+}
+// 7. the frames' counters from the hooks' state; the lists are current
+static void pcs_close_counters(PoolCsFrames &F)
+{
+    mcrat_hip_ctx *c = F.c;
+    for (int r = 0; r < F.R; ++r) {
+        if (!F.open[(size_t)r]) continue;
+        mcrat_hip_ctx *v = c->views[r];
+        cs_frame_close(F.cf[(size_t)r], F.emit_base[(size_t)r], F.counts[r]);
+        v->pending_applied = false;
+        v->rank_current = true;
+        if (F.stats) state_to_stats(c->h_rstates[r], v->ph.n, &F.stats[r]);
+    }
+}
+// 8. :853-878, the lists over max_photons all at once
+static int pcs_end_rebin(PoolCsFrames &F)
+{
+    std::vector<int> over;
+    for (int r = 0; r < F.R; ++r)
+        if (cs_end_rebin_due(F.emits(r), F.counts[r], F.max_photons)) over.push_back(r);
+    std::vector<PoolRebinResult> res;
+    int rc = pool_rebin(F.c, F.cs, F.max_photons, over, res);
+    if (rc) return rc;
+    for (size_t j = 0; j < over.size(); ++j) {
+        if (res[j].rc != MCRAT_HIP_OK) continue;
+        const int r = over[j];
+        F.counts[r].rebins += 1;
+        F.counts[r].num_cyclosynch_ph_emit = res[j].num_cyclosynch_ph_emit;
+        F.counts[r].scatt_cyclosynch_num_ph = res[j].scatt_cyclosynch_num_ph;
+    }
+    return MCRAT_HIP_OK;
+}
+// 9. phAbsCyclosynch of every list that emitted, one launch
+static int pcs_absorb(PoolCsFrames &F)
+{
+    mcrat_hip_ctx *c = F.c;
+    const int R = F.R;
+    int rc;
+    std::vector<int> absorb((size_t)R, 0);
+    bool any_absorb = false;
+    for (int r = 0; r < R; ++r)
+        if (cs_end_absorb_due(F.emits(r), F.counts[r])) { absorb[(size_t)r] = 1; any_absorb = true; }
+    if (!any_absorb) return MCRAT_HIP_OK;
+    for (int r = 0; r < R; ++r)
+        if (absorb[(size_t)r] && (rc = flush_pending(c->views[r]))) return rc;
+    for (int r = 0; r < R; ++r) { c->h_desc[r].len = F.open[(size_t)r] ? c->views[r]->ph.n : 0; }
+    const size_t bytes = (sizeof(CsAbsPartial) + sizeof(int)) * (size_t)R;
+    if ((rc = ensure_aos(c, bytes + 64))) return rc;
+    CsAbsPartial *d_part = static_cast<CsAbsPartial *>(c->aos_buf);
+    int *d_sel = reinterpret_cast<int *>(d_part + R);
+    std::vector<CsAbsPartial> part((size_t)R);
+    HIPCHK(c, hipMemcpyAsync(c->d_desc, c->h_desc, sizeof(RankDesc) * (size_t)R, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_sel, absorb.data(), sizeof(int) * (size_t)R, hipMemcpyHostToDevice, c->stream));
+    CsParams ap{c->kc.dimensions, F.cs->b_field_calc, F.cs->epsilon_b};
+    HIPCHK(c, launch_cs_absorb_pool(ap, c->ph, c->rank_stride, R, c->d_desc, d_sel, c->hy.temp, c->hcol, d_part, c->stream));
+    HIPCHK(c, hipMemcpyAsync(part.data(), d_part, sizeof(CsAbsPartial) * (size_t)R, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int r = 0; r < R; ++r) {
+        if (!absorb[(size_t)r]) continue;
+        F.counts[r].frame_abs_cnt = (int)part[(size_t)r].abs_count;
+        F.counts[r].scatt_cyclosynch_num_ph = (int)part[(size_t)r].scatt_count;
+        F.counts[r].n_comptonized -= part[(size_t)r].abs_weight;
+        drop_graph(c->views[r]);
+    }
+    return MCRAT_HIP_OK;
+}
+
 // The scatter frame of mcrat.c:706-878 with CYCLOSYNCHROTRON_SWITCH on for the lists of a rank pool: what mcrat_hip_scatter_frame_cyclosynch
 // does for one list, for every open list -- the loop of all of them in the same launches.  rank_loop_kernel (its CSH build) runs every list
 // and, after a pass the hook of :786-808 must look at (photonEvent reported a pool photon; a thousand scatterings are full), the hook itself:
 // it converts and replaces the pool photon (doubling the list inside its window of the pool when it has no null slot left) and evaluates
-// the rebinning trigger; the list goes on in the same launch.  Only the rebinning itself parks a list for the host (the view's
-// mcrat_hip_rebin_cyclosynch).  (First form, MCRAT_HIP_CS_HOOK_KERNEL=1: the list parks after every such pass and cs_replace_pool_kernel,
-// one workgroup per parked list, runs the hook between two launches of the loop.)
+// the rebinning trigger; the list goes on in the same launch.  Only the rebinning itself parks a list for the host (pool_rebin).
+// (First form, MCRAT_HIP_CS_HOOK_KERNEL=1: the list parks after every such pass and cs_replace_pool_kernel, one workgroup per parked list,
+// runs the hook between two launches of the loop, 8 pairs per read-back; no 64-thread lists.)
 extern "C" int mcrat_hip_pool_scatter_frames_cyclosynch(mcrat_hip_ctx *c, const mcrat_hip_cyclosynch *cs, int max_photons, double fps,
                                                         const mcrat_hip_pool_cs_list *lists, mcrat_hip_frame_stats *stats,
                                                         mcrat_hip_cyclosynch_counts *counts)
@@ -3903,170 +4053,19 @@ extern "C" int mcrat_hip_pool_scatter_frames_cyclosynch(mcrat_hip_ctx *c, const 
     if (!c->cfg.cyclosynchrotron_switch) { c->last_error = "the pool was created with cyclosynchrotron_switch = 0"; return MCRAT_HIP_ESTATE; }
     if (c->d_pool_tapes) { c->last_error = "the pool holds tapes of uniforms (mcrat_hip_pool_set_rng_tapes): the cyclo-synchrotron hook has no tape build"; return MCRAT_HIP_ESTATE; }
     if (!c->have_hydro || !c->hcol_buf) return MCRAT_HIP_ESTATE;
-    const int R = c->n_ranks;
+    PoolCsFrames F{};
+    F.c = c; F.cs = cs; F.max_photons = max_photons; F.R = c->n_ranks; F.fps = fps; F.lists = lists; F.stats = stats; F.counts = counts;
+    F.hook_kernel = env_flag("MCRAT_HIP_CS_HOOK_KERNEL");
     int rc;
-    std::vector<int> open((size_t)R, 0), emit_base((size_t)R, 0);
-    std::vector<uint64_t> seeds((size_t)R, 0);
-    std::vector<double> t_now((size_t)R, 0.0), t_rem((size_t)R, 0.0);
-    std::vector<mcrat_hip_cyclosynch> csr((size_t)R, *cs);
-    std::vector<int> carried((size_t)R, 0);
-    for (int r = 0; r < R; ++r) {
-        carried[(size_t)r] = counts[r].scatt_cyclosynch_num_ph;      // in: the counter main() carries from the previous frame (mcrat.c:873,921)
-        memset(&counts[r], 0, sizeof counts[r]);
-        if (!lists[r].open) continue;
-        mcrat_hip_ctx *v = c->views[r];
-        if (!v || !v->have_photons) { c->last_error = "pool_scatter_frames_cyclosynch: an open list does not exist"; return MCRAT_HIP_ESTATE; }
-        open[(size_t)r] = 1;
-        seeds[(size_t)r] = lists[r].seed; t_now[(size_t)r] = lists[r].time_now; t_rem[(size_t)r] = lists[r].remaining_time;
-        csr[(size_t)r].scatt_frame_number = lists[r].scatt_frame_number;
-        csr[(size_t)r].inj_frame_number = lists[r].inj_frame_number;
-    }
-    if ((rc = pool_emit_cyclosynch(c, cs, csr, max_photons, fps, lists, counts, emit_base))) return rc;                // :727-744
-    if ((rc = mcrat_hip_pool_begin_frames(c, open.data(), seeds.data(), t_now.data(), t_rem.data()))) return rc;
-    // the hooks' state, one CsFrame per list
-    if (c->d_cs_hook) { HIPCHK(c, hipFree(c->d_cs_hook)); c->d_cs_hook = nullptr; }
-    HIPCHK(c, hipMalloc((void **)&c->d_cs_hook, sizeof(CsFrame) * (size_t)R));
-    CsFrame *d_cf = static_cast<CsFrame *>(c->d_cs_hook);
-    std::vector<CsFrame> cf((size_t)R);
-    for (int r = 0; r < R; ++r) {
-        cf[(size_t)r] = CsFrame{};
-        cf[(size_t)r].max_photons = max_photons; cf[(size_t)r].last_iteration = ~0ull; cf[(size_t)r].scatt_num = carried[(size_t)r];
-    }
-    HIPCHK(c, hipMemcpyAsync(d_cf, cf.data(), sizeof(CsFrame) * (size_t)R, hipMemcpyHostToDevice, c->stream));
-    if ((rc = pool_describe(c))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    CsEmitParams p{};
-    p.dimensions = c->kc.dimensions; p.geometry = c->kc.geometry; p.b_field_calc = cs->b_field_calc; p.epsilon_b = cs->epsilon_b;
-    // lists that change length: columns stay in HBM/L2 (longest = the window), so LDS does not limit the lists per CU; with more than
-    // two lists per CU the 128-thread workgroups put four on one (cfg5 at 1e7 photons: 420 -> 380 ms per frame)
-    {
-        const int cus = device_cus(c);
-        c->rank_block = R > 2 * cus ? 128 : 256;
-        // ... and with eight and more per CU one wavefront per list (eight on a CU): no wave ever waits at a barrier for the one that walks
-        // the event (cfg5: 250 -> 230 ms per frame); only with the hook inside the loop (the hook kernel is written for 128 threads and more)
-        if (R > 8 * cus && !env_flag("MCRAT_HIP_CS_HOOK_KERNEL")) c->rank_block = 64;
-        c->rank_fuse = false;
-        if (const char *e = getenv("MCRAT_HIP_RANK_BLOCK")) c->rank_block = (atoi(e) == 64) ? 64 : (atoi(e) == 128) ? 128 : 256;
-    }
-    // The hook runs inside rank_loop_kernel (its CSH build: cs_hook_body right after the pass, the list goes on in the same launch); with
-    // MCRAT_HIP_CS_HOOK_KERNEL=1 the lists park after such a pass instead and cs_replace_pool_kernel runs it between two launches (the
-    // first form of this driver, kept for the A/B).  Either way a list only stays parked for the host when it has to be rebinned.
-    const bool hook_kernel = env_flag("MCRAT_HIP_CS_HOOK_KERNEL");
-    if (!c->d_cs_args) HIPCHK(c, hipMalloc(&c->d_cs_args, sizeof(CsHookArgs)));
-    {
-        CsHookArgs ha;
-        ha.p = p; ha.h = c->hcol;
-        HIPCHK(c, hipMemcpyAsync(c->d_cs_args, &ha, sizeof ha, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    const CsHookArgs *d_args = hook_kernel ? nullptr : static_cast<const CsHookArgs *>(c->d_cs_args);
-    const int pairs_per_sync = hook_kernel ? 8 : 2;
-    // (lists that change length: their columns stay in HBM/L2)
-    RankLaunch rl = rank_launch_of(c, c->d_desc, 4096);
-    rl.longest_list = RANK_COLUMNS_GLOBAL; rl.cs = d_cf; rl.hook = d_args;
-    for (;;) {
-        rc = profiled(c, pairs_per_sync, [&]() -> int {         // the loop's launches between events (bench.py: cfg5's loop-only roofline)
-            for (int k = 0; k < pairs_per_sync; ++k) {
-                HIPCHK(c, launch_rank_loop(c->kc, c->ph, c->hy, c->d_rstates, c->key, rl, c->stream));
-                if (hook_kernel) HIPCHK(c, launch_cs_replace_pool(p, c->hy, c->hcol, c->d_rstates, c->ph, c->rank_stride, R, c->d_desc, d_cf, c->stream));
-            }
-            return MCRAT_HIP_OK;
-        });
-        if (rc) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->h_rstates, c->d_rstates, sizeof(LoopState) * (size_t)R, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(cf.data(), d_cf, sizeof(CsFrame) * (size_t)R, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->h_desc, c->d_desc, sizeof(RankDesc) * (size_t)R, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        bool all_done = true;
-        std::vector<int> parked;                                                                  // lists waiting for rebinCyclosynchCompPhotons (:797-808)
-        for (int r = 0; r < R; ++r) {
-            if (!open[(size_t)r]) continue;
-            mcrat_hip_ctx *v = c->views[r];
-            v->ph.n = c->h_desc[r].len;                                                           // the list may have doubled in the hook
-            CsFrame &f = cf[(size_t)r];
-            if (f.halt == CS_HALT_GROW) {
-                c->last_error = "a cyclo-synchrotron list outgrew the pool's slots per rank (mcrat_hip_pool_create: allow for the doublings)";
-                return MCRAT_HIP_ENOMEM;
-            }
-            if (f.halt == CS_HALT_REBIN) parked.push_back(r);
-        }
-        if (!parked.empty()) {                                                                    // all of them in the same two launches
-            std::vector<PoolRebinResult> res;
-            if ((rc = pool_rebin(c, cs, max_photons, parked, res))) return rc;
-            for (size_t j = 0; j < parked.size(); ++j) {
-                const int r = parked[j];
-                CsFrame &f = cf[(size_t)r];
-                if (res[j].rc == MCRAT_HIP_OK) {
-                    counts[r].rebins += 1;
-                    emit_base[(size_t)r] = res[j].num_cyclosynch_ph_emit;
-                    f.emitted = 0;
-                    f.scatt_num = res[j].scatt_cyclosynch_num_ph;
-                }
-                f.halt = 0;
-                c->h_rstates[r].done = f.saved_done;
-                HIPCHK(c, hipMemcpyAsync(d_cf + r, &f, sizeof f, hipMemcpyHostToDevice, c->stream));
-                HIPCHK(c, hipMemcpyAsync(reinterpret_cast<char *>(c->d_rstates + r) + offsetof(LoopState, done), &c->h_rstates[r].done, sizeof(int),
-                                         hipMemcpyHostToDevice, c->stream));
-            }
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-        }
-        for (int r = 0; r < R; ++r)
-            if (open[(size_t)r] && c->h_rstates[r].done != LOOP_DONE) all_done = false;
-        if (all_done) break;
-    }
-    std::vector<int> absorb((size_t)R, 0);
-    bool any_absorb = false;
-    for (int r = 0; r < R; ++r) {
-        if (!open[(size_t)r]) continue;
-        mcrat_hip_ctx *v = c->views[r];
-        const CsFrame &f = cf[(size_t)r];
-        counts[r].num_cyclosynch_ph_emit = emit_base[(size_t)r] + f.emitted;
-        counts[r].scatt_cyclosynch_num_ph = f.scatt_num;
-        counts[r].n_comptonized = f.n_comptonized;
-        v->pending_applied = false;
-        v->rank_current = true;
-        if (stats) state_to_stats(c->h_rstates[r], v->ph.n, &stats[r]);
-    }
-    {                                                                                             // :853-878, the lists over max_photons all at once
-        std::vector<int> over;
-        for (int r = 0; r < R; ++r)
-            if (open[(size_t)r] && lists[r].emit_pool && counts[r].scatt_cyclosynch_num_ph > max_photons) over.push_back(r);
-        std::vector<PoolRebinResult> res;
-        if ((rc = pool_rebin(c, cs, max_photons, over, res))) return rc;
-        for (size_t j = 0; j < over.size(); ++j) {
-            if (res[j].rc != MCRAT_HIP_OK) continue;
-            const int r = over[j];
-            counts[r].rebins += 1;
-            counts[r].num_cyclosynch_ph_emit = res[j].num_cyclosynch_ph_emit;
-            counts[r].scatt_cyclosynch_num_ph = res[j].scatt_cyclosynch_num_ph;
-        }
-        for (int r = 0; r < R; ++r)
-            if (open[(size_t)r] && lists[r].emit_pool && counts[r].num_cyclosynch_ph_emit > 0) { absorb[(size_t)r] = 1; any_absorb = true; }
-    }
-    if (any_absorb) {                                                                             // phAbsCyclosynch of every such list, one launch
-        for (int r = 0; r < R; ++r)
-            if (absorb[(size_t)r] && (rc = flush_pending(c->views[r]))) return rc;
-        for (int r = 0; r < R; ++r) { c->h_desc[r].len = open[(size_t)r] ? c->views[r]->ph.n : 0; }
-        const size_t bytes = (sizeof(CsAbsPartial) + sizeof(int)) * (size_t)R;
-        if ((rc = ensure_aos(c, bytes + 64))) return rc;
-        CsAbsPartial *d_part = static_cast<CsAbsPartial *>(c->aos_buf);
-        int *d_sel = reinterpret_cast<int *>(d_part + R);
-        std::vector<CsAbsPartial> part((size_t)R);
-        HIPCHK(c, hipMemcpyAsync(c->d_desc, c->h_desc, sizeof(RankDesc) * (size_t)R, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_sel, absorb.data(), sizeof(int) * (size_t)R, hipMemcpyHostToDevice, c->stream));
-        CsParams ap{c->kc.dimensions, cs->b_field_calc, cs->epsilon_b};
-        HIPCHK(c, launch_cs_absorb_pool(ap, c->ph, c->rank_stride, R, c->d_desc, d_sel, c->hy.temp, c->hcol, d_part, c->stream));
-        HIPCHK(c, hipMemcpyAsync(part.data(), d_part, sizeof(CsAbsPartial) * (size_t)R, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        for (int r = 0; r < R; ++r) {
-            if (!absorb[(size_t)r]) continue;
-            counts[r].frame_abs_cnt = (int)part[(size_t)r].abs_count;
-            counts[r].scatt_cyclosynch_num_ph = (int)part[(size_t)r].scatt_count;
-            counts[r].n_comptonized -= part[(size_t)r].abs_weight;
-            drop_graph(c->views[r]);
-        }
-    }
-    return MCRAT_HIP_OK;
+    if ((rc = pcs_collect(F))) return rc;
+    if ((rc = pool_emit_cyclosynch(F))) return rc;                                                                     // :727-744
+    if ((rc = mcrat_hip_pool_begin_frames(c, F.open.data(), F.seeds.data(), F.t_now.data(), F.t_rem.data()))) return rc;
+    if ((rc = pcs_upload_hooks(F))) return rc;
+    pcs_choose_block(F);
+    if ((rc = pcs_loop(F))) return rc;                                                                                 // :761-851
+    pcs_close_counters(F);
+    if ((rc = pcs_end_rebin(F))) return rc;                                                                            // :853-878
+    return pcs_absorb(F);
 }
 
 extern "C" int mcrat_hip_step_locate_sample(mcrat_hip_ctx *c, int find_nearest_block_switch)

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include "device_types.hpp"
 #include "frame_queue.hpp"
+#include "list_plan.hpp"
 
 namespace mcrat {
 
@@ -303,14 +304,6 @@ hipError_t launch_null_write(const PhotonDev &ph, const int *block_start, int *n
 // slots [first, first + count) become null photons (reallocatePhotonListMemory, photons.c:72-78)
 hipError_t launch_null_fill(const PhotonDev &ph, int first, int count, hipStream_t stream);
 // rebinCyclosynchCompPhotons on the device (inject.hip; mc_cyclosynch.c:246-712)
-struct RebinRange {            // collect_photon_statistics :273-322, one per workgroup, finished on the host
-    double p0_min, p0_max, theta_min, theta_max, phi_min, phi_max;
-    int valid, synch;
-};
-struct RebinAxes {             // the three uniform histograms' ranges (:360-391) and the bin counts (:324-347)
-    double e_lo, e_hi, t_lo, t_hi, p_lo, p_hi;
-    int num_bins, num_bins_theta, num_bins_phi, total_bins, three;
-};
 int rebin_range_blocks(int n);
 hipError_t launch_rebin_range(const PhotonDev &ph, int three, RebinRange *partials, hipStream_t stream);
 // bin of every slot (-1: not rebinned; -2: outside the histograms, the reference's exit(1)) and the number of slots per bin

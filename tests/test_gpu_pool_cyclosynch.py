@@ -2,7 +2,10 @@
 scatter frame of mcrat.c:706-878 in the same launches -- pool emission, the loop in which a scattered pool photon becomes a comptonised
 one and is replaced (the list doubling inside its window of the pool), the rebinning trigger, rebinning and absorption -- and every
 list must come out as orc_scatter_frame_cs leaves it when run on that list alone: same passes, scatterings, counters, list length,
-types, slots and weights; doubles to 1e-9."""
+types, slots and weights; doubles to 1e-9.  The frame is a sequence of steps in engine.hip (pcs_collect, pool_emit_cyclosynch, pcs_upload_hooks,
+pcs_choose_block, pcs_loop, pcs_close_counters, pcs_end_rebin, pcs_absorb); the rules it shares with the one-list path -- histogram axes, refusals,
+shell radii, weight search -- are list_plan.hpp's (tests/test_list_plan_cpu.py).  Both A/B forms are held equal to the default to the byte:
+MCRAT_HIP_POOL_REBIN_EACH=1 (rebinning list by list) and MCRAT_HIP_CS_HOOK_KERNEL=1 (the hook as a kernel between two launches)."""
 import ctypes as C
 
 import numpy as np
@@ -180,6 +183,46 @@ def test_dozens_of_lists_rebinned_in_the_same_frame(hip, oracle, monkeypatch):
         for f in ("p0", "r0", "r1", "r2", "s1"):
             scale = np.maximum(np.abs(want["p0"]), 1e-300) if f == "p0" else (np.maximum(np.abs(want[f]), 1e9) if f.startswith("r") else 1.0)
             assert np.all(np.abs(got[f] - want[f]) / scale <= 1e-9), (r, f)
+
+
+@pytest.mark.parametrize("threads", ["256", "128"])
+def test_the_hook_as_a_kernel_between_launches_gives_the_same_lists(hip, oracle, threads, monkeypatch):
+    """MCRAT_HIP_CS_HOOK_KERNEL=1 (the hook as cs_replace_pool_kernel between two launches of the loop, the first form of the pool frame) against
+    the hook inside the loop kernel: the "2d-rebinning-lists" pool -- a list doubles, a list is parked for rebinning -- comes out the same to the bit."""
+    monkeypatch.setenv("MCRAT_HIP_RANK_BLOCK", threads)
+    mesh, b_field_calc, max_photons, theta_max, ang_phi, lists = POOLS["2d-rebinning-lists"]
+    frame, ph, cfg = synth.config2(n_photons=300, nzc=8, lumi=3e53)
+    dens = np.ascontiguousarray(frame["dens"])
+    starts = [None if spec is None else _start_list(oracle, ph, 7 * r) for r, spec in enumerate(lists)]
+    args = [None if spec is None else dict(seed=spec[0], time_now=0.0, remaining_time=spec[1], r_inj=1e12, ph_weight_suggest=1e40, theta_min=0.0,
+                                           theta_max=theta_max, emit_pool=spec[2], scatt_frame_number=200, inj_frame_number=200) for spec in lists]
+    runs = {}
+    for hook_kernel in ("0", "1"):
+        monkeypatch.setenv("MCRAT_HIP_CS_HOOK_KERNEL", hook_kernel)
+        pool = hip.Engine(cfg["dimensions"], cfg["geometry"], 1, cyclosynchrotron=1)
+        pool.set_hydro(frame)
+        pool.set_hydro_extras(dens, None, None, None)
+        pool.pool_create(len(lists), 4800)
+        for r, before in enumerate(starts):
+            if before is not None:
+                pool.pool_rank(r, r).set_photons_aos(before.astype(hip.PHOTON_DTYPE))
+        sts, cnts = pool.pool_scatter_frames_cyclosynch(args, max_photons, frame["fps"], b_field_calc=b_field_calc, rebin_ang_phi=ang_phi)
+        runs[hook_kernel] = (sts, cnts, [None if s is None else pool.pool_rank(r, r).get_photons_aos() for r, s in enumerate(starts)])
+        pool.close()
+    (sa, ca, la), (sb, cb, lb) = runs["0"], runs["1"]
+    grew = rebinned = 0
+    for r, spec in enumerate(lists):
+        if spec is None:
+            continue
+        assert sa[r].iterations == sb[r].iterations, r
+        assert sa[r].frame_scatt_cnt == sb[r].frame_scatt_cnt, r
+        assert (ca[r].num_cyclosynch_ph_emit, ca[r].scatt_cyclosynch_num_ph, ca[r].frame_abs_cnt, ca[r].rebins) == \
+            (cb[r].num_cyclosynch_ph_emit, cb[r].scatt_cyclosynch_num_ph, cb[r].frame_abs_cnt, cb[r].rebins), r
+        assert len(la[r]) == len(lb[r]), r
+        assert la[r].tobytes() == lb[r].tobytes(), r
+        grew += len(la[r]) > 600
+        rebinned += ca[r].rebins
+    assert grew >= 1 and rebinned >= 1                      # the case is the one it is meant to be: a list doubled, a list was parked for rebinning
 
 
 def test_a_pool_too_small_for_the_doublings_says_so(hip, oracle):
