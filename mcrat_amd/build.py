@@ -13,9 +13,10 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmcrat_hip.so")
+ABI_HEADER = os.path.join("..", "..", "include", "mcrat_hip.h")        # the C ABI, relative to csrc
 KERNEL_TUS = ["kernels%s_d%d.hip" % (m, d) for m in ("", "_table") for d in (0, 1, 2)]   # kernels.hip per TAU_CALCULATION x DIMENSIONS
 SOURCES = KERNEL_TUS + ["launchers.hip", "grid_build.hip", "staging.hip", "inject.hip", "ingest.hip", "hot_table.hip", "functions.hip", "engine.hip"]
-HEADERS = ["kernels.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp", "physics.hpp", "rng.hpp", "cs_device.hpp", os.path.join("..", "..", "include", "mcrat_hip.h")]
+HEADERS = ["kernels.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp", "hydro_plan.hpp", "physics.hpp", "rng.hpp", "cs_device.hpp", ABI_HEADER]
 # -amdgpu-prealloc-sgpr-spill-vgprs: the loop kernels sit at 256 VGPRs with hundreds of scalar registers spilled to lanes of vector registers; with the
 #   compiler's default (those vector registers chosen after everything else is allocated) single instantiations wrote a wrong Stokes V -- another
 #   instantiation after every larger edit (round 3: 3-D spherical; round 4: 3-D polar; without the shadow draws: 3-D spherical again), every time cured
@@ -26,17 +27,20 @@ HEADERS = ["kernels.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-fvisibility=hidden",
          "-mllvm", "-amdgpu-prealloc-sgpr-spill-vgprs=1", "--offload-compress"]
 OBJDIR = os.path.join(HERE, "_obj")
-_KERNEL_DEPS = ["kernels.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp", "physics.hpp", "rng.hpp", "cs_device.hpp"]
-DEPS = {"launchers.hip": ["launchers.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp"],
-        "grid_build.hip": ["grid_build.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp"],
-        "staging.hip": ["staging.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp", os.path.join("..", "..", "include", "mcrat_hip.h")],
-        "inject.hip": ["inject.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp", "physics.hpp", "rng.hpp", "cs_device.hpp"],
-        "ingest.hip": ["ingest.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp"],
-        "hot_table.hip": ["hot_table.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp", "physics.hpp", "rng.hpp"],
-        "functions.hip": ["functions.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp", "physics.hpp", "rng.hpp", os.path.join("..", "..", "include", "mcrat_hip.h")],
-        "engine.hip": ["engine.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp", "photon_cols.hpp", "rng.hpp", os.path.join("..", "..", "include", "mcrat_hip.h")]}
+_KERNEL_DEPS = ["kernels.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp", "hydro_plan.hpp", "physics.hpp", "rng.hpp", "cs_device.hpp"]
+DEPS = {"launchers.hip": ["launchers.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp", "hydro_plan.hpp"],
+        "grid_build.hip": ["grid_build.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp", "hydro_plan.hpp"],
+        "staging.hip": ["staging.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp", "hydro_plan.hpp", ABI_HEADER],
+        "inject.hip": ["inject.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp", "hydro_plan.hpp", "physics.hpp", "rng.hpp", "cs_device.hpp"],
+        "ingest.hip": ["ingest.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp", "hydro_plan.hpp"],
+        "hot_table.hip": ["hot_table.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp", "hydro_plan.hpp", "physics.hpp", "rng.hpp"],
+        "functions.hip": ["functions.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp", "hydro_plan.hpp", "physics.hpp", "rng.hpp", ABI_HEADER],
+        "engine.hip": ["engine.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp", "hydro_plan.hpp", "photon_cols.hpp", "rng.hpp", ABI_HEADER]}
 for _tu in KERNEL_TUS:
     DEPS[_tu] = _KERNEL_DEPS + [_tu]
+for _deps in DEPS.values():       # hydro_plan.hpp reads the ABI's structs, so every unit that includes launch.hpp does
+    if ABI_HEADER not in _deps:
+        _deps.append(ABI_HEADER)
 
 def hipcc():
     for c in (os.environ.get("HIPCC"), shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):

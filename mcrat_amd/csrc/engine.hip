@@ -177,6 +177,14 @@ struct mcrat_hip_ctx {
 
 static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 static bool env_flag(const char *name) { const char *e = getenv(name); return e && atoi(e) != 0; }      // an environment switch: set, and not to 0
+// a device buffer that only grows: room for `need` bytes at *buf -- the buffer as it is when it has them, a new one of `need` bytes when not (the
+// contents go; the caller has made sure that nothing on the device still reads them)
+static int ensure_device_bytes(mcrat_hip_ctx *c, void **buf, size_t *bytes, size_t need)
+{
+    if (*buf && *bytes < need) { HIPCHK(c, hipFree(*buf)); *buf = nullptr; *bytes = 0; }
+    if (!*buf) { HIPCHK(c, hipMalloc(buf, need)); *bytes = need; }
+    return MCRAT_HIP_OK;
+}
 
 // a temporary device array of one call: freed where its scope ends, whichever way the call leaves it
 template <class T>
@@ -440,200 +448,7 @@ extern "C" int mcrat_hip_create_hot_cross_section(mcrat_hip_ctx *c, double *ther
 }
 
 // ---------------------------------------------------------------------------------------------- hydro staging
-namespace {
-
-struct GridHost {
-    std::vector<int> start, cells;
-    std::vector<unsigned> hints;      // per bucket, see BucketDir
-    double ext_lo[3] = {0, 0, 0}, ext_hi[3] = {0, 0, 0}, ncell[3] = {1, 1, 1}, f0 = 1.0;   // grid_plan()
-    double org[3] = {0, 0, 0}, inv[3] = {0, 0, 0};
-    int dim[3] = {1, 1, 1}, logmap[3] = {0, 0, 0}, naxes = 2;
-};
-
-inline int bucket_of(double x, int logmap, double org, double inv, int dim)
-{
-    double u = logmap ? std::log(x) : x;
-    double f = std::floor((u - org) * inv);
-    if (!(f == f)) return 0;
-    if (f < 0.0) return 0;
-    if (f > (double)(dim - 1)) return dim - 1;
-    return (int)f;
-}
-
-// Exact accelerator for the reference's linear findContainingBlock (geometry.c:350-391).  Every cell is
-// entered into all buckets its closed extent, widened by 1e-9 relative, touches; cells are visited in
-// ascending index so each bucket list is ascending.  The device walks the list of the bucket holding the
-// point and applies the reference's own closed-interval test, so it returns the lowest-index containing
-// cell exactly as the linear scan does.  (The reference's own buildSpatialGrid, geometry.c:526-676, is
-// disabled at HEAD and tests DIMENSIONS against the wrong constants; it is not reproduced.)
-// extents, log mapping and typical cell widths of the mesh: what fixes the bucket grid up to a scale factor f
-struct MeshStats {      // what the plan needs from the mesh: per axis the extent, the smallest and largest width, and every
-    double lo[3], hi[3], smin[3], smax[3];       // stride-th cell's centre and width (stride = max(1, M / 4096))
-    std::vector<double> sc[3], ss[3];
-};
-inline int plan_stride(int M) { return std::max(1, M / 4096); }
-
-bool grid_plan_from_stats(const MeshStats &ms, int M, int naxes, GridHost &g)
-{
-    g.naxes = naxes;
-    double *ext_lo = g.ext_lo, *ext_hi = g.ext_hi, *ncell = g.ncell;
-    for (int k = 0; k < naxes; ++k) {
-        const double lo = ms.lo[k], hi = ms.hi[k], smin = ms.smin[k], smax = ms.smax[k];
-        if (!(hi > lo) || !(smin > 0)) return false;
-        g.logmap[k] = (lo > 0 && smax / smin > 4.0) ? 1 : 0;
-        // typical cell width in the mapped coordinate: median over a sample
-        std::vector<double> w;
-        for (size_t i = 0; i < ms.sc[k].size(); ++i) {
-            const double a = ms.sc[k][i] - 0.5 * ms.ss[k][i], b = ms.sc[k][i] + 0.5 * ms.ss[k][i];
-            w.push_back(g.logmap[k] ? std::log(b) - std::log(std::max(a, 1e-300)) : b - a);
-        }
-        if (w.empty()) return false;
-        // bucket width = a small typical cell (lower quartile): in a mesh with two refinement levels the fine cells,
-        // where the photons are, then get buckets of their own size instead of lists of nine
-        std::nth_element(w.begin(), w.begin() + w.size() / 4, w.end());
-        const double med = w[w.size() / 4];
-        ext_lo[k] = g.logmap[k] ? std::log(lo) : lo;
-        ext_hi[k] = g.logmap[k] ? std::log(hi) : hi;
-        ncell[k] = std::max(1.0, (ext_hi[k] - ext_lo[k]) / med);
-    }
-    double prod = 1;
-    for (int k = 0; k < naxes; ++k) prod *= ncell[k];
-    const double target = std::min(std::max(4.0 * (double)M, 1.0), 16777216.0);
-    g.f0 = (prod > target) ? std::pow(target / prod, 1.0 / naxes) : 1.0;
-    return true;
-}
-
-bool grid_plan(const mcrat_hip_hydro *h, int naxes, GridHost &g)
-{
-    const int M = h->num_elements;
-    const double *c[3] = {h->r0, h->r1, h->r2};
-    const double *s[3] = {h->r0_size, h->r1_size, h->r2_size};
-    MeshStats ms;
-    for (int k = 0; k < naxes; ++k) {
-        double lo = INFINITY, hi = -INFINITY, smin = INFINITY, smax = 0;
-        for (int i = 0; i < M; ++i) {
-            lo = std::min(lo, c[k][i] - 0.5 * s[k][i]);
-            hi = std::max(hi, c[k][i] + 0.5 * s[k][i]);
-            smin = std::min(smin, s[k][i]);
-            smax = std::max(smax, s[k][i]);
-        }
-        ms.lo[k] = lo; ms.hi[k] = hi; ms.smin[k] = smin; ms.smax[k] = smax;
-        for (int i = 0; i < M; i += plan_stride(M)) { ms.sc[k].push_back(c[k][i]); ms.ss[k].push_back(s[k][i]); }
-    }
-    return grid_plan_from_stats(ms, M, naxes, g);
-}
-
-// the bucket grid for scale factor f; returns the number of buckets
-long long grid_dims(GridHost &g, int naxes, double f)
-{
-    long long nb = 1;
-    for (int k = 0; k < 3; ++k) {
-        g.dim[k] = 1; g.org[k] = 0; g.inv[k] = 0;
-        if (k < naxes) {
-            // buckets of about one cell, shifted by half a bucket against the mesh: on a regular mesh a bucket then
-            // straddles 2 cells per axis (4 in 2-D); aligned buckets would each touch 3 per axis because cell faces lie
-            // on bucket faces
-            const int nbk = (int)std::max(1.0, std::min(65536.0, std::floor(g.ncell[k] * f)));
-            const double width = (g.ext_hi[k] - g.ext_lo[k]) / nbk;
-            g.dim[k] = nbk + 1;
-            g.org[k] = g.ext_lo[k] - 0.5 * width;
-            g.inv[k] = 1.0 / width;
-        }
-        nb *= g.dim[k];
-    }
-    return nb;
-}
-
-// the host build (MCRAT_HIP_HOST_GRID=1): the cross-check of grid_build.hip
-bool build_grid(const mcrat_hip_hydro *h, int naxes, GridHost &g)
-{
-    const int M = h->num_elements;
-    const double *c[3] = {h->r0, h->r1, h->r2};
-    const double *s[3] = {h->r0_size, h->r1_size, h->r2_size};
-    if (!grid_plan(h, naxes, g)) return false;
-    double f = g.f0;
-
-    for (int attempt = 0; attempt < 12; ++attempt, f *= 0.5) {
-        const long long nb = grid_dims(g, naxes, f);
-        std::vector<long long> count((size_t)nb + 1, 0);
-        auto range = [&](int i, int k, int &b0, int &b1) {
-            const double m = 1e-9 * (std::fabs(c[k][i]) + s[k][i]);
-            double a = c[k][i] - 0.5 * s[k][i] - m, b = c[k][i] + 0.5 * s[k][i] + m;
-            if (g.logmap[k] && a <= 0) a = 1e-300;
-            b0 = bucket_of(a, g.logmap[k], g.org[k], g.inv[k], g.dim[k]);
-            b1 = bucket_of(b, g.logmap[k], g.org[k], g.inv[k], g.dim[k]);
-        };
-        long long total = 0;
-        for (int i = 0; i < M; ++i) {
-            int lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-            for (int k = 0; k < naxes; ++k) range(i, k, lo[k], hi[k]);
-            for (int z = lo[2]; z <= hi[2]; ++z)
-                for (int y = lo[1]; y <= hi[1]; ++y)
-                    for (int x = lo[0]; x <= hi[0]; ++x) count[((size_t)z * g.dim[1] + y) * g.dim[0] + x + 1]++;
-            total += (long long)(hi[0] - lo[0] + 1) * (hi[1] - lo[1] + 1) * (hi[2] - lo[2] + 1);
-            if (total > 64LL * M + 1024) break;
-        }
-        if (total > 64LL * M + 1024) continue;   // too fine for this mesh: coarsen and retry
-        if (total > 2000000000LL) continue;
-        for (size_t b = 0; b < (size_t)nb; ++b) count[b + 1] += count[b];
-        g.start.resize((size_t)nb + 1);
-        for (size_t b = 0; b <= (size_t)nb; ++b) g.start[b] = (int)count[b];
-        if (getenv("MCRAT_HIP_VERBOSE"))
-            fprintf(stderr, "mcrat_hip: cell-lookup grid %d x %d x %d buckets, %lld entries for %d cells (%.2f per bucket)\n",
-                    g.dim[0], g.dim[1], g.dim[2], total, M, (double)total / (double)nb);
-        g.cells.assign((size_t)total, -1);
-        std::vector<int> fill(g.start.begin(), g.start.end() - 1);
-        for (int i = 0; i < M; ++i) {
-            int lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-            for (int k = 0; k < naxes; ++k) range(i, k, lo[k], hi[k]);
-            for (int z = lo[2]; z <= hi[2]; ++z)
-                for (int y = lo[1]; y <= hi[1]; ++y)
-                    for (int x = lo[0]; x <= hi[0]; ++x) g.cells[(size_t)fill[((size_t)z * g.dim[1] + y) * g.dim[0] + x]++] = i;
-        }
-        if (nb > (long long)GRID_CODE_BUCKET_MASK) continue;      // bucket codes keep 27 bits for the index
-        // hints: an octant of a bucket gets the entry whose cell is the ONLY one reaching into the octant's interior
-        // (extents shrunk by the 1e-9 margin the lists were widened by, so cells that merely abut do not count)
-        g.hints.assign((size_t)nb, 0);
-        const int nocts = 1 << naxes;
-        auto mapped = [&](double x, int k) { return g.logmap[k] ? std::log(std::max(x, 1e-300)) : x; };
-        for (long long b = 0; b < nb; ++b) {
-            int bi[3] = {(int)(b % g.dim[0]), (int)((b / g.dim[0]) % g.dim[1]), (int)(b / ((long long)g.dim[0] * g.dim[1]))};
-            const int e0 = g.start[(size_t)b], n = g.start[(size_t)b + 1] - e0;
-            unsigned h = 0;
-            for (int o = 0; o < 8; ++o) {
-                unsigned pick = GRID_NO_HINT;
-                if (o < nocts) {
-                    int found = 0;
-                    for (int e = 0; e < n && found < 2; ++e) {
-                        const int ci = g.cells[(size_t)e0 + e];
-                        bool reaches = true;
-                        for (int k = 0; k < naxes && reaches; ++k) {
-                            const double w = 1.0 / g.inv[k];
-                            const double olo = g.org[k] + (bi[k] + 0.5 * ((o >> k) & 1)) * w, ohi = olo + 0.5 * w;
-                            const double m = 1e-9 * (std::fabs(c[k][ci]) + s[k][ci]);
-                            const double clo = mapped(c[k][ci] - 0.5 * s[k][ci] + m, k), chi = mapped(c[k][ci] + 0.5 * s[k][ci] - m, k);
-                            reaches = (clo < ohi) && (chi > olo);
-                        }
-                        if (reaches) { found += 1; if (e < (int)GRID_NO_HINT) pick = (unsigned)e; else found = 2; }
-                    }
-                    if (found != 1) pick = GRID_NO_HINT;
-                }
-                h |= pick << (4 * o);
-            }
-            g.hints[(size_t)b] = h;
-        }
-        if (getenv("MCRAT_HIP_VERBOSE")) {
-            long long hinted = 0;
-            for (long long b = 0; b < nb; ++b)
-                for (int o = 0; o < nocts; ++o) hinted += ((g.hints[(size_t)b] >> (4 * o)) & 15u) != GRID_NO_HINT;
-            fprintf(stderr, "mcrat_hip: %.1f %% of the bucket octants have a single-cell hint\n", 100.0 * hinted / ((double)nb * nocts));
-        }
-        return true;
-    }
-    return false;
-}
-
-}  // namespace
+// (the host's rules -- the bucket grid's plan and its host build, the buffers' layouts, an ingest's slab and box table -- are hydro_plan.hpp)
 
 static void apply_hot_table(mcrat_hip_ctx *c)
 {
@@ -726,213 +541,243 @@ static int view_refuses(mcrat_hip_ctx *c, const char *what)
     return MCRAT_HIP_ESTATE;
 }
 
-// The frame's per-cell records and cell-lookup grid.  h == nullptr (the product path): from the device columns c->hcol,
-// on the device -- stage_cells_kernel (ingest.hip) + grid_build.hip; the host only plans the bucket grid from the mesh
-// statistics the kernel reduces.  h != nullptr (MCRAT_HIP_HOST_GRID=1): staging loop and grid build on the host, the
-// cross-check of the device path (tests/test_gpu_parity.py).
-static int stage_hydro(mcrat_hip_ctx *c, const mcrat_hip_hydro *h, int M, const double *dom0, const double *dom1, const double *dom2)
+// Staging a frame: its per-cell records and its cell-lookup grid into c->hy_buf and c->grid_buf, then c->hy.  The product path takes the device
+// columns c->hcol and works on the device -- stage_cells_kernel (ingest.hip) + grid_build.hip; the host only plans the bucket grid from the mesh
+// statistics the kernel reduces.  With the caller's host columns (MCRAT_HIP_HOST_GRID=1) the staging loop and the grid build run on the host: the
+// cross-check of the device path (tests/test_gpu_parity.py).  Each is a sequence of steps over one HydroStage (stage_hydro_device, stage_hydro_host);
+// they share the buffers' steps and end in the same publish_grid and finish_frame.
+namespace {
+
+struct HydroStage {
+    mcrat_hip_ctx *c;
+    int M, naxes;
+    CellLayout cells{};               // c->hy_buf
+    GridLayout grid{};                // c->grid_buf
+    GridScale scale{};                // device build: the grid up to its scale factor, from the staging kernel's statistics
+    GridPlan plan{};                  // the grid that is built, with its buckets and list entries
+    long long nb = 0, entries = 0;
+    bool any_hot = false;             // a cell has T >= 1e7 K: the frame gets the k2e column
+    template <class T> T *cell_at(size_t o) const { return reinterpret_cast<T *>(static_cast<char *>(c->hy_buf) + o); }
+    template <class T> T *grid_at(size_t o) const { return reinterpret_cast<T *>(static_cast<char *>(c->grid_buf) + o); }
+};
+// what the host build keeps between its steps: the caller's columns, the grid, and the per-cell buffer's image (the bucket lists copy from it)
+struct HostFrame {
+    const mcrat_hip_hydro *h;
+    GridHost grid;
+    std::vector<char> image;
+};
+
+// host build: the whole grid, before anything of the context changes (a mesh it refuses leaves the buffers alone)
+int host_build_grid(HydroStage &s, HostFrame &hf)
 {
-    if (c->hydro_owner) { c->last_error = "stage_hydro on a context that reads another one's frame"; return MCRAT_HIP_ESTATE; }   // (ensure_hcol released it)
-    const bool three = c->kc.dimensions == DIM_THREE, two = c->kc.dimensions == DIM_TWO;
-    const int naxes = three ? 3 : 2;
-    const bool host_grid = h != nullptr;
-    GridHost g;
-    if (host_grid && !build_grid(h, naxes, g)) { c->last_error = "cell-lookup grid: degenerate mesh"; return MCRAT_HIP_EINVAL; }
-    bool any_hot = false;
-    if (host_grid)
-        for (int i = 0; i < M; ++i) any_hot = any_hot || (h->temp[i] >= 1e7);
+    const mcrat_hip_hydro *h = hf.h;
+    const double *ctr[3] = {h->r0, h->r1, h->r2}, *size[3] = {h->r0_size, h->r1_size, h->r2_size};
+    if (!build_grid(ctr, size, s.M, s.naxes, hf.grid)) { s.c->last_error = "cell-lookup grid: degenerate mesh"; return MCRAT_HIP_EINVAL; }
+    s.plan = hf.grid.plan; s.nb = hf.grid.nb; s.entries = (long long)hf.grid.cells.size();
+    for (int i = 0; i < s.M; ++i) s.any_hot = s.any_hot || (h->temp[i] >= 1e7);
+    return MCRAT_HIP_OK;
+}
 
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    const size_t o_geom = take(sizeof(CellGeom) * M);
-    const size_t o_geom2 = three ? take(sizeof(CellGeom2) * M) : 0;
-    const size_t o_fluid = take(sizeof(CellFluid) * M);
-    const size_t o_temp = take(sizeof(double) * M);
-    const size_t o_fc = !two ? take(sizeof(double) * M) : 0;
-    const size_t o_k2e = (any_hot || !host_grid) ? take(sizeof(double) * M) : 0;     // device path: known only after staging
-    const size_t o_gamma = take(sizeof(double) * M);
-    const size_t total = off;
-
+int ensure_cell_buffer(HydroStage &s, bool reserve_k2e)
+{
+    mcrat_hip_ctx *c = s.c;
+    s.cells = cell_layout(c->kc.dimensions, s.M, reserve_k2e);
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->hy_buf && c->hy_bytes < total) { HIPCHK(c, hipFree(c->hy_buf)); c->hy_buf = nullptr; c->hy_bytes = 0; }
-    if (!c->hy_buf) { HIPCHK(c, hipMalloc(&c->hy_buf, total)); c->hy_bytes = total; }
-    char *base = static_cast<char *>(c->hy_buf);
+    return ensure_device_bytes(c, &c->hy_buf, &c->hy_bytes, s.cells.total);
+}
 
-    if (!host_grid) {
-        const int nblk = stage_cells_blocks(M), stride = plan_stride(M), nsamp = (M + stride - 1) / stride;
-        const size_t scratch_bytes = sizeof(StagePartial) * (size_t)nblk + sizeof(double) * 2 * naxes * (size_t)nsamp;
-        int rc = ensure_aos(c, scratch_bytes);
-        if (rc) return rc;
-        StagePartial *d_part = static_cast<StagePartial *>(c->aos_buf);
-        double *d_samp = reinterpret_cast<double *>(d_part + nblk);
-        HIPCHK(c, launch_stage_cells(c->kc.dimensions, c->kc.geometry, c->hcol, M, reinterpret_cast<CellGeom *>(base + o_geom),
-                                     three ? reinterpret_cast<CellGeom2 *>(base + o_geom2) : nullptr, reinterpret_cast<CellFluid *>(base + o_fluid),
-                                     !two ? reinterpret_cast<double *>(base + o_fc) : nullptr, reinterpret_cast<double *>(base + o_temp),
-                                     reinterpret_cast<double *>(base + o_gamma), d_part, d_samp, stride, nsamp, c->stream));
-        std::vector<char> hs(scratch_bytes);
-        HIPCHK(c, hipMemcpyAsync(hs.data(), c->aos_buf, scratch_bytes, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        const StagePartial *part = reinterpret_cast<const StagePartial *>(hs.data());
-        const double *samp = reinterpret_cast<const double *>(part + nblk);
-        MeshStats ms;
-        for (int k = 0; k < naxes; ++k) {
-            double lo = INFINITY, hi = -INFINITY, smin = INFINITY, smax = 0;
-            for (int b = 0; b < nblk; ++b) {
-                lo = std::min(lo, part[b].lo[k]);
-                hi = std::max(hi, part[b].hi[k]);
-                smin = (part[b].smin[k] < smin || !(part[b].smin[k] == part[b].smin[k])) ? part[b].smin[k] : smin;
-                smax = std::max(smax, part[b].smax[k]);
-            }
-            ms.lo[k] = lo; ms.hi[k] = hi; ms.smin[k] = smin; ms.smax[k] = smax;
-            ms.sc[k].assign(samp + (size_t)(2 * k) * nsamp, samp + (size_t)(2 * k + 1) * nsamp);
-            ms.ss[k].assign(samp + (size_t)(2 * k + 1) * nsamp, samp + (size_t)(2 * k + 2) * nsamp);
-        }
-        for (int b = 0; b < nblk; ++b) any_hot = any_hot || part[b].any_hot;
-        if (!grid_plan_from_stats(ms, M, naxes, g)) { c->last_error = "cell-lookup grid: degenerate mesh"; return MCRAT_HIP_EINVAL; }
-    }
+// device build: the cells' records from c->hcol, and from the statistics the kernel reduced on the way the grid up to its scale
+int stage_cells_device(HydroStage &s)
+{
+    mcrat_hip_ctx *c = s.c;
+    const CellLayout &l = s.cells;
+    const int M = s.M, nblk = stage_cells_blocks(M), stride = plan_stride(M), nsamp = (M + stride - 1) / stride;
+    const size_t scratch_bytes = sizeof(StagePartial) * (size_t)nblk + sizeof(double) * 2 * s.naxes * (size_t)nsamp;
+    int rc = ensure_aos(c, scratch_bytes);
+    if (rc) return rc;
+    StagePartial *d_part = static_cast<StagePartial *>(c->aos_buf);
+    double *d_samp = reinterpret_cast<double *>(d_part + nblk);
+    HIPCHK(c, launch_stage_cells(c->kc.dimensions, c->kc.geometry, c->hcol, M, s.cell_at<CellGeom>(l.geom), l.has_geom2 ? s.cell_at<CellGeom2>(l.geom2) : nullptr,
+                                 s.cell_at<CellFluid>(l.fluid), l.has_fluid_c ? s.cell_at<double>(l.fluid_c) : nullptr, s.cell_at<double>(l.temp),
+                                 s.cell_at<double>(l.gamma), d_part, d_samp, stride, nsamp, c->stream));
+    std::vector<char> hs(scratch_bytes);
+    HIPCHK(c, hipMemcpyAsync(hs.data(), c->aos_buf, scratch_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const StagePartial *part = reinterpret_cast<const StagePartial *>(hs.data());
+    const MeshStats ms = mesh_stats_from_partials(part, nblk, reinterpret_cast<const double *>(part + nblk), nsamp, s.naxes, &s.any_hot);
+    if (!grid_plan_from_stats(ms, M, s.naxes, s.scale)) { c->last_error = "cell-lookup grid: degenerate mesh"; return MCRAT_HIP_EINVAL; }
+    return MCRAT_HIP_OK;
+}
 
-    std::vector<char> host(host_grid ? total : 0, 0);
-    CellGeom *geom = reinterpret_cast<CellGeom *>(host.data() + o_geom);
-    CellFluid *fluid = reinterpret_cast<CellFluid *>(host.data() + o_fluid);
-    // the per-cell part of hydroVectorToCartesian (geometry.c:189-253) is applied here, once per frame; the device adds the
-    // photon-azimuth part (physics.hpp, cell_beta)
-    double *fc = !two ? reinterpret_cast<double *>(host.data() + o_fc) : nullptr;
-    const int geomv = c->kc.geometry;
-    for (int i = 0; host_grid && i < M; ++i) {
+// host build: the same records from the caller's columns, as the buffer's image, and up
+int stage_cells_host(HydroStage &s, HostFrame &hf)
+{
+    mcrat_hip_ctx *c = s.c;
+    const mcrat_hip_hydro *h = hf.h;
+    const CellLayout &l = s.cells;
+    const int M = s.M;
+    hf.image.assign(l.total, 0);
+    char *host = hf.image.data();
+    CellGeom *geom = reinterpret_cast<CellGeom *>(host + l.geom);
+    CellFluid *fluid = reinterpret_cast<CellFluid *>(host + l.fluid);
+    double *fc = l.has_fluid_c ? reinterpret_cast<double *>(host + l.fluid_c) : nullptr;
+    for (int i = 0; i < M; ++i) {
         geom[i].c0 = h->r0[i]; geom[i].c1 = h->r1[i]; geom[i].s0 = h->r0_size[i]; geom[i].s1 = h->r1_size[i];
-        const double v0 = h->v0[i], v1 = h->v1[i], v2 = two ? 0.0 : h->v2[i];
-        double fa, fb, fcv = 0.0;
-        if (!three) {
-            if (geomv == GEOM_SPHERICAL) {
-                const double th = h->r1[i];
-                fa = v0 * std::sin(th) + v1 * std::cos(th);
-                fb = v0 * std::cos(th) - v1 * std::sin(th);
-            } else {
-                fa = v0;
-                fb = v1;
-            }
-            fcv = v2;
-        } else if (geomv == GEOM_CARTESIAN) {
-            fa = v0; fb = v1; fcv = v2;
-        } else if (geomv == GEOM_SPHERICAL) {
-            const double x1 = h->r1[i], x2 = h->r2[i];
-            fa = v0 * std::sin(x1) * std::cos(x2) + v1 * std::cos(x1) * std::cos(x2) - v2 * std::sin(x2);
-            fb = v0 * std::sin(x1) * std::sin(x2) + v1 * std::cos(x1) * std::sin(x2) + v2 * std::cos(x2);
-            fcv = v0 * std::cos(x1) - v1 * std::sin(x1);
-        } else {   // POLAR
-            const double x1 = h->r1[i];
-            fa = v0 * std::cos(x1) - v1 * std::sin(x1);
-            fb = v0 * std::sin(x1) + v1 * std::cos(x1);
-            fcv = v2;
-        }
-        if (fc) fc[i] = fcv;
-        cell_staged_operands(fa, fb, fcv, h->gamma[i], h->dens_lab[i], fluid[i]);
+        double v[3];
+        cell_velocity_staged(c->kc.dimensions, c->kc.geometry, h->v0[i], h->v1[i], l.has_fluid_c ? h->v2[i] : 0.0, h->r1[i], l.has_geom2 ? h->r2[i] : 0.0, v);
+        if (fc) fc[i] = v[2];
+        cell_staged_operands(v[0], v[1], v[2], h->gamma[i], h->dens_lab[i], fluid[i]);
     }
-    if (host_grid) {
-        if (three) {
-            CellGeom2 *g2 = reinterpret_cast<CellGeom2 *>(host.data() + o_geom2);
-            for (int i = 0; i < M; ++i) { g2[i].c2 = h->r2[i]; g2[i].s2 = h->r2_size[i]; }
-        }
-        memcpy(host.data() + o_temp, h->temp, sizeof(double) * M);
-        memcpy(host.data() + o_gamma, h->gamma, sizeof(double) * M);
-        HIPCHK(c, hipMemcpy(c->hy_buf, host.data(), total, hipMemcpyHostToDevice));
+    if (l.has_geom2) {
+        CellGeom2 *g2 = reinterpret_cast<CellGeom2 *>(host + l.geom2);
+        for (int i = 0; i < M; ++i) { g2[i].c2 = h->r2[i]; g2[i].s2 = h->r2_size[i]; }
     }
+    memcpy(host + l.temp, h->temp, sizeof(double) * M);
+    memcpy(host + l.gamma, h->gamma, sizeof(double) * M);
+    HIPCHK(c, hipMemcpy(c->hy_buf, host, l.total, hipMemcpyHostToDevice));
+    return MCRAT_HIP_OK;
+}
 
-    HydroDev &hy = c->hy;
-    hy.geom = reinterpret_cast<const CellGeom *>(base + o_geom);
-    hy.geom2 = three ? reinterpret_cast<const CellGeom2 *>(base + o_geom2) : nullptr;
-    hy.fluid = reinterpret_cast<const CellFluid *>(base + o_fluid);
-    hy.temp = reinterpret_cast<const double *>(base + o_temp);
-    hy.fluid_c = !two ? reinterpret_cast<const double *>(base + o_fc) : nullptr;
-    hy.k2e = any_hot ? reinterpret_cast<const double *>(base + o_k2e) : nullptr;
-    hy.gamma = reinterpret_cast<const double *>(base + o_gamma);
-    hy.M = M;
+void publish_cells(HydroStage &s, const double *dom0, const double *dom1, const double *dom2)
+{
+    const CellLayout &l = s.cells;
+    HydroDev &hy = s.c->hy;
+    hy.geom = s.cell_at<const CellGeom>(l.geom);
+    hy.geom2 = l.has_geom2 ? s.cell_at<const CellGeom2>(l.geom2) : nullptr;
+    hy.fluid = s.cell_at<const CellFluid>(l.fluid);
+    hy.temp = s.cell_at<const double>(l.temp);
+    hy.fluid_c = l.has_fluid_c ? s.cell_at<const double>(l.fluid_c) : nullptr;
+    hy.k2e = s.any_hot ? s.cell_at<const double>(l.k2e) : nullptr;
+    hy.gamma = s.cell_at<const double>(l.gamma);
+    hy.M = s.M;
     hy.dom0[0] = dom0[0]; hy.dom0[1] = dom0[1];
     hy.dom1[0] = dom1[0]; hy.dom1[1] = dom1[1];
     hy.dom2[0] = dom2[0]; hy.dom2[1] = dom2[1];
+}
 
-    // ---- the grid
-    long long nb = 0, entries_total = 0;
-    if (host_grid) {
-        nb = (long long)g.start.size() - 1;
-        entries_total = (long long)g.cells.size();
-    } else {
-        { int rc = ensure_counts(c, 1); if (rc) return rc; }
-        double f = g.f0;
-        bool ok = false;
-        for (int attempt = 0; attempt < 12 && !ok; ++attempt, f *= 0.5) {
-            nb = grid_dims(g, naxes, f);
-            if (nb > (long long)GRID_CODE_BUCKET_MASK) continue;              // bucket codes keep 27 bits for the index
-            { int rc = ensure_counts(c, (size_t)nb); if (rc) return rc; }
-            GridPlan plan;
-            for (int k = 0; k < 3; ++k) { plan.org[k] = g.org[k]; plan.inv[k] = g.inv[k]; plan.dim[k] = g.dim[k]; plan.logmap[k] = g.logmap[k]; }
-            plan.naxes = naxes;
-            HIPCHK(c, grid_count(plan, hy.geom, hy.geom2, M, c->grid_count, nb, c->d_grid_total, c->stream));
-            unsigned long long tot = 0;
-            HIPCHK(c, hipMemcpyAsync(&tot, c->d_grid_total, sizeof tot, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (tot > (unsigned long long)(64LL * M + 1024) || tot > 2000000000ull) continue;   // too fine for this mesh: coarsen and retry
-            entries_total = (long long)tot;
-            ok = true;
-            if (getenv("MCRAT_HIP_VERBOSE"))
-                fprintf(stderr, "mcrat_hip: cell-lookup grid %d x %d x %d buckets, %lld entries for %d cells (%.2f per bucket), built on the device\n",
-                        g.dim[0], g.dim[1], g.dim[2], entries_total, M, (double)entries_total / (double)nb);
-        }
-        if (!ok) { c->last_error = "cell-lookup grid: no bucket size fits this mesh"; return MCRAT_HIP_EINVAL; }
+// device build: the entries a plan's bucket lists would hold (grid_build.hip counts them, per bucket too: c->grid_count)
+int count_grid_entries(HydroStage &s, const GridPlan &plan, long long nb, unsigned long long *total)
+{
+    mcrat_hip_ctx *c = s.c;
+    { int rc = ensure_counts(c, (size_t)nb); if (rc) return rc; }
+    HIPCHK(c, grid_count(plan, c->hy.geom, c->hy.geom2, s.M, c->grid_count, nb, c->d_grid_total, c->stream));
+    HIPCHK(c, hipMemcpyAsync(total, c->d_grid_total, sizeof *total, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MCRAT_HIP_OK;
+}
+int choose_scale_device(HydroStage &s)
+{
+    mcrat_hip_ctx *c = s.c;
+    int rc = ensure_counts(c, 1);
+    if (rc) return rc;
+    const GridChoice ch = choose_grid_scale(s.scale, s.M, [&](const GridPlan &plan, long long nb, long long) {
+        unsigned long long total = 0;
+        rc = count_grid_entries(s, plan, nb, &total);
+        return rc ? -1LL : (long long)std::min(total, 0x7fffffffffffffffull);
+    });
+    if (ch.result == GRID_SCALE_ABANDONED) return rc;
+    if (ch.result != GRID_SCALE_OK) { c->last_error = "cell-lookup grid: no bucket size fits this mesh"; return MCRAT_HIP_EINVAL; }
+    s.plan = ch.plan; s.nb = ch.nb; s.entries = ch.entries;
+    if (getenv("MCRAT_HIP_VERBOSE"))
+        fprintf(stderr, "mcrat_hip: cell-lookup grid %d x %d x %d buckets, %lld entries for %d cells (%.2f per bucket), built on the device\n",
+                s.plan.dim[0], s.plan.dim[1], s.plan.dim[2], s.entries, s.M, (double)s.entries / (double)s.nb);
+    return MCRAT_HIP_OK;
+}
+
+int ensure_grid_buffer(HydroStage &s)
+{
+    s.grid = grid_layout(s.nb, s.entries, grid_scan_scratch_ints(s.nb));
+    return ensure_device_bytes(s.c, &s.c->grid_buf, &s.c->grid_bytes, s.grid.total);
+}
+
+int build_grid_device(HydroStage &s)
+{
+    mcrat_hip_ctx *c = s.c;
+    const GridLayout &g = s.grid;
+    HIPCHK(c, grid_build(s.plan, c->hy.geom, c->hy.geom2, c->hy.fluid, c->hy.fluid_c, s.M, c->grid_count, s.grid_at<int>(g.start), s.grid_at<int>(g.scan),
+                         s.grid_at<int>(g.entries), s.grid_at<FatCell>(g.cells), s.grid_at<BucketDir>(g.dir), s.nb, s.entries, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MCRAT_HIP_OK;
+}
+
+// host build: the bucket records and the lists -- complete copies of the member cells' records -- as the image of what the lookup reads, and up
+int upload_host_grid(HydroStage &s, const HostFrame &hf)
+{
+    const GridHost &g = hf.grid;
+    const CellGeom *geom = reinterpret_cast<const CellGeom *>(hf.image.data() + s.cells.geom);
+    const CellFluid *fluid = reinterpret_cast<const CellFluid *>(hf.image.data() + s.cells.fluid);
+    const bool three = s.cells.has_geom2;
+    std::vector<char> gh(s.grid.start, 0);
+    BucketDir *dir = reinterpret_cast<BucketDir *>(gh.data() + s.grid.dir);
+    for (size_t b = 0; b < (size_t)s.nb; ++b) {
+        dir[b].e0 = g.start[b]; dir[b].n = g.start[b + 1] - g.start[b]; dir[b].hints = g.hints[b]; dir[b].pad = 0;
     }
-    size_t goff = 0;
-    auto gtake = [&](size_t bytes) { size_t o = goff; goff = align_up(goff + bytes, 256); return o; };
-    const size_t o_dir = gtake(sizeof(BucketDir) * (size_t)nb);
-    const size_t o_cells = gtake(sizeof(FatCell) * std::max<size_t>((size_t)entries_total, 1));
-    const size_t o_start = gtake(sizeof(int) * ((size_t)nb + 1));                // device build only: scratch
-    const size_t o_scan = gtake(sizeof(int) * grid_scan_scratch_ints(nb));
-    const size_t o_entries = gtake(sizeof(int) * std::max<size_t>((size_t)entries_total, 1));
-    const size_t gtotal = goff;
-    if (c->grid_buf && c->grid_bytes < gtotal) { HIPCHK(c, hipFree(c->grid_buf)); c->grid_buf = nullptr; c->grid_bytes = 0; }
-    if (!c->grid_buf) { HIPCHK(c, hipMalloc(&c->grid_buf, gtotal)); c->grid_bytes = gtotal; }
-    char *gbase = static_cast<char *>(c->grid_buf);
-    if (host_grid) {
-        std::vector<char> gh(o_start, 0);
-        BucketDir *dir = reinterpret_cast<BucketDir *>(gh.data() + o_dir);
-        for (size_t b = 0; b < (size_t)nb; ++b) {
-            dir[b].e0 = g.start[b]; dir[b].n = g.start[b + 1] - g.start[b]; dir[b].hints = g.hints[b]; dir[b].pad = 0;
-        }
-        // bucket lists as complete copies of the member cells' records (device_types.hpp, FatCell)
-        FatCell *fat = reinterpret_cast<FatCell *>(gh.data() + o_cells);
-        for (size_t e = 0; e < g.cells.size(); ++e) {
-            const int ci = g.cells[e];
-            FatCell &f = fat[e];
-            f.c0 = geom[ci].c0; f.c1 = geom[ci].c1; f.s0 = geom[ci].s0; f.s1 = geom[ci].s1;
-            f.a = fluid[ci].a; f.b = fluid[ci].b; f.c = fluid[ci].c; f.w = fluid[ci].w;
-            f.nsig = fluid[ci].nsig; f.gam = fluid[ci].gam;
-            f.c2 = three ? h->r2[ci] : 0.0; f.s2 = three ? h->r2_size[ci] : 0.0;
-            f.cell = ci; f.pad = 0; f.pad2[0] = f.pad2[1] = f.pad2[2] = 0.0;
-        }
-        HIPCHK(c, hipMemcpy(gbase, gh.data(), o_start, hipMemcpyHostToDevice));
-    } else {
-        GridPlan plan;
-        for (int k = 0; k < 3; ++k) { plan.org[k] = g.org[k]; plan.inv[k] = g.inv[k]; plan.dim[k] = g.dim[k]; plan.logmap[k] = g.logmap[k]; }
-        plan.naxes = naxes;
-        HIPCHK(c, grid_build(plan, hy.geom, hy.geom2, hy.fluid, hy.fluid_c, M, c->grid_count, reinterpret_cast<int *>(gbase + o_start),
-                             reinterpret_cast<int *>(gbase + o_scan), reinterpret_cast<int *>(gbase + o_entries),
-                             reinterpret_cast<FatCell *>(gbase + o_cells), reinterpret_cast<BucketDir *>(gbase + o_dir), nb, entries_total, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+    FatCell *fat = reinterpret_cast<FatCell *>(gh.data() + s.grid.cells);
+    for (size_t e = 0; e < g.cells.size(); ++e) {
+        const int ci = g.cells[e];
+        fat[e] = fat_cell(geom[ci], fluid[ci], three ? hf.h->r2[ci] : 0.0, three ? hf.h->r2_size[ci] : 0.0, ci);
     }
-    hy.grid.dir = reinterpret_cast<const BucketDir *>(gbase + o_dir);
-    hy.grid.cells = reinterpret_cast<const FatCell *>(gbase + o_cells);
-    for (int k = 0; k < 3; ++k) {
-        hy.grid.org[k] = g.org[k]; hy.grid.inv[k] = g.inv[k]; hy.grid.dim[k] = g.dim[k]; hy.grid.logmap[k] = g.logmap[k];
-    }
-    hy.grid.naxes = g.naxes;
-    apply_hot_table(c);
-    if (any_hot) {
-        HIPCHK(c, launch_k2e(hy.temp, reinterpret_cast<double *>(base + o_k2e), M, c->stream));
+    HIPCHK(s.c, hipMemcpy(s.c->grid_buf, gh.data(), s.grid.start, hipMemcpyHostToDevice));
+    return MCRAT_HIP_OK;
+}
+
+void publish_grid(HydroStage &s)
+{
+    HydroDev &hy = s.c->hy;
+    hy.grid.dir = s.grid_at<const BucketDir>(s.grid.dir);
+    hy.grid.cells = s.grid_at<const FatCell>(s.grid.cells);
+    grid_plan_to_dev(s.plan, hy.grid);
+    apply_hot_table(s.c);
+}
+
+// exp(x) K_2(x) of the hot cells, and the frame is there
+int finish_frame(HydroStage &s)
+{
+    mcrat_hip_ctx *c = s.c;
+    if (s.any_hot) {
+        HIPCHK(c, launch_k2e(c->hy.temp, s.cell_at<double>(s.cells.k2e), s.M, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     c->have_hydro = true;
     drop_graph(c);
     sync_views(c);
     return MCRAT_HIP_OK;
+}
+
+}  // namespace
+
+// the product path: everything on the device, from the columns in c->hcol
+static int stage_hydro_device(HydroStage &s, const double *dom0, const double *dom1, const double *dom2)
+{
+    int rc;
+    if ((rc = ensure_cell_buffer(s, true))) return rc;          // whether a cell is hot is known only after the staging: k2e is always reserved
+    if ((rc = stage_cells_device(s))) return rc;
+    publish_cells(s, dom0, dom1, dom2);
+    if ((rc = choose_scale_device(s))) return rc;
+    if ((rc = ensure_grid_buffer(s))) return rc;
+    if ((rc = build_grid_device(s))) return rc;
+    publish_grid(s);
+    return finish_frame(s);
+}
+// the cross-check (MCRAT_HIP_HOST_GRID=1): staging loop and grid build on the host, from the caller's columns h
+static int stage_hydro_host(HydroStage &s, const mcrat_hip_hydro *h, const double *dom0, const double *dom1, const double *dom2)
+{
+    HostFrame hf{h};
+    int rc;
+    if ((rc = host_build_grid(s, hf))) return rc;
+    if ((rc = ensure_cell_buffer(s, s.any_hot))) return rc;
+    if ((rc = stage_cells_host(s, hf))) return rc;
+    publish_cells(s, dom0, dom1, dom2);
+    if ((rc = ensure_grid_buffer(s))) return rc;
+    if ((rc = upload_host_grid(s, hf))) return rc;
+    publish_grid(s);
+    return finish_frame(s);
+}
+static int stage_hydro(mcrat_hip_ctx *c, const mcrat_hip_hydro *h, int M, const double *dom0, const double *dom1, const double *dom2)
+{
+    if (c->hydro_owner) { c->last_error = "stage_hydro on a context that reads another one's frame"; return MCRAT_HIP_ESTATE; }   // (ensure_hcol released it)
+    HydroStage s{c, M, c->kc.dimensions == DIM_THREE ? 3 : 2};
+    return h ? stage_hydro_host(s, h, dom0, dom1, dom2) : stage_hydro_device(s, dom0, dom1, dom2);
 }
 
 // a context that reads another one's staged frame (mcrat_hip_share_hydro) holds that context's pointers: forget them before staging its own
@@ -993,8 +838,7 @@ static int ensure_hcol(mcrat_hip_ctx *c, int M)
     detach_sharers(c, "staged another frame");              // the buffers they point into are about to be rewritten or freed
     const size_t stride = align_up(sizeof(double) * (size_t)M, 256), total = 19 * stride;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->hcol_buf && c->hcol_bytes < total) { HIPCHK(c, hipFree(c->hcol_buf)); c->hcol_buf = nullptr; c->hcol_bytes = 0; }
-    if (!c->hcol_buf) { HIPCHK(c, hipMalloc(&c->hcol_buf, total)); c->hcol_bytes = total; }
+    { int rc = ensure_device_bytes(c, &c->hcol_buf, &c->hcol_bytes, total); if (rc) return rc; }
     char *b = static_cast<char *>(c->hcol_buf);
     double **cols[19] = {&c->hcol.r0, &c->hcol.r1, &c->hcol.r2, &c->hcol.s0, &c->hcol.s1, &c->hcol.s2, &c->hcol.v0, &c->hcol.v1, &c->hcol.v2,
                          &c->hcol.dens, &c->hcol.dens_lab, &c->hcol.pres, &c->hcol.temp, &c->hcol.gamma, &c->hcol.r, &c->hcol.theta,
@@ -1051,29 +895,13 @@ struct RawPacker {
     int upload()
     {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->raw_buf && c->raw_bytes < off) { HIPCHK(c, hipFree(c->raw_buf)); c->raw_buf = nullptr; c->raw_bytes = 0; }
-        if (!c->raw_buf) { HIPCHK(c, hipMalloc(&c->raw_buf, off)); c->raw_bytes = off; }
+        { int rc = ensure_device_bytes(c, &c->raw_buf, &c->raw_bytes, off); if (rc) return rc; }
         for (const auto &it : items)
             if (it.second.first) HIPCHK(c, hipMemcpyAsync(static_cast<char *>(c->raw_buf) + it.first, it.second.first, it.second.second, hipMemcpyHostToDevice, c->stream));
         return MCRAT_HIP_OK;
     }
     template <class T> const T *at(size_t o) const { return reinterpret_cast<const T *>(static_cast<const char *>(c->raw_buf) + o); }
 };
-
-// the slab for one elem_factor (mclib_flash.c:84-85,309 == mclib_pluto.c:1081-1082,1276)
-SlabDev slab_for(const mcrat_hip_ctx *c, const mcrat_hip_slab *s, int elem_factor)
-{
-    SlabDev d{};
-    d.dimensions = c->kc.dimensions; d.geometry = c->kc.geometry; d.ph_inj_switch = s->ph_inj_switch;
-    d.r_inj_095 = 0.95 * s->r_inj;
-    if (s->ph_inj_switch == 0) {
-        d.r_lo = s->min_r - elem_factor * C_LIGHT / s->fps;
-        d.r_hi = s->max_r + elem_factor * C_LIGHT / s->fps;
-        d.th_lo = s->min_theta - 2 * 0.017453292519943295;
-        d.th_hi = s->max_theta + 2 * 0.017453292519943295;
-    }
-    return d;
-}
 
 // the part of getHydroData both readers share: count with a growing elem_factor, scan, write, fill r/theta, overwrite
 // with the analytic outflow, stage
@@ -1094,7 +922,7 @@ int ingest_common(mcrat_hip_ctx *c, long long n_virtual, const mcrat_hip_slab *s
             c->last_error = "hydro ingest: no cell lies in the requested slab for any elem_factor up to 1000 (the reference would not return)";
             return MCRAT_HIP_EINVAL;
         }
-        sd = slab_for(c, slab, elem_factor);
+        sd = slab_for(c->kc.dimensions, c->kc.geometry, slab, elem_factor);
         HIPCHK(c, count(sd));
         HIPCHK(c, hipMemcpyAsync(&total, c->d_grid_total, sizeof total, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1118,9 +946,6 @@ int ingest_common(mcrat_hip_ctx *c, long long n_virtual, const mcrat_hip_slab *s
     if (result) { result->num_elements = M; result->elem_factor = elem_factor; }
     return stage_hydro(c, nullptr, M, slab->r0_domain, slab->r1_domain, slab->r2_domain);
 }
-
-bool slab_ok(const mcrat_hip_slab *s) { return s && s->fps > 0 && (s->ph_inj_switch == 0 || s->ph_inj_switch == 1); }
-bool outflow_ok(const mcrat_hip_outflow *o) { return !o || (o->simulation_type >= MCRAT_HIP_SCIENCE && o->simulation_type <= MCRAT_HIP_STRUCTURED_SPHERICAL_OUTFLOW); }
 
 }  // namespace
 
@@ -1205,65 +1030,15 @@ extern "C" int mcrat_hip_ingest_chombo(mcrat_hip_ctx *c, const mcrat_hip_chombo 
     if (c->parent) return view_refuses(c, "ingest_chombo");
     if (h->num_levels <= 0 || h->num_vars <= 0 || !h->levels || !h->var_names || !h->data) return MCRAT_HIP_EINVAL;
     const bool three = c->kc.dimensions == DIM_THREE;
-    const int nd = three ? 3 : 2, bi = 2 * nd, nl = h->num_levels, nv = h->num_vars;
-    // the box table in the reader's cell numbering, and the per-level coordinate arrays (mclib_pluto.c:446-517)
-    std::vector<ChomboBox> boxes;
-    std::vector<int> level_first_box(nl + 1, 0);
-    std::vector<double> xs[3], dxs[3];
-    long long total = 0;                                         // doubles of all levels: start_displacement (:151-155)
-    for (int i = 0; i < nl; ++i) {
-        const mcrat_hip_chombo_level &L = h->levels[i];
-        if (L.n_boxes < 0 || (L.n_boxes > 0 && (!L.boxes || !L.box_offsets)) || L.data_len < 0 || L.ref_ratio <= 0) return MCRAT_HIP_EINVAL;
-        int ext[3] = {1, 1, 1}, cb[3] = {0, 0, 0};
-        for (int a = 0; a < nd; ++a) {
-            ext[a] = L.prob_domain[nd + a] - L.prob_domain[a] + 1;
-            if (ext[a] <= 0) return MCRAT_HIP_EINVAL;
-            cb[a] = (int)xs[a].size();
-        }
-        for (int j = 0; j < ext[0]; ++j) {
-            const int g = L.prob_domain[0] + j;
-            if (L.logr == 0) { xs[0].push_back(L.dombeg1 + L.dx * (g + 0.5)); dxs[0].push_back(L.dx); }
-            else {
-                xs[0].push_back(L.dombeg1 * 0.5 * (std::exp(L.dx * (g + 1)) + std::exp(L.dx * g)));
-                dxs[0].push_back(L.dombeg1 * (std::exp(L.dx * (g + 1)) - std::exp(L.dx * g)));
-            }
-        }
-        for (int j = 0; j < ext[1]; ++j) { xs[1].push_back(L.dombeg2 + L.dx * L.g_x2stretch * (L.prob_domain[1] + j + 0.5)); dxs[1].push_back(L.dx * L.g_x2stretch); }
-        for (int j = 0; three && j < ext[2]; ++j) { xs[2].push_back(L.dombeg3 + L.dx * L.g_x3stretch * (L.prob_domain[2] + j + 0.5)); dxs[2].push_back(L.dx * L.g_x3stretch); }
-        level_first_box[i] = (int)boxes.size();
-        for (int j = 0; j < L.n_boxes; ++j) {
-            const int *b = L.boxes + (size_t)j * bi;
-            ChomboBox r{};
-            r.level = i;
-            long long ncell = 1;
-            for (int a = 0; a < 3; ++a) {
-                r.lo[a] = a < nd ? b[a] : 0;
-                r.n[a] = a < nd ? b[nd + a] - b[a] + 1 : 1;
-                r.cb[a] = cb[a];
-                // the reader indexes its coordinate arrays with the box's own indices (:541): they must exist
-                if (r.n[a] <= 0 || (a < nd && (r.lo[a] < 0 || r.lo[a] + r.n[a] > ext[a]))) { c->last_error = "PLUTO-Chombo ingest: a box lies outside its level's prob_domain"; return MCRAT_HIP_EINVAL; }
-                ncell *= r.n[a];
-            }
-            r.data_off = total + L.box_offsets[j];
-            r.first_cell = r.data_off / nv;
-            if (L.box_offsets[j] < 0 || L.box_offsets[j] + ncell * nv > L.data_len) { c->last_error = "PLUTO-Chombo ingest: a box's data lies outside its level's data"; return MCRAT_HIP_EINVAL; }
-            if (!boxes.empty() && r.first_cell != boxes.back().first_cell + (long long)boxes.back().n[0] * boxes.back().n[1] * boxes.back().n[2]) {
-                c->last_error = "PLUTO-Chombo ingest: box data do not follow one another in data:offsets order";
-                return MCRAT_HIP_EINVAL;
-            }
-            boxes.push_back(r);
-        }
-        total += L.data_len;
+    const int nd = three ? 3 : 2, nl = h->num_levels;
+    ChomboPlan plan;                                             // the box table and the per-level coordinate arrays (hydro_plan.hpp)
+    if (const char *why = chombo_plan(h, c->kc.dimensions, plan)) {
+        if (*why) c->last_error = why;
+        return MCRAT_HIP_EINVAL;
     }
-    level_first_box[nl] = (int)boxes.size();
-    const long long cells = total / nv;
-    if (boxes.empty() || cells <= 0 || cells > 0x7fffffffLL || boxes.front().first_cell != 0) return MCRAT_HIP_EINVAL;
-    int kv[5] = {-1, -1, -1, -1, -1};
-    static const char *want[5] = {"rho", "vx1", "vx2", "vx3", "prs"};
-    for (int k = 0; k < nv; ++k)
-        for (int w = 0; w < 5; ++w)
-            if (h->var_names[k] && strcmp(h->var_names[k], want[w]) == 0) kv[w] = k;
-    if (kv[0] < 0 || kv[1] < 0 || kv[2] < 0 || kv[4] < 0 || (c->kc.dimensions != DIM_TWO && kv[3] < 0)) { c->last_error = "PLUTO-Chombo ingest: a component (rho, vx1, vx2, [vx3], prs) is missing"; return MCRAT_HIP_EINVAL; }
+    const std::vector<ChomboBox> &boxes = plan.boxes;
+    const std::vector<int> &level_first_box = plan.level_first_box;
+    const long long total = plan.total, cells = plan.cells;
 
     c->have_hydro = false;
     sync_views(c);
@@ -1271,7 +1046,7 @@ extern "C" int mcrat_hip_ingest_chombo(mcrat_hip_ctx *c, const mcrat_hip_chombo 
     RawPacker pk{c};
     const size_t o_box = pk.add(boxes.data(), sizeof(ChomboBox) * boxes.size());
     size_t o_x[3] = {0, 0, 0}, o_dx[3] = {0, 0, 0};
-    for (int a = 0; a < nd; ++a) { o_x[a] = pk.add(xs[a].data(), sizeof(double) * xs[a].size()); o_dx[a] = pk.add(dxs[a].data(), sizeof(double) * dxs[a].size()); }
+    for (int a = 0; a < nd; ++a) { o_x[a] = pk.add(plan.xs[a].data(), sizeof(double) * plan.xs[a].size()); o_dx[a] = pk.add(plan.dxs[a].data(), sizeof(double) * plan.dxs[a].size()); }
     const size_t o_data = pk.add(h->data, sizeof(double) * (size_t)total);
     const size_t o_mask = masked ? pk.add(nullptr, (size_t)cells) : 0;
     int rc = pk.upload();
@@ -1280,7 +1055,7 @@ extern "C" int mcrat_hip_ingest_chombo(mcrat_hip_ctx *c, const mcrat_hip_chombo 
     d.boxes = pk.at<ChomboBox>(o_box); d.n_boxes = (int)boxes.size(); d.cells = cells;
     d.data = pk.at<double>(o_data);
     for (int a = 0; a < nd; ++a) { d.x[a] = pk.at<double>(o_x[a]); d.dx[a] = pk.at<double>(o_dx[a]); }
-    for (int w = 0; w < 5; ++w) d.kv[w] = kv[w];
+    for (int w = 0; w < 5; ++w) d.kv[w] = plan.kv[w];
     d.L = h->l_scale; d.D = h->d_scale; d.P = h->p_scale;
     if (masked) {
         unsigned char *mask = static_cast<unsigned char *>(c->raw_buf) + o_mask;
@@ -1399,8 +1174,7 @@ static int alloc_photons(mcrat_hip_ctx *c, int n)
     const size_t o_type = take(n_pad);
     const size_t total = off;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->ph_buf && c->ph_bytes < total) { HIPCHK(c, hipFree(c->ph_buf)); c->ph_buf = nullptr; c->ph_bytes = 0; }
-    if (!c->ph_buf) { HIPCHK(c, hipMalloc(&c->ph_buf, total)); c->ph_bytes = total; }
+    { int rc = ensure_device_bytes(c, &c->ph_buf, &c->ph_bytes, total); if (rc) return rc; }
     HIPCHK(c, hipMemsetAsync(c->ph_buf, 0, total, c->stream));
     char *b = static_cast<char *>(c->ph_buf);
     PhotonDev &p = c->ph;
@@ -1497,9 +1271,7 @@ static int ensure_aos(mcrat_hip_ctx *c, size_t bytes)
         c->aos_buf = c->parent->aos_buf; c->aos_bytes = c->parent->aos_bytes;
         return rc;
     }
-    if (c->aos_buf && c->aos_bytes < bytes) { HIPCHK(c, hipFree(c->aos_buf)); c->aos_buf = nullptr; c->aos_bytes = 0; }
-    if (!c->aos_buf) { HIPCHK(c, hipMalloc(&c->aos_buf, bytes)); c->aos_bytes = bytes; }
-    return MCRAT_HIP_OK;
+    return ensure_device_bytes(c, &c->aos_buf, &c->aos_bytes, bytes);
 }
 
 // Page-lock the caller's memory (its struct photon array, its hydro columns) so that the copies of set_photons / get_photons /

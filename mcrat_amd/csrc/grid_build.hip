@@ -1,5 +1,5 @@
 // grid_build.hip -- the cell-lookup grid of a hydro frame, built on the device ("build the device
-// cell-lookup structure at load").  Same structure as the host build in engine.hip (kept as the cross-check,
+// cell-lookup structure at load").  Same structure as the host build of hydro_plan.hpp (kept as the cross-check,
 // MCRAT_HIP_HOST_GRID=1): every cell is entered into all buckets its closed extent, widened by 1e-9 relative,
 // touches; every bucket list is ascending in cell index (so the first hit of the device's closed-interval test is
 // the lowest-index containing cell, what the linear scan of geometry.c:350-391 returns); every entry is a complete

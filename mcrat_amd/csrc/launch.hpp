@@ -4,6 +4,7 @@
 #include "device_types.hpp"
 #include "frame_queue.hpp"
 #include "list_plan.hpp"
+#include "hydro_plan.hpp"
 
 namespace mcrat {
 
@@ -118,12 +119,7 @@ struct OutputCols {
 hipError_t launch_output_count(const PhotonDev &ph, int n, unsigned *block_count, unsigned long long *d_total, hipStream_t stream);
 hipError_t launch_output_write(const PhotonDev &ph, int n, const int *block_start, const OutputCols &out, hipStream_t stream);
 
-// the cell-lookup grid, built on the device (grid_build.hip)
-struct GridPlan {
-    double org[3], inv[3];
-    int dim[3], logmap[3];
-    int naxes;
-};
+// the cell-lookup grid, built on the device (grid_build.hip) from a GridPlan (hydro_plan.hpp)
 hipError_t grid_count(const GridPlan &p, const CellGeom *geom, const CellGeom2 *geom2, int M, unsigned *count, long long nb,
                       unsigned long long *d_total, hipStream_t stream);
 size_t grid_scan_scratch_ints(long long nb);
@@ -160,18 +156,13 @@ hipError_t launch_inject_slab_write(const InjectParams &p, const HydroDev &hy, c
                                     hipStream_t stream);
 hipError_t launch_inject_pool(const InjectParams &p, const HydroDev &hy, const PhotonDev &pool, int stride, int n_ranks, const InjectSlabCell *slab, int n_slab,
                               PoolInject *lists, int group, hipStream_t stream);
-// getHydroData on the device (ingest.hip; mcrat_io.c:1898-1990)
+// getHydroData on the device (ingest.hip; mcrat_io.c:1898-1990); SlabDev, ChomboBox and StagePartial: hydro_plan.hpp
 struct HydroCols {          // struct hydro_dataframe's columns (mcrat.h:194-244), device arrays of M doubles
     double *r0, *r1, *r2, *s0, *s1, *s2;
     double *v0, *v1, *v2;
     double *dens, *dens_lab, *pres, *temp, *gamma;
     double *r, *theta;
     double *B0, *B1, *B2;   // magnetic field (B_FIELD_CALC == SIMULATION; mcrat_hip_set_hydro_extras)
-};
-struct SlabDev {
-    int dimensions, geometry, ph_inj_switch;
-    double r_inj_095;                          // 0.95 r_inj
-    double r_lo, r_hi, th_lo, th_hi;           // the widened slab for the current elem_factor
 };
 struct FlashDev {           // device copies of a FLASH checkpoint's datasets (mclib_flash.c:143-193)
     const double *coord, *bsize;
@@ -186,14 +177,6 @@ struct PlutoDev {           // device copies of readGridFile's arrays and the .d
     const double *x1, *dx1, *x2, *dx2, *x3, *dx3;
     const double *rho, *vx1, *vx2, *vx3, *prs;
     double L, D, P;
-};
-struct ChomboBox {          // one box of a PLUTO-Chombo level (mclib_pluto.c:520-545)
-    long long first_cell;   // (start_displacement + box_offset) / num_vars: where its cells sit in the reader's cell numbering
-    long long data_off;     // start_displacement + box_offset: its data in the concatenated "data:datatype=0" arrays
-    int level;
-    int lo[3], n[3];        // lo_i, lo_j, lo_k; cells per axis
-    int cb[3];              // where this level's 1-D coordinate arrays start in ChomboDev::x / dx
-    int pad[2];
 };
 struct ChomboDev {
     const ChomboBox *boxes;
@@ -221,10 +204,6 @@ hipError_t launch_cs_absorb(const CsParams &p, const PhotonDev &ph, const double
 struct OutflowDev {
     int simulation_type;
     double gamma_infinity, lumi, r00, t_comov, ddensity, theta_j, p;
-};
-struct StagePartial {       // one per workgroup of stage_cells_kernel
-    double lo[3], hi[3], smin[3], smax[3];
-    int any_hot, pad;
 };
 long long ingest_blocks(long long n_virtual);   // workgroups (and block_count entries) of the two selection passes
 hipError_t ingest_count_flash(const FlashDev &f, const SlabDev &slab, unsigned *block_count, unsigned long long *d_total, hipStream_t stream);

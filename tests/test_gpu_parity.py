@@ -712,6 +712,43 @@ def test_device_built_grid_equals_host_built_grid(hip, which, monkeypatch):
     assert (got[0][~snap] == pick[~snap]).all()
 
 
+def _linear_scan(frame, a0, a1):
+    """findContainingBlock (geometry.c:350-391) in numpy: the lowest-index cell whose closed extent holds the point, -1 if none"""
+    inside = ((2 * np.abs(a0[:, None] - frame["r0"][None, :]) - frame["r0_size"][None, :] <= 0) &
+              (2 * np.abs(a1[:, None] - frame["r1"][None, :]) - frame["r1_size"][None, :] <= 0))
+    return np.where(inside.any(axis=1), inside.argmax(axis=1), -1).astype(np.int32)
+
+
+@pytest.mark.parametrize("host_grid", [False, True], ids=["device-build", "host-build"])
+def test_one_context_staging_a_smaller_then_a_larger_frame(hip, host_grid, monkeypatch):
+    """one context stages 32x32, then 8x8 (every buffer is reused as it is), then 48x48 cells (every buffer grows): after each, the
+    cell lookup is the lowest-index linear scan of THAT frame -- interior points, points on faces and corners, points outside"""
+    if host_grid:
+        monkeypatch.setenv("MCRAT_HIP_HOST_GRID", "1")
+    else:
+        monkeypatch.delenv("MCRAT_HIP_HOST_GRID", raising=False)
+    rng = np.random.default_rng(5)
+    frames = [synth.config1(n_photons=8, n0=n, n1=n) for n in (32, 8, 48)]
+    e = hip.Engine(frames[0][2]["dimensions"], frames[0][2]["geometry"], 0)
+    try:
+        for frame, _, _ in frames:
+            n = int(round(frame["num_elements"] ** 0.5))
+            e.set_hydro(frame)
+            pick = rng.integers(0, n * n, 300)
+            u = rng.random((2, pick.size)) - 0.5
+            snap = (np.arange(pick.size) % 3 == 0)
+            u[:, snap] = np.sign(u[:, snap]) * 0.5
+            u[1, snap & (np.arange(pick.size) % 2 == 0)] = 0.123
+            a0 = np.concatenate([frame["r0"][pick] + u[0] * frame["r0_size"][pick], [frame["r0"].max() * 3.0, -1.0]])
+            a1 = np.concatenate([frame["r1"][pick] + u[1] * frame["r1_size"][pick], [frame["r1"].max() * 3.0, frame["r1"].mean()]])
+            want = _linear_scan(frame, a0, a1)
+            got = e.lookup_cell(a0, a1)
+            assert np.array_equal(got, want), n
+            assert np.array_equal(want[:-2][~snap], pick[~snap]) and (want[:-2][snap] != pick[snap]).any() and (want[-2:] == -1).all(), n
+    finally:
+        e.close()
+
+
 # ------------------------------------------------------------------ photonInjection on the device (SURVEY.md 8f-2)
 @pytest.mark.parametrize("case", ["cfg2-bb", "cfg2-wien", "cfg3-spherical", "3d-cartesian"])
 def test_photon_injection_equals_oracle(hip, oracle, case):
