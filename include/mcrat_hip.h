@@ -788,6 +788,43 @@ int mcrat_hip_ph_minmax(mcrat_hip_ctx *ctx, double *min_r, double *max_r, double
 int mcrat_hip_scatt_stats(mcrat_hip_ctx *ctx, int *max_scatt, int *min_scatt, double *avg_scatt, double *avg_r); /* mclib.c:1385 */
 int mcrat_hip_avg_energy(mcrat_hip_ctx *ctx, double *erg);                                                    /* mclib.c:1358 */
 
+/* mock observations on the resident photons: light curves, spectra, polarisation ---
+ * The photons binned by observer, detection time and energy in one pass on the device, without the HDF5 round trip.  The polar axis is r2 / p3.
+ * A slot counts when it is part of a list, weight != 0 and its type is neither 'p' (pool photon) nor 'N' (null photon).  Observer o accepts a
+ * photon when  p3 <= p0 * cos_lo[o] && p3 > p0 * cos_hi[o]  (its cone as two cosines, cos_lo > cos_hi; cones may overlap, and a photon counts for
+ * every observer that accepts it).  Its energy is  e = p0 * C_LIGHT  [erg] and its detection time
+ *     t_det = time_now - ((r2 * cos_obs[o] + sqrt(r0 * r0 + r1 * r1) * sin_obs[o]) / C_LIGHT)   [s].
+ * Bin k of an axis holds  edges[k] <= x < edges[k + 1]; an accepted photon outside either range is in no bin and counted in n_outside[o].  Per
+ * (observer, time bin, energy bin): count, W = sum w, WE = sum w * e, and the Stokes sums I, Q, U, V = sum w * s0 .. s3 (zero with stokes_switch
+ * off).  Light curves, spectra, polarisation degree and angle are sums and quotients of these planes: the caller's.
+ * Every expression above is evaluated in exactly that order in IEEE double without contraction, so the counts are exact: the same as the same
+ * expressions in host code.  The sums are added with floating-point atomics and are NOT bit-reproducible from run to run; each is within
+ * (m + 2) * 2^-53 * sum|term| of the exact sum of its bin's m terms.
+ * MCRAT_HIP_EINVAL, with its own text in mcrat_hip_last_error: n_obs, n_t or n_e < 1; n_obs * n_t * n_e overflowing an int; cos_lo <= cos_hi;
+ * edges that are not finite or not strictly ascending; more edges and observers than the kernel can stage (about 10 000 values together).
+ *   mcrat_hip_observe         one list: a stand-alone context, or a view of a pool (that list alone); time_now is the list's clock.
+ *   mcrat_hip_pool_observe    every list of a pool in one launch, each with its own clock time_now[r]; reads what mcrat_hip_pool_summaries reads:
+ *                             the pool's live columns as they stand, every slot with its valid flag (slots beyond a list's length and lists
+ *                             never created carry none).  Like mcrat_hip_pool_summaries it flushes nothing a view holds pending: lists whose
+ *                             frames the pool has run (mcrat_hip_run on the pool, mcrat_hip_pool_run_frames) are current; a list stepped one
+ *                             by one through its view (mcrat_hip_step_locate_sample, mcrat_hip_step_event) must be observed through that view, which flushes it first.
+ *   mcrat_hip_observe_path    how the context's last observation was accumulated: 1 a copy of the cube per workgroup in LDS, flushed once; 2
+ *                             atomics straight into the cube in HBM (a cube too large for LDS); 0 none yet.  MCRAT_HIP_OBSERVE_PATH=lds|global
+ *                             in the environment forces one (lds is refused for a cube that does not fit).
+ * Both calls synchronise before they return. */
+typedef struct mcrat_hip_observer {      /* inputs, host pointers */
+    int n_obs; const double *cos_obs, *sin_obs, *cos_lo, *cos_hi;   /* [n_obs] */
+    int n_t;   const double *t_edges;                               /* [n_t + 1] seconds */
+    int n_e;   const double *e_edges;                               /* [n_e + 1] erg */
+} mcrat_hip_observer;
+typedef struct mcrat_hip_observation {   /* outputs, host pointers, each [n_obs * n_t * n_e], observer-major then time then energy; any may be NULL */
+    long long *count; double *w, *we, *i, *q, *u, *v;
+    long long *n_accepted, *n_outside;   /* [n_obs] */
+} mcrat_hip_observation;
+int mcrat_hip_observe(mcrat_hip_ctx *ctx, const mcrat_hip_observer *obs, double time_now, mcrat_hip_observation *out);
+int mcrat_hip_pool_observe(mcrat_hip_ctx *pool, const mcrat_hip_observer *obs, const double *time_now /* [n_ranks] */, mcrat_hip_observation *out);
+int mcrat_hip_observe_path(const mcrat_hip_ctx *ctx);
+
 /* introspection used by bench.py / tests -------------------------------------- */
 int mcrat_hip_synchronize(mcrat_hip_ctx *ctx);
 size_t mcrat_hip_device_bytes(const mcrat_hip_ctx *ctx);   /* HBM held by the context */

@@ -19,6 +19,7 @@
 #include "../../include/mcrat_hip.h"
 #include "device_types.hpp"
 #include "launch.hpp"
+#include "observe_plan.hpp"
 #include "photon_cols.hpp"
 #include "rng.hpp"
 
@@ -154,6 +155,9 @@ struct mcrat_hip_ctx {
     ReducePartial *d_red = nullptr;
     ReducePartial *h_red = nullptr;   // pinned
     static constexpr int RED_BLOCKS = 512;
+    void *obs_buf = nullptr;          // mcrat_hip_observe: the cube, the per-observer counters and the staged inputs (observe_plan.hpp); a view uses its pool's
+    size_t obs_bytes = 0;
+    int obs_path = 0;                 // the accumulation path of the last observation (ObservePath)
 
     // profiling
     std::vector<hipEvent_t> ev;
@@ -399,6 +403,7 @@ extern "C" void mcrat_hip_destroy(mcrat_hip_ctx *c)
     if (c->h_state) (void)hipHostFree(c->h_state);
     if (c->d_red) (void)hipFree(c->d_red);
     if (c->h_red) (void)hipHostFree(c->h_red);
+    if (c->obs_buf) (void)hipFree(c->obs_buf);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -423,7 +428,7 @@ extern "C" size_t mcrat_hip_device_bytes(const mcrat_hip_ctx *c)
 {
     if (!c) return 0;
     return c->ph_bytes + c->hy_bytes + c->grid_bytes + c->grid_count_cap * sizeof(unsigned) + sizeof(Shortlist) + sizeof(LoopState) + (size_t)c->partials_cap * sizeof(Cand) +
-           sizeof(ReducePartial) * mcrat_hip_ctx::RED_BLOCKS;
+           sizeof(ReducePartial) * mcrat_hip_ctx::RED_BLOCKS + c->obs_bytes;
 }
 
 extern "C" int mcrat_hip_create_hot_cross_section(mcrat_hip_ctx *c, double *thermal_table, int n_ph_e, int n_t, double log_ph_e_min,
@@ -4133,6 +4138,84 @@ extern "C" int mcrat_hip_avg_energy(mcrat_hip_ctx *c, double *erg)
     *erg = (t.e_sum * C_LIGHT) / t.w_sum;
     return MCRAT_HIP_OK;
 }
+
+// ---------------------------------------------------------------------------------------------- mock observations
+// The photons of c->ph -- n_slots of them -- binned by observer, detection time and energy (observe_plan.hpp, observe.hip), and the cube read back.
+// clocks: one per slots_per_clock slots (a rank pool's lists), or nullptr and time_now for all.  The device block belongs to the pool when c is a view.
+static int observe_run(mcrat_hip_ctx *c, const mcrat_hip_observer *obs, int n_slots, const double *clocks, int n_clocks, int slots_per_clock, double time_now,
+                       mcrat_hip_observation *out)
+{
+    c->obs_path = OBSERVE_PATH_NONE;
+    if (!obs->cos_obs || !obs->sin_obs || !obs->cos_lo || !obs->cos_hi || !obs->t_edges || !obs->e_edges) {
+        c->last_error = "observe: a null array in mcrat_hip_observer";
+        return MCRAT_HIP_EINVAL;
+    }
+    ObservePath forced;
+    ObservePlan plan;
+    ObserveRefusal why = observe_path_switch(getenv("MCRAT_HIP_OBSERVE_PATH"), &forced);
+    if (why == OBSERVE_OK) why = observe_plan(obs->n_obs, obs->cos_lo, obs->cos_hi, obs->n_t, obs->t_edges, obs->n_e, obs->e_edges, forced, &plan);
+    if (why != OBSERVE_OK) { c->last_error = observe_refusal_text(why); return MCRAT_HIP_EINVAL; }
+
+    // the inputs in the order the kernel stages them, the clocks behind them: one copy
+    const size_t n_obs = (size_t)plan.n_obs;
+    std::vector<double> in;
+    in.reserve(plan.staged_doubles + (size_t)n_clocks);
+    in.insert(in.end(), obs->cos_obs, obs->cos_obs + n_obs); in.insert(in.end(), obs->sin_obs, obs->sin_obs + n_obs);
+    in.insert(in.end(), obs->cos_lo, obs->cos_lo + n_obs); in.insert(in.end(), obs->cos_hi, obs->cos_hi + n_obs);
+    in.insert(in.end(), obs->t_edges, obs->t_edges + plan.n_t + 1); in.insert(in.end(), obs->e_edges, obs->e_edges + plan.n_e + 1);
+    if (clocks) in.insert(in.end(), clocks, clocks + n_clocks);
+
+    mcrat_hip_ctx *owner = c->parent ? c->parent : c;
+    HIPCHK(c, hipStreamSynchronize(c->stream));                  // (the block may be replaced: nothing may still read the old one)
+    int rc = ensure_device_bytes(c, &owner->obs_buf, &owner->obs_bytes, plan.out_bytes + sizeof(double) * in.size());
+    if (rc) return rc;
+    char *d = static_cast<char *>(owner->obs_buf);
+    double *d_in = reinterpret_cast<double *>(d + plan.out_bytes);
+    ObserveDev a{};
+    a.n_slots = n_slots; a.n_obs = plan.n_obs; a.n_t = plan.n_t; a.n_e = plan.n_e; a.n_bins = plan.n_bins;
+    a.staged = d_in;
+    a.clocks = clocks ? d_in + plan.staged_doubles : nullptr;
+    a.slots_per_clock = slots_per_clock;
+    a.time_now = time_now;
+    a.cube = reinterpret_cast<double *>(d);
+    a.n_accepted = reinterpret_cast<unsigned long long *>(d + plan.cube_bytes);
+    a.n_outside = a.n_accepted + n_obs;
+    HIPCHK(c, hipMemsetAsync(d, 0, plan.out_bytes, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_in, in.data(), sizeof(double) * in.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_observe(c->ph, a, plan, c->kc.stokes != 0, device_cus(c), c->stream));
+    const size_t plane = sizeof(double) * (size_t)plan.n_bins;
+    void *planes[OBSERVE_PLANES] = {out->count, out->w, out->we, out->i, out->q, out->u, out->v};
+    static_assert(sizeof(long long) == 8, "the count plane is read back as it is");
+    for (int k = 0; k < OBSERVE_PLANES; ++k)
+        if (planes[k]) HIPCHK(c, hipMemcpyAsync(planes[k], d + plane * (size_t)k, plane, hipMemcpyDeviceToHost, c->stream));
+    if (out->n_accepted) HIPCHK(c, hipMemcpyAsync(out->n_accepted, a.n_accepted, sizeof(long long) * n_obs, hipMemcpyDeviceToHost, c->stream));
+    if (out->n_outside) HIPCHK(c, hipMemcpyAsync(out->n_outside, a.n_outside, sizeof(long long) * n_obs, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->obs_path = plan.path;
+    return MCRAT_HIP_OK;
+}
+
+extern "C" int mcrat_hip_observe(mcrat_hip_ctx *c, const mcrat_hip_observer *obs, double time_now, mcrat_hip_observation *out)
+{
+    if (!c || !obs || !out) return MCRAT_HIP_EINVAL;
+    if (!c->have_photons) return MCRAT_HIP_ESTATE;
+    if (c->is_pool) { c->last_error = "observe: a rank pool's lists have clocks of their own (mcrat_hip_pool_observe, or mcrat_hip_observe on a view)"; return MCRAT_HIP_ESTATE; }
+    int rc = flush_pending(c);
+    if (rc) return rc;
+    return observe_run(c, obs, c->ph.n, nullptr, 0, 1, time_now, out);
+}
+
+extern "C" int mcrat_hip_pool_observe(mcrat_hip_ctx *c, const mcrat_hip_observer *obs, const double *time_now, mcrat_hip_observation *out)
+{
+    if (!c || !obs || !time_now || !out) return MCRAT_HIP_EINVAL;
+    if (!c->is_pool) return MCRAT_HIP_ESTATE;
+    // every slot of the pool: those beyond a list's length, and those of lists never created, are not FLAG_VALID and contribute nothing (windows
+    // are cleared on upload, lists only grow, grown slots are type 'N').  No flush_pending, as in mcrat_hip_pool_summaries: a list stepped one by
+    // one through its view is read through the view (mcrat_hip_observe), which flushes it -- the header says so.
+    return observe_run(c, obs, c->ph.n, time_now, c->n_ranks, c->rank_stride, 0.0, out);
+}
+
+extern "C" int mcrat_hip_observe_path(const mcrat_hip_ctx *c) { return c ? c->obs_path : 0; }
 
 extern "C" int mcrat_hip_eval_function(mcrat_hip_ctx *c, int fn, int n, const double *in, double *out, uint64_t seed)
 {

@@ -106,6 +106,20 @@ hipError_t launch_convert_comptonized(const PhotonDev &ph, unsigned *converted, 
 hipError_t launch_clear_slots(const PhotonDev &ph, int first, int count, hipStream_t stream);   // every column zeroed: no list's slots
 // rank pool: the per-frame reductions and printPhotons' count for every list (desc[r].len slots from r * stride), one launch
 hipError_t launch_rank_reduce(const PhotonDev &ph, int stride, int n_ranks, const RankDesc *desc, ReducePartial *out, int *n_out, hipStream_t stream);
+// mock observations (observe.hip): the photons binned by observer, detection time and energy in one pass over n_slots slots.  The cube and the
+// staged inputs are laid out as observe_plan.hpp says; clocks != nullptr: slot i takes its list's clock clocks[i / slots_per_clock] (rank pool),
+// else time_now.  The plan has chosen the accumulation path; the adds go on top of what the cube holds (the caller zeroes it).
+struct ObservePlan;
+struct ObserveDev {
+    int n_slots, n_obs, n_t, n_e, n_bins;
+    const double *staged;                // cos_obs, sin_obs, cos_lo, cos_hi [n_obs each], t_edges [n_t + 1], e_edges [n_e + 1]
+    const double *clocks;
+    int slots_per_clock;
+    double time_now;
+    double *cube;                        // OBSERVE_PLANES planes of n_bins; plane 0 holds 64-bit integer counts
+    unsigned long long *n_accepted, *n_outside;   // [n_obs]
+};
+hipError_t launch_observe(const PhotonDev &ph, const ObserveDev &a, const ObservePlan &plan, bool stokes, int cus, hipStream_t stream);
 hipError_t launch_init_states_multi(LoopState *ranks, int n_ranks, const int *open, const double *time_now, const double *remaining, hipStream_t stream);
 hipError_t launch_aos_to_soa(const void *aos, const PhotonDev &ph, int n, hipStream_t stream);
 // many lists of a rank pool at once: desc = `count` device records {int rank, int n, long long first record in aos}; the rest of each window is cleared

@@ -182,6 +182,20 @@ class PoolCsList(C.Structure):
                 ("theta_min", C.c_double), ("theta_max", C.c_double)]
 
 
+class Observer(C.Structure):
+    """mcrat_hip_observer: the observers' directions and cones and the bin edges of a mock observation"""
+    _fields_ = [("n_obs", C.c_int), ("cos_obs", _dp), ("sin_obs", _dp), ("cos_lo", _dp), ("cos_hi", _dp),
+                ("n_t", C.c_int), ("t_edges", _dp), ("n_e", C.c_int), ("e_edges", _dp)]
+
+
+class Observation(C.Structure):
+    """mcrat_hip_observation: the cube's planes, each [n_obs * n_t * n_e], and the per-observer counters"""
+    _fields_ = [("count", C.POINTER(C.c_longlong)), ("w", _dp), ("we", _dp), ("i", _dp), ("q", _dp), ("u", _dp), ("v", _dp),
+                ("n_accepted", C.POINTER(C.c_longlong)), ("n_outside", C.POINTER(C.c_longlong))]
+
+
+OBSERVE_PATH_LDS, OBSERVE_PATH_GLOBAL = 1, 2      # mcrat_hip_observe_path
+
 SCIENCE, CYLINDRICAL_OUTFLOW, SPHERICAL_OUTFLOW, STRUCTURED_SPHERICAL_OUTFLOW = 0, 1, 2, 3    # SIMULATION_TYPE, mcrat.h:30-33
 
 # every symbol include/mcrat_hip.h declares: (restype, argtypes)
@@ -278,6 +292,9 @@ SYMBOLS = {
     "mcrat_hip_ph_minmax": (C.c_int, [_ctx, _dp, _dp, _dp, _dp]),
     "mcrat_hip_scatt_stats": (C.c_int, [_ctx, _ip, _ip, _dp, _dp]),
     "mcrat_hip_avg_energy": (C.c_int, [_ctx, _dp]),
+    "mcrat_hip_observe": (C.c_int, [_ctx, C.POINTER(Observer), C.c_double, C.POINTER(Observation)]),
+    "mcrat_hip_pool_observe": (C.c_int, [_ctx, C.POINTER(Observer), _dp, C.POINTER(Observation)]),
+    "mcrat_hip_observe_path": (C.c_int, [_ctx]),
     "mcrat_hip_synchronize": (C.c_int, [_ctx]),
     "mcrat_hip_device_bytes": (C.c_size_t, [_ctx]),
     "mcrat_hip_eval_function": (C.c_int, [_ctx, C.c_int, C.c_int, _dp, _dp, C.c_uint64]),
@@ -316,6 +333,18 @@ class McratHipError(RuntimeError):
 
 def _f8(a):
     return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def observer_angles(theta_obs_deg, dtheta_deg):
+    """observers at polar angles theta_obs_deg [degrees from the r2 axis], each accepting photons whose direction lies within its cone of full width
+    dtheta_deg: theta_obs - dtheta / 2 < theta <= theta_obs + dtheta / 2, cut at the axis  ->  (cos_obs, sin_obs, cos_lo, cos_hi) for
+    Engine.observe.  The lower edge is closed at the axis (cos_lo just above 1), so that a photon along the axis is seen by an observer there."""
+    th = np.radians(np.atleast_1d(_f8(theta_obs_deg)))
+    half = 0.5 * np.radians(np.broadcast_to(_f8(dtheta_deg), th.shape))
+    lo, hi = th - half, th + half
+    cos_lo = np.where(lo <= 0.0, np.nextafter(1.0, 2.0), np.cos(np.maximum(lo, 0.0)))
+    cos_hi = np.where(hi >= np.pi, -np.nextafter(1.0, 2.0), np.cos(np.minimum(hi, np.pi)))
+    return np.cos(th), np.sin(th), cos_lo, cos_hi
 
 
 class Engine:
@@ -943,6 +972,40 @@ class Engine:
         e = C.c_double()
         self._check(self.lib.mcrat_hip_avg_energy(self.ctx, C.byref(e)), "avg_energy")
         return e.value
+
+    # ---- mock observations: the resident photons binned by observer, detection time and energy (include/mcrat_hip.h)
+    def _observe(self, call, what, cos_obs, sin_obs, cos_lo, cos_hi, t_edges, e_edges, time_now):
+        co, so, cl, ch, te, ee = (_f8(a).ravel() for a in (cos_obs, sin_obs, cos_lo, cos_hi, t_edges, e_edges))
+        n_obs, n_t, n_e = len(co), len(te) - 1, len(ee) - 1
+        if not (len(so) == len(cl) == len(ch) == n_obs):
+            raise ValueError("%s: cos_obs, sin_obs, cos_lo and cos_hi must have one entry per observer" % what)
+        obs = Observer(n_obs, co.ctypes.data_as(_dp), so.ctypes.data_as(_dp), cl.ctypes.data_as(_dp), ch.ctypes.data_as(_dp),
+                       n_t, te.ctypes.data_as(_dp), n_e, ee.ctypes.data_as(_dp))
+        shape = (max(n_obs, 0), max(n_t, 0), max(n_e, 0))
+        res = {"count": np.zeros(shape, dtype=np.int64), "n_accepted": np.zeros(shape[0], dtype=np.int64), "n_outside": np.zeros(shape[0], dtype=np.int64)}
+        for k in ("w", "we", "i", "q", "u", "v"):
+            res[k] = np.zeros(shape)
+        ll = C.POINTER(C.c_longlong)
+        out = Observation(res["count"].ctypes.data_as(ll), *[res[k].ctypes.data_as(_dp) for k in ("w", "we", "i", "q", "u", "v")],
+                          res["n_accepted"].ctypes.data_as(ll), res["n_outside"].ctypes.data_as(ll))
+        self._check(call(self.ctx, C.byref(obs), time_now, C.byref(out)), what)
+        return res
+
+    def observe(self, cos_obs, sin_obs, cos_lo, cos_hi, t_edges, e_edges, time_now):
+        """this list's photons as the observers see them at the list's clock time_now -> dict of (n_obs, n_t, n_e) arrays count, w, we, i, q, u, v
+        and the per-observer n_accepted, n_outside (mcrat_hip_observe; observer_angles gives the four cosine arrays)"""
+        return self._observe(self.lib.mcrat_hip_observe, "observe", cos_obs, sin_obs, cos_lo, cos_hi, t_edges, e_edges, float(time_now))
+
+    def pool_observe(self, cos_obs, sin_obs, cos_lo, cos_hi, t_edges, e_edges, time_now):
+        """every list of the pool in one launch, list r at its own clock time_now[r] (mcrat_hip_pool_observe)"""
+        tn = _f8(time_now).ravel()
+        if len(tn) != self.n_pool_ranks:
+            raise ValueError("pool_observe: time_now needs one clock per rank of the pool")
+        return self._observe(self.lib.mcrat_hip_pool_observe, "pool_observe", cos_obs, sin_obs, cos_lo, cos_hi, t_edges, e_edges, tn.ctypes.data_as(_dp))
+
+    def observe_path(self):
+        """how the last observation of this context was accumulated: OBSERVE_PATH_LDS, OBSERVE_PATH_GLOBAL, 0: none yet"""
+        return int(self.lib.mcrat_hip_observe_path(self.ctx))
 
     def synchronize(self):
         self._check(self.lib.mcrat_hip_synchronize(self.ctx), "synchronize")
