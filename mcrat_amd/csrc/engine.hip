@@ -13,7 +13,6 @@
 #include <mutex>
 #include <new>
 #include <string>
-#include <type_traits>
 #include <vector>
 
 #include "../../include/mcrat_hip.h"
@@ -21,6 +20,7 @@
 #include "launch.hpp"
 #include "observe_plan.hpp"
 #include "photon_cols.hpp"
+#include "photon_plan.hpp"
 #include "rng.hpp"
 
 using namespace mcrat;
@@ -31,6 +31,12 @@ static_assert(offsetof(mcrat_hip_photon, num_scatt) == 128 && offsetof(mcrat_hip
               offsetof(mcrat_hip_photon, time_to_scatter) == 160 && offsetof(mcrat_hip_photon, total_optical_depth) == 168,
               "struct photon field offsets");
 static_assert(sizeof(LoopState) == 256, "LoopState is one 256-B record");
+// the column table of photon_plan.hpp is in the order the loop kernels number the columns (photon_cols.hpp)
+static_assert(N_PHOTON_COLS == N_DOUBLE_COLS && N_BLOCK_COLS == N_DOUBLE_COLS + 1, "the block: PhotonDev's double columns and ListCols::draw_log");
+#define MCRAT_X(name, K) static_assert(PHOTON_COLS[K] == &PhotonDev::name, "PHOTON_COLS[" #K "] is not PhotonDev::" #name);
+MCRAT_DOUBLE_COLS(MCRAT_X)
+#undef MCRAT_X
+static_assert(sizeof(OutputCols::col) / sizeof(double *) == N_OUTPUT_COLS, "OUTPUT_COLS names the caller's member for every column of OutputCols");
 
 struct mcrat_hip_ctx {
     mcrat_hip_config cfg;
@@ -41,6 +47,7 @@ struct mcrat_hip_ctx {
 
     // photons
     PhotonDev ph{};
+    PhotonLayout ph_lay{};            // the block at ph_buf (photon_plan.hpp); ph is it bound, a view's ph a window of its pool's
     void *ph_buf = nullptr;
     size_t ph_bytes = 0;
     void *ph_snap = nullptr;          // mcrat_hip_snapshot_photons
@@ -57,7 +64,7 @@ struct mcrat_hip_ctx {
     size_t aos_bytes = 0;
     int step_blocks = 0;
     Cand *partials = nullptr;
-    int partials_cap = 0;
+    size_t partials_bytes = 0;
     Shortlist *shortlist = nullptr;
 
     // hydro
@@ -117,7 +124,7 @@ struct mcrat_hip_ctx {
     double rank_passes_per_list = 0;  // of the last completed frame
     LoopState *d_rstates = nullptr;
     LoopState *h_rstates = nullptr;   // pinned
-    int rstates_cap = 0;
+    size_t d_rstates_bytes = 0, h_rstates_bytes = 0;
 
     // rank pool (mcrat_hip_pool_*): the photon arrays hold n_ranks lists of up to rank_stride slots, each with its own length,
     // seed, stream and clock -- the reference's MPI ranks, adopted by one GPU.  List r is reached through a *view*: a context
@@ -189,6 +196,13 @@ static int ensure_device_bytes(mcrat_hip_ctx *c, void **buf, size_t *bytes, size
     if (!*buf) { HIPCHK(c, hipMalloc(buf, need)); *bytes = need; }
     return MCRAT_HIP_OK;
 }
+// ... and its pinned-host twin
+static int ensure_host_bytes(mcrat_hip_ctx *c, void **buf, size_t *bytes, size_t need)
+{
+    if (*buf && *bytes < need) { HIPCHK(c, hipHostFree(*buf)); *buf = nullptr; *bytes = 0; }
+    if (!*buf && need) { HIPCHK(c, hipHostMalloc(buf, need, hipHostMallocDefault)); *bytes = need; }
+    return MCRAT_HIP_OK;
+}
 
 // a temporary device array of one call: freed where its scope ends, whichever way the call leaves it
 template <class T>
@@ -224,6 +238,7 @@ static void drop_graph(mcrat_hip_ctx *c)
 
 static void sync_views(mcrat_hip_ctx *c);
 static int view_refuses(mcrat_hip_ctx *c, const char *what);
+static int capture_refuses(mcrat_hip_ctx *c, const char *what);
 static void release_shared_hydro(mcrat_hip_ctx *c);
 static int ensure_counts(mcrat_hip_ctx *c, size_t n);
 
@@ -427,7 +442,7 @@ extern "C" int mcrat_hip_synchronize(mcrat_hip_ctx *c)
 extern "C" size_t mcrat_hip_device_bytes(const mcrat_hip_ctx *c)
 {
     if (!c) return 0;
-    return c->ph_bytes + c->hy_bytes + c->grid_bytes + c->grid_count_cap * sizeof(unsigned) + sizeof(Shortlist) + sizeof(LoopState) + (size_t)c->partials_cap * sizeof(Cand) +
+    return c->ph_bytes + c->hy_bytes + c->grid_bytes + c->grid_count_cap * sizeof(unsigned) + sizeof(Shortlist) + sizeof(LoopState) + c->partials_bytes +
            sizeof(ReducePartial) * mcrat_hip_ctx::RED_BLOCKS + c->obs_bytes;
 }
 
@@ -543,6 +558,15 @@ static int ensure_counts(mcrat_hip_ctx *c, size_t n)
 static int view_refuses(mcrat_hip_ctx *c, const char *what)
 {
     c->last_error = std::string(what) + ": a rank view shares its pool's hydro frame; call this on the pool context";
+    return MCRAT_HIP_ESTATE;
+}
+
+// While a captured frame is selected (mcrat_hip_pool_select_frame) the pool's columns are that capture's: the read entry points are meant to look
+// there, every pool entry point that writes photons or loop state refuses -- it would write into the capture
+static int capture_refuses(mcrat_hip_ctx *c, const char *what)
+{
+    if (c->selected_frame < 0) return MCRAT_HIP_OK;
+    c->last_error = std::string(what) + ": a captured frame is selected (mcrat_hip_pool_select_frame(pool, -1) first)";
     return MCRAT_HIP_ESTATE;
 }
 
@@ -1142,19 +1166,11 @@ static int alloc_view_photons(mcrat_hip_ctx *c, int n, bool clear_window = true)
         c->last_error = "the list is longer than the pool's slots per rank (mcrat_hip_pool_create)";
         return MCRAT_HIP_ENOMEM;
     }
-    const size_t o = (size_t)c->view_rank * (size_t)P->rank_stride;
-    PhotonDev p = P->ph;
-    double **cols[24] = {&p.r0, &p.r1, &p.r2, &p.p0, &p.p1, &p.p2, &p.p3, &p.c0, &p.c1, &p.c2, &p.c3, &p.s0, &p.s1, &p.s2, &p.s3,
-                         &p.num_scatt, &p.weight, &p.tau, &p.tts, &p.u0, &p.u1, &p.u2, &p.ntau, &p.tau_next};
-    for (int k = 0; k < 24; ++k) *cols[k] += o;
-    p.idx += o; p.flags += o; p.type += o;
-    p.n = n;
-    p.n_pad = P->rank_stride;                 // (col_stride stays the pool's: the columns of a view are windows into the pool's)
-    c->ph = p;
+    c->ph = photon_window(P->ph, c->view_rank, P->rank_stride, n);
     if (clear_window) HIPCHK(c, launch_clear_slots(c->ph, 0, P->rank_stride, c->stream));
-    c->step_blocks = step_grid_blocks(p.n_pad);
+    c->step_blocks = step_grid_blocks(c->ph.n_pad);
     c->partials = P->partials;                // list-mode scratch is the pool's: one stream, one list at a time
-    c->partials_cap = P->partials_cap;
+    c->partials_bytes = P->partials_bytes;
     c->shortlist = P->shortlist;
     if (clear_window) HIPCHK(c, hipMemsetAsync(c->shortlist, 0, sizeof(Shortlist), c->stream));
     c->n_ranks = 0;
@@ -1169,57 +1185,25 @@ static int alloc_photons(mcrat_hip_ctx *c, int n)
         c->last_error = "this context is a rank pool: its photons are set through the views (mcrat_hip_pool_rank)";
         return MCRAT_HIP_ESTATE;
     }
-    const int n_pad = (int)align_up((size_t)std::max(n, 1), 2 * STEP_BLOCK);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    size_t o_d[25];                                                           // the 24 columns of PhotonDev + rank_loop_kernel's scratch column
-    for (int k = 0; k < 25; ++k) o_d[k] = take(sizeof(double) * n_pad);     // (photon_cols.hpp, ListCols::draw_log)
-    const size_t o_idx = take(sizeof(int) * n_pad);
-    const size_t o_flags = take(n_pad);
-    const size_t o_type = take(n_pad);
-    const size_t total = off;
+    int rc;
+    // the layout
+    if (const PhotonLayoutStatus why = photon_layout(n, &c->ph_lay)) { c->last_error = photon_layout_text(why); return MCRAT_HIP_EINVAL; }
+    // the buffer, zeroed
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    { int rc = ensure_device_bytes(c, &c->ph_buf, &c->ph_bytes, total); if (rc) return rc; }
-    HIPCHK(c, hipMemsetAsync(c->ph_buf, 0, total, c->stream));
-    char *b = static_cast<char *>(c->ph_buf);
-    PhotonDev &p = c->ph;
-    double **cols[19] = {&p.r0, &p.r1, &p.r2, &p.p0, &p.p1, &p.p2, &p.p3, &p.c0, &p.c1, &p.c2, &p.c3,
-                         &p.s0, &p.s1, &p.s2, &p.s3, &p.num_scatt, &p.weight, &p.tau, &p.tts};
-    for (int k = 0; k < 19; ++k) *cols[k] = reinterpret_cast<double *>(b + o_d[k]);
-    p.u0 = reinterpret_cast<double *>(b + o_d[19]);
-    p.u1 = reinterpret_cast<double *>(b + o_d[20]);
-    p.u2 = reinterpret_cast<double *>(b + o_d[21]);
-    p.ntau = reinterpret_cast<double *>(b + o_d[22]);
-    p.tau_next = reinterpret_cast<double *>(b + o_d[23]);
-    p.idx = reinterpret_cast<int *>(b + o_idx);
-    p.flags = reinterpret_cast<unsigned char *>(b + o_flags);
-    p.type = b + o_type;
-    p.n = n;
-    p.n_pad = n_pad;
-    if ((o_d[1] - o_d[0]) / sizeof(double) * 25 > 0xffffffffull) { c->last_error = "photon list: more than 2^32 / 25 slots"; return MCRAT_HIP_EINVAL; }
-    p.col_stride = (unsigned)((o_d[1] - o_d[0]) / sizeof(double));
-    for (int k = 1; k < 25; ++k)
-        if (o_d[k] - o_d[k - 1] != o_d[1] - o_d[0]) { c->last_error = "photon columns are not equally spaced"; return MCRAT_HIP_EHIP; }
-    c->step_blocks = step_grid_blocks(n_pad);
-    const int need = c->step_blocks;                          // one candidate per workgroup of the step kernel
-    if (c->partials_cap < need) {
-        if (c->partials) HIPCHK(c, hipFree(c->partials));
-        c->partials = nullptr;
-        HIPCHK(c, hipMalloc((void **)&c->partials, sizeof(Cand) * need));
-        c->partials_cap = need;
-    }
+    if ((rc = ensure_device_bytes(c, &c->ph_buf, &c->ph_bytes, c->ph_lay.total))) return rc;
+    HIPCHK(c, hipMemsetAsync(c->ph_buf, 0, c->ph_lay.total, c->stream));
+    // the columns
+    c->ph = bind_photons(c->ph_lay, c->ph_buf, n);
+    // the context's scratch: one candidate per workgroup of the step kernel, one LoopState per virtual rank, the shortlist
+    c->step_blocks = step_grid_blocks(c->ph.n_pad);
+    if ((rc = ensure_device_bytes(c, (void **)&c->partials, &c->partials_bytes, sizeof(Cand) * (size_t)c->step_blocks))) return rc;
     c->n_ranks = 0;
     if (c->cfg.virtual_rank_photons > 0) {
         c->rank_stride = c->cfg.virtual_rank_photons;
         c->n_ranks = (n + c->cfg.virtual_rank_photons - 1) / c->cfg.virtual_rank_photons;
-        if (c->rstates_cap < c->n_ranks) {
-            if (c->d_rstates) HIPCHK(c, hipFree(c->d_rstates));
-            if (c->h_rstates) HIPCHK(c, hipHostFree(c->h_rstates));
-            c->d_rstates = nullptr; c->h_rstates = nullptr;
-            HIPCHK(c, hipMalloc((void **)&c->d_rstates, sizeof(LoopState) * c->n_ranks));
-            HIPCHK(c, hipHostMalloc((void **)&c->h_rstates, sizeof(LoopState) * c->n_ranks, hipHostMallocDefault));
-            c->rstates_cap = c->n_ranks;
-        }
+        const size_t bytes = sizeof(LoopState) * (size_t)c->n_ranks;
+        if ((rc = ensure_device_bytes(c, (void **)&c->d_rstates, &c->d_rstates_bytes, bytes))) return rc;
+        if ((rc = ensure_host_bytes(c, (void **)&c->h_rstates, &c->h_rstates_bytes, bytes))) return rc;
     }
     if (!c->shortlist) HIPCHK(c, hipMalloc((void **)&c->shortlist, sizeof(Shortlist)));
     HIPCHK(c, hipMemsetAsync(c->shortlist, 0, sizeof(Shortlist), c->stream));
@@ -1227,45 +1211,27 @@ static int alloc_photons(mcrat_hip_ctx *c, int n)
     return MCRAT_HIP_OK;
 }
 
-static inline unsigned char make_flags(char type, double weight, int recalc)
-{
-    unsigned f = FLAG_VALID;
-    if (type != 'p' && weight != 0) f |= FLAG_MOVES;      // mclib.c:1070
-    if (recalc == 1) f |= FLAG_RECALC;
-    return (unsigned char)f;
-}
+// a list has come in: the context holds photons, and whatever frame was open is not theirs
+static void photons_are_set(mcrat_hip_ctx *c) { c->have_photons = true; c->frame_open = false; }
 
-static int upload_columns(mcrat_hip_ctx *c, int n, const std::vector<const double *> &src, const int *idx,
-                          const unsigned char *flags, const char *type)
+// the caller's columns into the list's, with the derived columns and the flag byte made from them (photon_plan.hpp)
+static int upload_columns(mcrat_hip_ctx *c, const mcrat_hip_photon_soa *s)
 {
-    PhotonDev &p = c->ph;
-    double *cols[19] = {p.r0, p.r1, p.r2, p.p0, p.p1, p.p2, p.p3, p.c0, p.c1, p.c2, p.c3,
-                        p.s0, p.s1, p.s2, p.s3, p.num_scatt, p.weight, p.tau, p.tts};
-    for (int k = 0; k < 19; ++k)
-        if (src[k]) HIPCHK(c, hipMemcpyAsync(cols[k], src[k], sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-    // derived columns (device_types.hpp): same operations, in the same order, as mclib.c:1074-1080 and :680
-    std::vector<double> der((size_t)4 * n, 0.0);
-    for (int i = 0; i < n; ++i) {
-        const double p0 = src[3][i];
-        if (p0 != 0) {
-            const double d = 1.0 / p0;
-            der[i] = src[4][i] * d * C_LIGHT;
-            der[(size_t)n + i] = src[5][i] * d * C_LIGHT;
-            der[(size_t)2 * n + i] = src[6][i] * d * C_LIGHT;
-        }
-        const double tau = src[17] ? src[17][i] : 0.0;
-        der[(size_t)3 * n + i] = -1.0 / tau;
-    }
-    HIPCHK(c, hipMemcpyAsync(p.u0, der.data(), sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(p.u1, der.data() + n, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(p.u2, der.data() + (size_t)2 * n, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(p.ntau, der.data() + (size_t)3 * n, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(p.idx, idx, sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(p.flags, flags, n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(p.type, type, n, hipMemcpyHostToDevice, c->stream));
+    const PhotonDev &p = c->ph;
+    const size_t n = (size_t)s->n;
+    for (int k = 0; k < N_ABI_COLS; ++k)
+        if (s->*SOA_COLS[k]) HIPCHK(c, hipMemcpyAsync(p.*PHOTON_COLS[k], s->*SOA_COLS[k], sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+    std::vector<double> der(4 * n);
+    derived_columns(s->n, s->p0, s->p1, s->p2, s->p3, s->total_optical_depth, der.data());
+    double *const derived[4] = {p.u0, p.u1, p.u2, p.ntau};
+    for (int k = 0; k < 4; ++k) HIPCHK(c, hipMemcpyAsync(derived[k], der.data() + k * n, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+    std::vector<unsigned char> flags(n);
+    for (size_t i = 0; i < n; ++i) flags[i] = make_flags(s->type[i], s->weight[i], s->recalc_properties[i]);
+    HIPCHK(c, hipMemcpyAsync(p.idx, s->nearest_block_index, sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(p.flags, flags.data(), n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(p.type, s->type, n, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->have_photons = true;
-    c->frame_open = false;
+    photons_are_set(c);
     return MCRAT_HIP_OK;
 }
 
@@ -1307,8 +1273,7 @@ extern "C" int mcrat_hip_set_photons(mcrat_hip_ctx *c, const mcrat_hip_photon_li
     HIPCHK(c, hipMemcpyAsync(c->aos_buf, l->photons, bytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, launch_aos_to_soa(c->aos_buf, c->ph, n, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->have_photons = true;
-    c->frame_open = false;
+    photons_are_set(c);
     return MCRAT_HIP_OK;
 }
 
@@ -1320,6 +1285,7 @@ extern "C" int mcrat_hip_pool_set_photons(mcrat_hip_ctx *c, int count, const int
 {
     if (!c || count < 0 || (count > 0 && (!rank_of || !lists))) return MCRAT_HIP_EINVAL;
     if (!c->is_pool) return MCRAT_HIP_ESTATE;
+    if (int rc_ = capture_refuses(c, "pool_set_photons")) return rc_;
     if (count == 0) return MCRAT_HIP_OK;
     struct Desc { int rank, n; long long first; };
     static_assert(sizeof(Desc) == 16, "PoolSetDesc of staging.hip");
@@ -1373,8 +1339,7 @@ extern "C" int mcrat_hip_pool_set_photons(mcrat_hip_ctx *c, int count, const int
     for (int j = 0; j < count; ++j) {
         mcrat_hip_ctx *v = c->views[desc[(size_t)j].rank];
         if ((rc = alloc_view_photons(v, desc[(size_t)j].n, false))) { c->last_error = v->last_error; return rc; }    // the view's columns in place; the launch above filled and cleared the window
-        v->have_photons = true;
-        v->frame_open = false;
+        photons_are_set(v);
     }
     HIPCHK(c, hipMemsetAsync(c->shortlist, 0, sizeof(Shortlist), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1415,8 +1380,7 @@ extern "C" int mcrat_hip_inject_photons(mcrat_hip_ctx *c, double r_inj, double p
     HIPCHK(c, launch_exclusive_scan(c->grid_count, M, start, scratch, (long long)total, c->stream));
     HIPCHK(c, launch_inject_generate(p, c->hy, weight, key, start, c->ph, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->have_photons = true;
-    c->frame_open = false;
+    photons_are_set(c);
     if (num_photons) *num_photons = n;
     if (ph_weight_adjusted) *ph_weight_adjusted = weight;
     return MCRAT_HIP_OK;
@@ -1430,6 +1394,7 @@ extern "C" int mcrat_hip_pool_inject_photons(mcrat_hip_ctx *c, double fps, mcrat
 {
     if (!c || !lists || !(fps > 0)) return MCRAT_HIP_EINVAL;
     if (!c->is_pool) return MCRAT_HIP_ESTATE;
+    if (int rc_ = capture_refuses(c, "pool_inject_photons")) return rc_;
     if (!c->have_hydro) return MCRAT_HIP_ESTATE;
     const int R = c->n_ranks, M = c->hy.M;
     std::vector<Region> slabs((size_t)R);                   // the lists grouped by their slab
@@ -1508,8 +1473,7 @@ extern "C" int mcrat_hip_pool_inject_photons(mcrat_hip_ctx *c, double fps, mcrat
             continue;
         }
         v->ph.n = e.n;
-        v->have_photons = true;
-        v->frame_open = false;
+        photons_are_set(v);
         q.num_photons = e.n;
         q.ph_weight_adjusted = e.weight_out;
     }
@@ -1533,12 +1497,14 @@ static int grow_photons(mcrat_hip_ctx *c, int new_n)
         return MCRAT_HIP_OK;
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->ph_buf = nullptr; c->ph_bytes = 0;                     // a fresh, zeroed allocation
+    // not the grow-only buffer as it is (ensure_device_bytes): a fresh, zeroed allocation, so that the old one is still there to be copied from
+    const PhotonLayout old_lay = c->ph_lay;
+    const size_t old_bytes = c->ph_bytes;
+    c->ph_buf = nullptr; c->ph_bytes = 0;
     int rc = alloc_photons(c, new_n);
-    if (rc) { if (c->ph_buf) (void)hipFree(c->ph_buf); c->ph_buf = old_buf; c->ph = old; return rc; }
-#define MCRAT_X(name, K) HIPCHK(c, hipMemcpyAsync(c->ph.name, old.name, sizeof(double) * (size_t)old_n, hipMemcpyDeviceToDevice, c->stream));
-    MCRAT_DOUBLE_COLS(MCRAT_X)
-#undef MCRAT_X
+    if (rc) { if (c->ph_buf) (void)hipFree(c->ph_buf); c->ph_buf = old_buf; c->ph_bytes = old_bytes; c->ph_lay = old_lay; c->ph = old; return rc; }
+    for (int k = 0; k < N_PHOTON_COLS; ++k)
+        HIPCHK(c, hipMemcpyAsync(c->ph.*PHOTON_COLS[k], old.*PHOTON_COLS[k], sizeof(double) * (size_t)old_n, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->ph.idx, old.idx, sizeof(int) * (size_t)old_n, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->ph.flags, old.flags, (size_t)old_n, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->ph.type, old.type, (size_t)old_n, hipMemcpyDeviceToDevice, c->stream));
@@ -1656,16 +1622,8 @@ extern "C" int mcrat_hip_set_photons_soa(mcrat_hip_ctx *c, const mcrat_hip_photo
     if (!s->type || !s->p0 || !s->p1 || !s->p2 || !s->p3 || !s->r0 || !s->r1 || !s->r2 || !s->num_scatt ||
         !s->recalc_properties || !s->weight || !s->nearest_block_index)
         return MCRAT_HIP_EINVAL;
-    const int n = s->n;
-    int rc = alloc_photons(c, n);
-    if (rc) return rc;
-    std::vector<unsigned char> flags(n);
-    for (int i = 0; i < n; ++i) flags[i] = make_flags(s->type[i], s->weight[i], s->recalc_properties[i]);
-    std::vector<const double *> src = {s->r0, s->r1, s->r2, s->p0, s->p1, s->p2, s->p3,
-                                       s->comv_p0, s->comv_p1, s->comv_p2, s->comv_p3,
-                                       s->s0, s->s1, s->s2, s->s3, s->num_scatt, s->weight,
-                                       s->total_optical_depth, s->time_to_scatter};
-    return upload_columns(c, n, src, s->nearest_block_index, flags.data(), s->type);
+    const int rc = alloc_photons(c, s->n);
+    return rc ? rc : upload_columns(c, s);
 }
 
 extern "C" int mcrat_hip_snapshot_photons(mcrat_hip_ctx *c)
@@ -1673,9 +1631,9 @@ extern "C" int mcrat_hip_snapshot_photons(mcrat_hip_ctx *c)
     if (!c) return MCRAT_HIP_EINVAL;
     if (!c->have_photons) return MCRAT_HIP_ESTATE;
     if (c->parent) { c->last_error = "snapshot the pool, not one of its views"; return MCRAT_HIP_ESTATE; }
+    if (int rc_ = capture_refuses(c, "snapshot_photons")) return rc_;
     if (c->frame_open && c->n_ranks == 0) { HIPCHK(c, launch_flush(c->ph, c->d_state, c->step_blocks, c->stream)); }
-    if (c->ph_snap && c->ph_snap_bytes < c->ph_bytes) { HIPCHK(c, hipFree(c->ph_snap)); c->ph_snap = nullptr; }
-    if (!c->ph_snap) { HIPCHK(c, hipMalloc(&c->ph_snap, c->ph_bytes)); c->ph_snap_bytes = c->ph_bytes; }
+    if (int rc_ = ensure_device_bytes(c, &c->ph_snap, &c->ph_snap_bytes, c->ph_bytes)) return rc_;
     HIPCHK(c, hipMemcpyAsync(c->ph_snap, c->ph_buf, c->ph_bytes, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->snap_lens.clear();
@@ -1687,6 +1645,7 @@ extern "C" int mcrat_hip_restore_photons(mcrat_hip_ctx *c)
 {
     if (!c) return MCRAT_HIP_EINVAL;
     if (c->parent || !c->have_photons || !c->ph_snap || c->ph_snap_bytes < c->ph_bytes) return MCRAT_HIP_ESTATE;
+    if (int rc_ = capture_refuses(c, "restore_photons")) return rc_;
     HIPCHK(c, hipMemcpyAsync(c->ph_buf, c->ph_snap, c->ph_bytes, hipMemcpyDeviceToDevice, c->stream));
     c->frame_open = false;        // the loop state no longer matches the photons: begin_frame comes next
     for (size_t r = 0; r < c->views.size(); ++r) {
@@ -1869,13 +1828,9 @@ extern "C" int mcrat_hip_get_photons_soa(mcrat_hip_ctx *c, const mcrat_hip_photo
     const int n = c->ph.n;
     int rc = flush_pending(c);
     if (rc) return rc;
-    PhotonDev &p = c->ph;
-    const double *cols[19] = {p.r0, p.r1, p.r2, p.p0, p.p1, p.p2, p.p3, p.c0, p.c1, p.c2, p.c3,
-                              p.s0, p.s1, p.s2, p.s3, p.num_scatt, p.weight, p.tau, p.tts};
-    double *dst[19] = {s->r0, s->r1, s->r2, s->p0, s->p1, s->p2, s->p3, s->comv_p0, s->comv_p1, s->comv_p2, s->comv_p3,
-                       s->s0, s->s1, s->s2, s->s3, s->num_scatt, s->weight, s->total_optical_depth, s->time_to_scatter};
-    for (int k = 0; k < 19; ++k)
-        if (dst[k]) HIPCHK(c, hipMemcpyAsync(dst[k], cols[k], sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+    const PhotonDev &p = c->ph;
+    for (int k = 0; k < N_ABI_COLS; ++k)
+        if (s->*SOA_COLS[k]) HIPCHK(c, hipMemcpyAsync(s->*SOA_COLS[k], p.*PHOTON_COLS[k], sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
     if (s->nearest_block_index) HIPCHK(c, hipMemcpyAsync(s->nearest_block_index, p.idx, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
     if (s->type) HIPCHK(c, hipMemcpyAsync(s->type, p.type, n, hipMemcpyDeviceToHost, c->stream));
     std::vector<unsigned char> flags;
@@ -1945,6 +1900,20 @@ extern "C" int mcrat_hip_convert_comptonized(mcrat_hip_ctx *c, int *num_converte
     return MCRAT_HIP_OK;
 }
 
+// the output block's scan (photon_plan.hpp, output_layout): the first output slot of each 256 slots, and the launcher's scratch
+static size_t output_scan_ints(long long nblk) { return (size_t)nblk + 1 + grid_scan_scratch_ints(nblk); }
+// the compacted output columns of the `total` photons with weight != 0 into the block at `base`; c->grid_count holds their number per 256 slots
+static int write_output(mcrat_hip_ctx *c, const OutputLayout &lay, void *base, long long nblk, unsigned long long total, OutputCols *oc)
+{
+    char *b = static_cast<char *>(base);
+    for (int k = 0; k < N_OUTPUT_COLS; ++k) oc->col[k] = reinterpret_cast<double *>(b + lay.col[k]);
+    oc->type = b + lay.type;
+    int *start = reinterpret_cast<int *>(b + lay.scan), *scratch = start + nblk + 1;
+    HIPCHK(c, launch_exclusive_scan(c->grid_count, nblk, start, scratch, (long long)total, c->stream));
+    HIPCHK(c, launch_output_write(c->ph, c->ph.n, start, *oc, c->stream));
+    return MCRAT_HIP_OK;
+}
+
 extern "C" int mcrat_hip_get_output(mcrat_hip_ctx *c, mcrat_hip_output_columns *out)
 {
     if (!c || !out) return MCRAT_HIP_EINVAL;
@@ -1959,27 +1928,18 @@ extern "C" int mcrat_hip_get_output(mcrat_hip_ctx *c, mcrat_hip_output_columns *
     HIPCHK(c, hipMemcpyAsync(&total, c->d_grid_total, sizeof total, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const int m = (int)total;
-    double *dst[17] = {out->p0, out->p1, out->p2, out->p3, out->comv_p0, out->comv_p1, out->comv_p2, out->comv_p3, out->r0, out->r1, out->r2,
-                       out->s0, out->s1, out->s2, out->s3, out->num_scatt, out->weight};
     bool any = out->type != nullptr;
-    for (double *d : dst) any = any || d;
+    for (int k = 0; k < N_OUTPUT_COLS; ++k) any = any || out->*OUTPUT_COLS[k];
     if (!any) { out->count = m; return MCRAT_HIP_OK; }            // sizing call
     if (out->count < m) { out->count = m; return MCRAT_HIP_EINVAL; }
     out->count = m;
     if (m == 0) return MCRAT_HIP_OK;
-    const size_t stride = align_up(sizeof(double) * (size_t)m, 256);
-    const size_t o_scan = 17 * stride + align_up((size_t)m, 256);
-    const size_t bytes = o_scan + sizeof(int) * ((size_t)nblk + 1 + grid_scan_scratch_ints(nblk));
-    if ((rc = ensure_aos(c, bytes))) return rc;
-    char *base = static_cast<char *>(c->aos_buf);
+    const OutputLayout lay = output_layout((size_t)m, output_scan_ints(nblk), 0);
+    if ((rc = ensure_aos(c, lay.total))) return rc;
     OutputCols oc;
-    for (int k = 0; k < 17; ++k) oc.col[k] = reinterpret_cast<double *>(base + k * stride);
-    oc.type = base + 17 * stride;
-    int *start = reinterpret_cast<int *>(base + o_scan), *scratch = start + nblk + 1;
-    HIPCHK(c, launch_exclusive_scan(c->grid_count, nblk, start, scratch, (long long)total, c->stream));
-    HIPCHK(c, launch_output_write(c->ph, n, start, oc, c->stream));
-    for (int k = 0; k < 17; ++k)
-        if (dst[k]) HIPCHK(c, hipMemcpyAsync(dst[k], oc.col[k], sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = write_output(c, lay, c->aos_buf, nblk, total, &oc))) return rc;
+    for (int k = 0; k < N_OUTPUT_COLS; ++k)
+        if (out->*OUTPUT_COLS[k]) HIPCHK(c, hipMemcpyAsync(out->*OUTPUT_COLS[k], oc.col[k], sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
     if (out->type) HIPCHK(c, hipMemcpyAsync(out->type, oc.type, (size_t)m, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return MCRAT_HIP_OK;
@@ -1995,8 +1955,8 @@ struct mcrat_hip_outbox {
     hipStream_t copy = nullptr;
     hipEvent_t staged = nullptr, landed = nullptr;
     void *d_buf = nullptr, *h_buf = nullptr;
-    size_t cap = 0;
-    size_t o_rec = 0, o_cols = 0, col_stride = 0;
+    size_t d_bytes = 0, h_bytes = 0;
+    OutputLayout lay{};               // of the last post, in both buffers
     int n_records = 0, n_output = 0;
     bool posted = false, have_records = false, have_output = false;
 };
@@ -2046,43 +2006,24 @@ extern "C" int mcrat_hip_outbox_post(mcrat_hip_ctx *c, mcrat_hip_outbox *b, int 
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     const size_t m = (size_t)total;
-    const size_t rec_bytes = want_records ? align_up(sizeof(mcrat_hip_photon) * (size_t)n, 256) : 0;
-    const size_t stride = align_up(sizeof(double) * (m ? m : 1), 256);
-    const size_t cols_bytes = want_output ? 17 * stride + align_up(m ? m : 1, 256) : 0;
-    const size_t scan_bytes = want_output ? align_up(sizeof(int) * ((size_t)nblk + 1 + grid_scan_scratch_ints(nblk)), 256) : 0;
-    const size_t need = rec_bytes + cols_bytes + scan_bytes;
-    if (need > b->cap) {
-        const size_t cap = need + need / 4;
-        if (b->d_buf) (void)hipFree(b->d_buf);
-        if (b->h_buf) (void)hipHostFree(b->h_buf);
-        b->d_buf = b->h_buf = nullptr;
-        b->cap = 0;
-        HIPCHK(c, hipMalloc(&b->d_buf, cap));
-        HIPCHK(c, hipHostMalloc(&b->h_buf, cap, hipHostMallocDefault));
-        b->cap = cap;
-    }
-    char *d = static_cast<char *>(b->d_buf), *h = static_cast<char *>(b->h_buf);
-    b->o_rec = 0; b->o_cols = rec_bytes; b->col_stride = stride;
+    const OutputLayout lay = output_layout(m, output_scan_ints(nblk), want_records ? n : 0, want_output != 0);
+    const size_t room = lay.total > b->d_bytes ? lay.total + lay.total / 4 : lay.total;        // (grown with a quarter to spare)
+    if ((rc = ensure_device_bytes(c, &b->d_buf, &b->d_bytes, room)) || (rc = ensure_host_bytes(c, &b->h_buf, &b->h_bytes, room))) return rc;
+    char *d = static_cast<char *>(b->d_buf);
+    b->lay = lay;
     b->n_records = want_records ? n : 0;
     b->n_output = (int)m;
     b->have_records = want_records != 0;
     b->have_output = want_output != 0;
     if (want_records) {
-        HIPCHK(c, hipMemsetAsync(d, 0, rec_bytes, c->stream));            // the bytes between the members: zero
-        HIPCHK(c, launch_soa_to_aos(c->ph, d, 0, n, c->stream));
+        HIPCHK(c, hipMemsetAsync(d + lay.rec, 0, lay.rec_bytes, c->stream));                   // the bytes between the members: zero
+        HIPCHK(c, launch_soa_to_aos(c->ph, d + lay.rec, 0, n, c->stream));
     }
-    if (want_output && m > 0) {
-        OutputCols oc;
-        for (int k = 0; k < 17; ++k) oc.col[k] = reinterpret_cast<double *>(d + b->o_cols + k * stride);
-        oc.type = d + b->o_cols + 17 * stride;
-        int *start = reinterpret_cast<int *>(d + rec_bytes + cols_bytes), *scratch = start + nblk + 1;
-        HIPCHK(c, launch_exclusive_scan(c->grid_count, nblk, start, scratch, (long long)total, c->stream));
-        HIPCHK(c, launch_output_write(c->ph, n, start, oc, c->stream));
-    }
+    OutputCols oc;
+    if (want_output && m > 0 && (rc = write_output(c, lay, d, nblk, total, &oc))) return rc;
     HIPCHK(c, hipEventRecord(b->staged, c->stream));
     HIPCHK(c, hipStreamWaitEvent(b->copy, b->staged, 0));
-    const size_t bytes = rec_bytes + (want_output && m > 0 ? cols_bytes : 0);
-    if (bytes) HIPCHK(c, hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, b->copy));
+    if (lay.copy_bytes) HIPCHK(c, hipMemcpyAsync(b->h_buf, d, lay.copy_bytes, hipMemcpyDeviceToHost, b->copy));
     HIPCHK(c, hipEventRecord(b->landed, b->copy));
     b->posted = true;
     return MCRAT_HIP_OK;
@@ -2095,17 +2036,12 @@ extern "C" int mcrat_hip_outbox_wait(mcrat_hip_outbox *b, const mcrat_hip_photon
     if (hipSetDevice(b->device) != hipSuccess) return MCRAT_HIP_ENODEV;       // (the caller may be a thread of its own)
     if (hipEventSynchronize(b->landed) != hipSuccess) return MCRAT_HIP_EHIP;
     char *h = static_cast<char *>(b->h_buf);
-    if (records) *records = b->have_records ? reinterpret_cast<const mcrat_hip_photon *>(h + b->o_rec) : nullptr;
+    if (records) *records = b->have_records ? reinterpret_cast<const mcrat_hip_photon *>(h + b->lay.rec) : nullptr;
     if (n_records) *n_records = b->n_records;
     if (cols) {
         memset(cols, 0, sizeof *cols);
         cols->count = b->have_output ? b->n_output : 0;
-        if (b->have_output && b->n_output > 0) {
-            double **dst[17] = {&cols->p0, &cols->p1, &cols->p2, &cols->p3, &cols->comv_p0, &cols->comv_p1, &cols->comv_p2, &cols->comv_p3, &cols->r0, &cols->r1,
-                                &cols->r2, &cols->s0, &cols->s1, &cols->s2, &cols->s3, &cols->num_scatt, &cols->weight};
-            for (int k = 0; k < 17; ++k) *dst[k] = reinterpret_cast<double *>(h + b->o_cols + k * b->col_stride);
-            cols->type = h + b->o_cols + 17 * b->col_stride;
-        }
+        if (b->have_output && b->n_output > 0) bind_output(b->lay, h, cols);
     }
     return MCRAT_HIP_OK;
 }
@@ -2290,8 +2226,7 @@ extern "C" int mcrat_hip_pool_create(mcrat_hip_ctx *c, int n_ranks, int slots_pe
     for (int r = 0; r < n_ranks; ++r) { c->h_rstates[r].done = 1; c->h_rstates[r].skip_idx = -1; c->h_rstates[r].last_scattered_index = -1; }
     HIPCHK(c, hipMemcpyAsync(c->d_rstates, c->h_rstates, sizeof(LoopState) * (size_t)n_ranks, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->have_photons = true;
-    c->frame_open = false;
+    photons_are_set(c);
     return MCRAT_HIP_OK;
 }
 
@@ -2340,6 +2275,7 @@ extern "C" int mcrat_hip_pool_begin_frames(mcrat_hip_ctx *c, const int *open, co
 {
     if (!c || !open || !seeds || !time_now || !remaining_time) return MCRAT_HIP_EINVAL;
     if (!c->is_pool) return MCRAT_HIP_ESTATE;
+    if (int rc_ = capture_refuses(c, "pool_begin_frames")) return rc_;
     if (!c->have_hydro) return MCRAT_HIP_ESTATE;
     if (c->cfg.tau_calculation == MCRAT_HIP_TAU_TABLE && !c->d_hot_table) {
         c->last_error = "TAU_CALCULATION == TABLE needs mcrat_hip_set_hot_cross_section first";
@@ -2792,7 +2728,7 @@ static int frames_check(mcrat_hip_ctx *c, const mcrat_hip_frame_plan *p, const m
 {
     if (!c || !p || !stats || p->n_frames <= 0 || !p->open || !p->seeds || !p->time_now || !p->remaining_time) return MCRAT_HIP_EINVAL;
     if (p->chain_clock && !p->frame_end) return MCRAT_HIP_EINVAL;
-    if (c->selected_frame >= 0) { c->last_error = "a captured frame is selected (mcrat_hip_pool_select_frame(pool, -1) first)"; return MCRAT_HIP_ESTATE; }
+    if (int rc_ = capture_refuses(c, "pool_run_frames")) return rc_;
     if (!c->is_pool) return MCRAT_HIP_ESTATE;
     if (!c->have_hydro) return MCRAT_HIP_ESTATE;
     if (c->cfg.cyclosynchrotron_switch) { c->last_error = "CYCLOSYNCHROTRON_SWITCH is on: its hook needs the host between passes, one frame per call (mcrat_hip_pool_scatter_frames_cyclosynch)"; return MCRAT_HIP_ESTATE; }
@@ -2901,23 +2837,17 @@ static int frames_queue_dev(mcrat_hip_ctx *c, const mcrat_hip_frame_plan *p, con
         HIPCHK(c, hipHostGetDevicePointer(&mapped, c->h_fq, 0));
         fq->records = lay.records(mapped);
     }
-    fq->snap_delta = p->restore_each_frame ? (long long)(static_cast<char *>(c->ph_snap) - static_cast<char *>(c->ph_buf)) : 0;
+    fq->snap_delta = p->restore_each_frame ? image_delta(c->ph_snap, c->ph_buf, 0, c->ph_bytes) : 0;
     c->cap_frames = 0;
     if (p->capture_frames && F > 1) {
-        const size_t need = c->ph_bytes * (size_t)(F - 1);
-        if (c->ph_cap_bytes < need) {
-            if (c->ph_cap) { HIPCHK(c, hipFree(c->ph_cap)); c->ph_cap = nullptr; c->ph_cap_bytes = 0; }
-            HIPCHK(c, hipMalloc(&c->ph_cap, need));
-            c->ph_cap_bytes = need;
-        }
-        fq->capture_delta = (long long)(static_cast<char *>(c->ph_cap) - static_cast<char *>(c->ph_buf));
-        fq->capture_stride = (long long)c->ph_bytes;
+        if (int rc = ensure_device_bytes(c, &c->ph_cap, &c->ph_cap_bytes, c->ph_bytes * (size_t)(F - 1))) return rc;
+        fq->capture_delta = image_delta(c->ph_cap, c->ph_buf, 0, c->ph_bytes);
+        fq->capture_stride = (long long)c->ph_bytes;          // (image_delta's block_bytes: the kernel adds frame * capture_stride itself)
         c->cap_frames = F - 1;
         // a capture holds the slots [0, list_capacity) of the lists that were open in its frame; every other slot must read as the empty slot it is in
         // the live lists (printPhotons' compaction keeps weight != 0 over the whole pool): the weight column starts from zero
         for (int f = 0; f < F - 1; ++f)
-            HIPCHK(c, hipMemsetAsync(reinterpret_cast<char *>(c->ph.weight) + fq->capture_delta + (long long)f * fq->capture_stride, 0,
-                                     sizeof(double) * (size_t)c->ph.n, c->stream));
+            HIPCHK(c, hipMemsetAsync(shift_photons(c->ph, image_delta(c->ph_cap, c->ph_buf, f, c->ph_bytes)).weight, 0, sizeof(double) * (size_t)c->ph.n, c->stream));
     }
     return MCRAT_HIP_OK;
 }
@@ -2982,7 +2912,8 @@ static int frames_run_one_by_one(mcrat_hip_ctx *c, const mcrat_hip_frame_plan *p
     if (rc) return rc;
     double *d_t = static_cast<double *>(c->aos_buf), *d_rem = d_t + R;
     int *d_open = reinterpret_cast<int *>(d_rem + R);
-    const long long snap = p->restore_each_frame ? (long long)(static_cast<char *>(c->ph_snap) - static_cast<char *>(c->ph_buf)) : 0;
+    const char *snap = static_cast<const char *>(c->ph_snap);
+    char *live = static_cast<char *>(c->ph_buf);
     rl.desc = c->d_desc;
     for (int f = 0; f < F; ++f) {
         bool any = false, all_lists = true;                               // (every list that exists takes part: the whole pool is restored in one copy)
@@ -2999,13 +2930,11 @@ static int frames_run_one_by_one(mcrat_hip_ctx *c, const mcrat_hip_frame_plan *p
             t_now[(size_t)r] = items[t].time_now; t_rem[(size_t)r] = items[t].remaining_time;
             if (p->chain_clock && f > first[r]) { t_now[(size_t)r] = rec[t - R].time_now; t_rem[(size_t)r] = items[t].frame_end - t_now[(size_t)r]; }
             if (p->restore_each_frame && !all_lists) {                    // the list's window of every column back from the snapshot
-                const size_t b0 = (size_t)r * (size_t)c->rank_stride, len = (size_t)v->ph.n;
-                char *col0 = reinterpret_cast<char *>(c->ph.r0 + b0);
-                HIPCHK(c, hipMemcpy2DAsync(col0, sizeof(double) * c->ph.col_stride, col0 + snap, sizeof(double) * c->ph.col_stride, sizeof(double) * len,
-                                           24, hipMemcpyDeviceToDevice, c->stream));
-                HIPCHK(c, hipMemcpyAsync(c->ph.idx + b0, reinterpret_cast<char *>(c->ph.idx + b0) + snap, sizeof(int) * len, hipMemcpyDeviceToDevice, c->stream));
-                HIPCHK(c, hipMemcpyAsync(c->ph.flags + b0, reinterpret_cast<char *>(c->ph.flags + b0) + snap, len, hipMemcpyDeviceToDevice, c->stream));
-                HIPCHK(c, hipMemcpyAsync(c->ph.type + b0, reinterpret_cast<char *>(c->ph.type + b0) + snap, len, hipMemcpyDeviceToDevice, c->stream));
+                CopyExtent ext[N_WINDOW_EXTENTS];
+                window_extents(c->ph_lay, (size_t)r * (size_t)c->rank_stride, (size_t)v->ph.n, ext);
+                for (const CopyExtent &e : ext)
+                    if (e.rows > 1) HIPCHK(c, hipMemcpy2DAsync(live + e.off, e.pitch, snap + e.off, e.pitch, e.width, e.rows, hipMemcpyDeviceToDevice, c->stream));
+                    else HIPCHK(c, hipMemcpyAsync(live + e.off, snap + e.off, e.width, hipMemcpyDeviceToDevice, c->stream));
             }
         }
         if (!any) continue;
@@ -3019,7 +2948,7 @@ static int frames_run_one_by_one(mcrat_hip_ctx *c, const mcrat_hip_frame_plan *p
         for (int r = 0; r < R; ++r)
             if (op[(size_t)r]) rec[(size_t)f * R + r].from_state(c->h_rstates[r]);
         if (c->cap_frames > 0 && f < F - 1)               // the pool as frame f leaves it
-            HIPCHK(c, hipMemcpyAsync(static_cast<char *>(c->ph_cap) + (size_t)f * c->ph_bytes, c->ph_buf, c->ph_bytes, hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(live + image_delta(c->ph_cap, live, f, c->ph_bytes), live, c->ph_bytes, hipMemcpyDeviceToDevice, c->stream));
     }
     // the lists' descriptions as a queue launch leaves them: every list of the plan with its length, also one that sat the last frame out
     // (mcrat_hip_rank_stats prices a list's passes with it)
@@ -3127,12 +3056,7 @@ extern "C" int mcrat_hip_pool_select_frame(mcrat_hip_ctx *c, int frame)
     if (frame < 0) return MCRAT_HIP_OK;
     if (frame >= c->cap_frames || !c->ph_cap) { c->last_error = "pool_select_frame: no capture of that frame (mcrat_hip_frame_plan.capture_frames; the last frame is the live lists)"; return MCRAT_HIP_ESTATE; }
     c->ph_live = c->ph;
-    const long long delta = (static_cast<char *>(c->ph_cap) - static_cast<char *>(c->ph_buf)) + (long long)frame * (long long)c->ph_bytes;
-    auto move = [&](auto *&ptr) { ptr = reinterpret_cast<std::remove_reference_t<decltype(ptr)>>(reinterpret_cast<char *>(ptr) + delta); };
-    PhotonDev &q = c->ph;
-    move(q.r0); move(q.r1); move(q.r2); move(q.p0); move(q.p1); move(q.p2); move(q.p3); move(q.c0); move(q.c1); move(q.c2); move(q.c3);
-    move(q.s0); move(q.s1); move(q.s2); move(q.s3); move(q.num_scatt); move(q.weight); move(q.tau); move(q.tts); move(q.u0); move(q.u1); move(q.u2);
-    move(q.ntau); move(q.tau_next); move(q.idx); move(q.flags); move(q.type);
+    c->ph = shift_photons(c->ph_live, image_delta(c->ph_cap, c->ph_buf, frame, c->ph_bytes));
     c->selected_frame = frame;
     return MCRAT_HIP_OK;
 }
@@ -3140,7 +3064,7 @@ extern "C" int mcrat_hip_pool_select_frame(mcrat_hip_ctx *c, int frame)
 extern "C" int mcrat_hip_run(mcrat_hip_ctx *c, long long max_iterations, mcrat_hip_frame_stats *stats)
 {
     if (!c) return MCRAT_HIP_EINVAL;
-    if (c->selected_frame >= 0) { c->last_error = "a captured frame is selected (mcrat_hip_pool_select_frame(pool, -1) first)"; return MCRAT_HIP_ESTATE; }
+    if (int rc_ = capture_refuses(c, "run")) return rc_;
     if (c->is_pool) {                              // every list whose view has opened a frame (or the pool's own begin_frame: all)
         if (!c->have_hydro) return MCRAT_HIP_ESTATE;
         if (c->cfg.cyclosynchrotron_switch) { c->last_error = "CYCLOSYNCHROTRON_SWITCH is on: run the views one by one (mcrat_hip_scatter_frame_cyclosynch)"; return MCRAT_HIP_ESTATE; }
@@ -3289,6 +3213,7 @@ extern "C" int mcrat_hip_pool_propagate_frames_fast(mcrat_hip_ctx *c, const int 
 {
     if (!c || !open || !seeds || !time_now || !remaining_time) return MCRAT_HIP_EINVAL;
     if (!c->is_pool) return MCRAT_HIP_ESTATE;
+    if (int rc_ = capture_refuses(c, "pool_propagate_frames_fast")) return rc_;
     if (c->d_pool_tapes) { c->last_error = "the pool holds tapes of uniforms (mcrat_hip_pool_set_rng_tapes): FAST mode has no tape build"; return MCRAT_HIP_ESTATE; }
     int rc = fast_refusals(c);
     if (rc) return rc;
@@ -3827,6 +3752,7 @@ extern "C" int mcrat_hip_pool_scatter_frames_cyclosynch(mcrat_hip_ctx *c, const 
 {
     if (!c || !cs || !lists || !counts || cs->b_field_calc < 0 || cs->b_field_calc > 2 || max_photons <= 0 || !(fps > 0)) return MCRAT_HIP_EINVAL;
     if (!c->is_pool) return MCRAT_HIP_ESTATE;
+    if (int rc_ = capture_refuses(c, "pool_scatter_frames_cyclosynch")) return rc_;
     if (!c->cfg.cyclosynchrotron_switch) { c->last_error = "the pool was created with cyclosynchrotron_switch = 0"; return MCRAT_HIP_ESTATE; }
     if (c->d_pool_tapes) { c->last_error = "the pool holds tapes of uniforms (mcrat_hip_pool_set_rng_tapes): the cyclo-synchrotron hook has no tape build"; return MCRAT_HIP_ESTATE; }
     if (!c->have_hydro || !c->hcol_buf) return MCRAT_HIP_ESTATE;

@@ -1108,6 +1108,7 @@ int mcrat_host_run_ranks(mcrat_hip_ctx *pool, mcrat_host_rank *ranks, int n_rank
             if (ranks[r].state == 1) { ranks[r].state = 2; ranks[r].frame += 1; }
             else if (ranks[r].state == 0 || ranks[r].state == 4) { ranks[r].state = 2; ranks[r].frame += 1; }      /* its injection frame lies beyond last_frm: nothing to scatter in */
     }
+    if (rc) (void)mcrat_hip_pool_select_frame(pool, -1);   /* every error exit of the loop above comes by here: the pool is left on its live lists, not on a capture */
     if (wr) {                                              /* the last frames' files, then the writer goes */
         if (wr->started) {
             const double tb = wall_ms();
