@@ -825,6 +825,58 @@ int mcrat_hip_observe(mcrat_hip_ctx *ctx, const mcrat_hip_observer *obs, double 
 int mcrat_hip_pool_observe(mcrat_hip_ctx *pool, const mcrat_hip_observer *obs, const double *time_now /* [n_ranks] */, mcrat_hip_observation *out);
 int mcrat_hip_observe_path(const mcrat_hip_ctx *ctx);
 
+/* line-of-sight optical depths and photospheres ---------------------------------
+ * A sightline is the straight ray from x_0 = (r0, r1, r2) along the unit vector of a photon 4-momentum (p0, p1, p2, p3) through ONE frozen staged
+ * hydro frame; the fluid is piecewise constant per cell and sampled at step midpoints:
+ *     ipn = 1 / sqrt((p1*p1 + p2*p2) + p3*p3);   n = (p1*ipn, p2*ipn, p3*ipn);   tau = 0;  path = 0;  k = 0
+ *     loop:  if k == max_steps                                    -> status STEP_CAP, stop
+ *            rho = sqrt((x*x + y*y) + z*z);  h = step_frac * rho;  if (!(h > h_min)) h = h_min
+ *            m = (x + (0.5*h)*n_x, y + (0.5*h)*n_y, z + (0.5*h)*n_z)
+ *            m outside the domain (the loop's strict test) or in no cell   -> status LEFT_MESH, stop
+ *            kappa [1/cm]: the optical depth per cm of the photon in the lowest-index cell that holds m, the cell's velocity taken at the azimuth
+ *                   of m, as the loop computes it; TAU_CALCULATION == TABLE: with the thermal cross section looked up at the photon's comoving
+ *                   energy in that cell and the cell's temperature -- where the reference would integrate afresh (off the table at a covered or
+ *                   higher temperature)                           -> status OFF_TABLE, stop (no integral is taken here)
+ *            tau += kappa*h;  path += h;  x += h*n_x;  y += h*n_y;  z += h*n_z;  k += 1
+ *            if tau >= tau_stop                                   -> status OPAQUE, stop          (tau_stop = +inf: never)
+ * Per ray: tau, path, steps (= k) and status -- 0 SKIPPED, 1 LEFT_MESH, 2 OPAQUE, 3 STEP_CAP, 4 OFF_TABLE; n_status counts the rays per status.
+ * Every position expression is evaluated in exactly this order in IEEE double, with correctly rounded division and square root and without
+ * contraction: steps, path and every decision that does not hang on tau are the same as the same expressions in host code.  A kappa that is not
+ * a number (a cell at rest: 0/0, as in the reference's cosine) goes into tau as it is.
+ * Surface (surface_level >= 0; negative: off): a ray with status LEFT_MESH has the total T = tau and the partial sums S_k (tau after k counted
+ * steps, S_0 = 0); surface_step is the smallest k with (T - S_k) <= surface_level and surface_r0 .. r2 is x_k -- the point from which at most
+ * surface_level of optical depth is left to the edge of the frame: the photosphere for level 1.  surface_step == 0: the start is already outside
+ * the surface.  Every other ray -- another status, the surface off, a T that is not a number -- gets surface_step = -1 and NaN positions.
+ *   mcrat_hip_sightline_rays           the caller's n rays (host arrays).
+ *   mcrat_hip_sightline_photons        the resident photons of one list (a stand-alone context, or a view of a pool): outputs of
+ *                                      mcrat_hip_num_photon_slots entries.  A slot is marched when it is part of the list, weight != 0 and its type
+ *                                      is neither 'p' nor 'N' (as the mock observations count it), from its r0 .. r2 along its p0 .. p3; every other
+ *                                      slot gets status SKIPPED, tau = path = 0, steps = 0.  A pending advance is flushed first; no column changes.
+ *   mcrat_hip_pool_sightline_photons   every slot of a pool in one launch: mcrat_hip_num_photon_slots(pool) entries, list r from r * the pool's
+ *                                      slots per list on.  It reads what mcrat_hip_pool_observe reads.
+ * hydro: the context whose staged frame the rays cross; NULL: ctx's own.  In a run the staged frame is only the photons' slab, which a ray leaves
+ * at once: a caller who wants the optical depth to the edge of the simulation stages the whole frame on a second context and passes it.  It must
+ * be on the same device with the same DIMENSIONS, GEOMETRY and TAU_CALCULATION (MCRAT_HIP_EINVAL otherwise).
+ * MCRAT_HIP_EINVAL, with its own text in mcrat_hip_last_error, checked in this order: n <= 0; step_frac negative or not finite; h_min not finite or
+ * <= 0; max_steps outside 1 .. 1048576; tau_stop NaN or <= 0; surface_level NaN or +inf.  MCRAT_HIP_ESTATE: no staged frame; no photons (the photon
+ * forms); TABLE without a cross-section table.  MCRAT_HIP_SIGHTLINE_REFILL=0|1 in the environment picks how rays are dealt to the kernel's lanes
+ * (1: a lane whose ray has ended takes the next unclaimed one); the outputs do not depend on it.  Every call synchronises before it returns. */
+#define MCRAT_HIP_SIGHTLINE_SKIPPED 0
+#define MCRAT_HIP_SIGHTLINE_LEFT_MESH 1
+#define MCRAT_HIP_SIGHTLINE_OPAQUE 2
+#define MCRAT_HIP_SIGHTLINE_STEP_CAP 3
+#define MCRAT_HIP_SIGHTLINE_OFF_TABLE 4
+typedef struct mcrat_hip_sightline_params { double step_frac, h_min; int max_steps; double tau_stop, surface_level; } mcrat_hip_sightline_params;
+typedef struct mcrat_hip_sightlines {       /* host pointers, [n]; any may be NULL */
+    double *tau, *path; int *steps, *status; int *surface_step; double *surface_r0, *surface_r1, *surface_r2;
+    long long n_status[5];
+} mcrat_hip_sightlines;
+int mcrat_hip_sightline_rays(mcrat_hip_ctx *ctx, const mcrat_hip_ctx *hydro /* or NULL */, const mcrat_hip_sightline_params *params, int n,
+                             const double *r0, const double *r1, const double *r2, const double *p0, const double *p1, const double *p2,
+                             const double *p3 /* host arrays [n] */, mcrat_hip_sightlines *out);
+int mcrat_hip_sightline_photons(mcrat_hip_ctx *ctx, const mcrat_hip_ctx *hydro, const mcrat_hip_sightline_params *params, mcrat_hip_sightlines *out);
+int mcrat_hip_pool_sightline_photons(mcrat_hip_ctx *pool, const mcrat_hip_ctx *hydro, const mcrat_hip_sightline_params *params, mcrat_hip_sightlines *out);
+
 /* introspection used by bench.py / tests -------------------------------------- */
 int mcrat_hip_synchronize(mcrat_hip_ctx *ctx);
 size_t mcrat_hip_device_bytes(const mcrat_hip_ctx *ctx);   /* HBM held by the context */

@@ -19,6 +19,7 @@
 #include "device_types.hpp"
 #include "launch.hpp"
 #include "observe_plan.hpp"
+#include "sightline_plan.hpp"
 #include "photon_cols.hpp"
 #include "photon_plan.hpp"
 #include "rng.hpp"
@@ -165,6 +166,8 @@ struct mcrat_hip_ctx {
     void *obs_buf = nullptr;          // mcrat_hip_observe: the cube, the per-observer counters and the staged inputs (observe_plan.hpp); a view uses its pool's
     size_t obs_bytes = 0;
     int obs_path = 0;                 // the accumulation path of the last observation (ObservePath)
+    void *sl_buf = nullptr;           // mcrat_hip_sightline_*: the output block and the caller's rays (sightline_plan.hpp); a view uses its pool's
+    size_t sl_bytes = 0;
 
     // profiling
     std::vector<hipEvent_t> ev;
@@ -419,6 +422,7 @@ extern "C" void mcrat_hip_destroy(mcrat_hip_ctx *c)
     if (c->d_red) (void)hipFree(c->d_red);
     if (c->h_red) (void)hipHostFree(c->h_red);
     if (c->obs_buf) (void)hipFree(c->obs_buf);
+    if (c->sl_buf) (void)hipFree(c->sl_buf);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -443,7 +447,7 @@ extern "C" size_t mcrat_hip_device_bytes(const mcrat_hip_ctx *c)
 {
     if (!c) return 0;
     return c->ph_bytes + c->hy_bytes + c->grid_bytes + c->grid_count_cap * sizeof(unsigned) + sizeof(Shortlist) + sizeof(LoopState) + c->partials_bytes +
-           sizeof(ReducePartial) * mcrat_hip_ctx::RED_BLOCKS + c->obs_bytes;
+           sizeof(ReducePartial) * mcrat_hip_ctx::RED_BLOCKS + c->obs_bytes + c->sl_bytes;
 }
 
 extern "C" int mcrat_hip_create_hot_cross_section(mcrat_hip_ctx *c, double *thermal_table, int n_ph_e, int n_t, double log_ph_e_min,
@@ -4142,6 +4146,100 @@ extern "C" int mcrat_hip_pool_observe(mcrat_hip_ctx *c, const mcrat_hip_observer
 }
 
 extern "C" int mcrat_hip_observe_path(const mcrat_hip_ctx *c) { return c ? c->obs_path : 0; }
+
+// ---------------------------------------------------------------------------------------------- line-of-sight optical depths
+// n rays marched through a staged frame (sightline_plan.hpp, sightline.hip) and the per-ray results read back.  rays: the caller's seven host
+// arrays r0, r1, r2, p0 .. p3, or nullptr -- then the rays are the n slots of c->ph.  hydro: the context whose staged frame the rays cross, or
+// nullptr for c's own.  The device block belongs to the pool when c is a view.
+static int sightline_run(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_sightline_params *params, int n, const double *const *rays,
+                         mcrat_hip_sightlines *out)
+{
+    const mcrat_hip_ctx *h = hydro ? hydro : c;
+    if (!h->have_hydro) { c->last_error = "sightline: no staged hydro frame"; return MCRAT_HIP_ESTATE; }
+    if (h != c && (h->kc.dimensions != c->kc.dimensions || h->kc.geometry != c->kc.geometry || h->kc.table != c->kc.table || h->cfg.device != c->cfg.device)) {
+        c->last_error = "sightline: a frame staged on a context with other switches (DIMENSIONS, GEOMETRY, TAU_CALCULATION) or on another device";
+        return MCRAT_HIP_EINVAL;
+    }
+    if (c->kc.table && !h->hy.hot_table) {
+        c->last_error = "TAU_CALCULATION == TABLE needs mcrat_hip_set_hot_cross_section first";
+        return MCRAT_HIP_ESTATE;
+    }
+    const SightlineParams p{params->step_frac, params->h_min, params->max_steps, params->tau_stop, params->surface_level};
+    int forced;
+    SightlinePlan plan;
+    const SightlineRefusal bad_switch = sightline_refill_switch(getenv("MCRAT_HIP_SIGHTLINE_REFILL"), &forced);
+    SightlineRefusal why = sightline_plan(n, p, forced, &plan);
+    if (why == SIGHTLINE_OK) why = bad_switch;                   // (what the arguments are refused for comes first)
+    if (why != SIGHTLINE_OK) { c->last_error = sightline_refusal_text(why); return MCRAT_HIP_EINVAL; }
+
+    mcrat_hip_ctx *owner = c->parent ? c->parent : c;
+    HIPCHK(c, hipStreamSynchronize(c->stream));                  // (the block may be replaced: nothing may still read the old one)
+    if (h != c) HIPCHK(c, hipStreamSynchronize(h->stream));      // ... and the other context's frame is staged on its stream
+    int rc = ensure_device_bytes(c, &owner->sl_buf, &owner->sl_bytes, plan.ray_offset + (rays ? plan.ray_bytes : 0));
+    if (rc) return rc;
+    char *d = static_cast<char *>(owner->sl_buf);
+    const int blocks = sightline_grid(plan, device_cus(c));
+    SightlineDev a{};
+    a.n = n;
+    a.step_frac = p.step_frac; a.h_min = p.h_min; a.max_steps = p.max_steps; a.tau_stop = p.tau_stop; a.surface_level = p.surface_level;
+    a.head = reinterpret_cast<unsigned long long *>(d);
+    a.f8 = reinterpret_cast<double *>(d + plan.f8_offset);
+    a.i4 = reinterpret_cast<int *>(d + plan.i4_offset);
+    a.refill = plan.refill ? 1 : 0;
+    a.own_rays = plan.refill ? sightline_own_rays(n, blocks) : 0;
+    HIPCHK(c, hipMemsetAsync(d, 0, sizeof(unsigned long long) * SIGHTLINE_HEAD_WORDS, c->stream));
+    if (rays) {
+        double *d_ray = reinterpret_cast<double *>(d + plan.ray_offset);
+        for (int k = 0; k < SIGHTLINE_RAY_PLANES; ++k)
+            HIPCHK(c, hipMemcpyAsync(d_ray + (size_t)k * (size_t)n, rays[k], sizeof(double) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        a.ray = d_ray;
+    }
+    HIPCHK(c, launch_sightline(c->kc, c->ph, h->hy, a, blocks, c->stream));
+    double *f8[SIGHTLINE_F8_PLANES] = {out->tau, out->path, out->surface_r0, out->surface_r1, out->surface_r2};
+    int *i4[SIGHTLINE_I4_PLANES] = {out->steps, out->status, out->surface_step};
+    for (int k = 0; k < SIGHTLINE_F8_PLANES; ++k)
+        if (f8[k]) HIPCHK(c, hipMemcpyAsync(f8[k], d + sightline_f8_plane(plan, k), sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    for (int k = 0; k < SIGHTLINE_I4_PLANES; ++k)
+        if (i4[k]) HIPCHK(c, hipMemcpyAsync(i4[k], d + sightline_i4_plane(plan, k), sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    static_assert(sizeof(long long) == 8, "the status counts are read back as they are");
+    HIPCHK(c, hipMemcpyAsync(out->n_status, d, sizeof(long long) * SIGHTLINE_N_STATUS, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MCRAT_HIP_OK;
+}
+
+extern "C" int mcrat_hip_sightline_rays(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_sightline_params *params, int n, const double *r0,
+                                        const double *r1, const double *r2, const double *p0, const double *p1, const double *p2, const double *p3,
+                                        mcrat_hip_sightlines *out)
+{
+    if (!c || !params || !out) return MCRAT_HIP_EINVAL;
+    if (n > 0 && (!r0 || !r1 || !r2 || !p0 || !p1 || !p2 || !p3)) { c->last_error = "sightline: a null ray array"; return MCRAT_HIP_EINVAL; }
+    if (c->have_photons) {
+        int rc = flush_pending(c);
+        if (rc) return rc;
+    }
+    const double *const rays[SIGHTLINE_RAY_PLANES] = {r0, r1, r2, p0, p1, p2, p3};
+    return sightline_run(c, hydro, params, n, rays, out);
+}
+
+extern "C" int mcrat_hip_sightline_photons(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_sightline_params *params, mcrat_hip_sightlines *out)
+{
+    if (!c || !params || !out) return MCRAT_HIP_EINVAL;
+    if (!c->have_photons) return MCRAT_HIP_ESTATE;
+    if (c->is_pool) { c->last_error = "sightline: one list is a stand-alone context or a view of a pool (mcrat_hip_pool_sightline_photons takes the pool)"; return MCRAT_HIP_ESTATE; }
+    int rc = flush_pending(c);
+    if (rc) return rc;
+    return sightline_run(c, hydro, params, c->ph.n, nullptr, out);
+}
+
+extern "C" int mcrat_hip_pool_sightline_photons(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_sightline_params *params, mcrat_hip_sightlines *out)
+{
+    if (!c || !params || !out) return MCRAT_HIP_EINVAL;
+    if (!c->is_pool) return MCRAT_HIP_ESTATE;
+    // every slot of the pool, as mcrat_hip_pool_observe reads them: slots beyond a list's length and lists never created are not FLAG_VALID
+    int rc = flush_pending(c);
+    if (rc) return rc;
+    return sightline_run(c, hydro, params, c->ph.n, nullptr, out);
+}
 
 extern "C" int mcrat_hip_eval_function(mcrat_hip_ctx *c, int fn, int n, const double *in, double *out, uint64_t seed)
 {

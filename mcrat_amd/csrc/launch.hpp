@@ -120,6 +120,21 @@ struct ObserveDev {
     unsigned long long *n_accepted, *n_outside;   // [n_obs]
 };
 hipError_t launch_observe(const PhotonDev &ph, const ObserveDev &a, const ObservePlan &plan, bool stokes, int cus, hipStream_t stream);
+// line-of-sight optical depths (sightline.hip): n rays marched through the frame hy, one lane per ray.  The block's head -- five status counts and
+// the refill form's ray counter -- and the output planes are laid out as sightline_plan.hpp says; the caller zeroes the head and sizes the grid
+// (sightline_grid).  ray != nullptr: the caller's rays, seven planes of n doubles (r0, r1, r2, p0, p1, p2, p3); else the n slots of ph.
+struct SightlineDev {
+    int n;
+    double step_frac, h_min;
+    int max_steps;
+    double tau_stop, surface_level;
+    const double *ray;
+    unsigned long long *head;            // n_status[5], then the global ray counter
+    double *f8;                          // tau, path, surface_r0, surface_r1, surface_r2: n each
+    int *i4;                             // steps, status, surface_step: n each
+    int refill, own_rays;                // lane refill, and the rays of a workgroup's own range (sightline_own_rays)
+};
+hipError_t launch_sightline(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, const SightlineDev &a, int blocks, hipStream_t stream);
 hipError_t launch_init_states_multi(LoopState *ranks, int n_ranks, const int *open, const double *time_now, const double *remaining, hipStream_t stream);
 hipError_t launch_aos_to_soa(const void *aos, const PhotonDev &ph, int n, hipStream_t stream);
 // many lists of a rank pool at once: desc = `count` device records {int rank, int n, long long first record in aos}; the rest of each window is cleared

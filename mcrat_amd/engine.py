@@ -196,6 +196,21 @@ class Observation(C.Structure):
 
 OBSERVE_PATH_LDS, OBSERVE_PATH_GLOBAL = 1, 2      # mcrat_hip_observe_path
 
+
+class SightlineParams(C.Structure):
+    """mcrat_hip_sightline_params: how a sightline is stepped and where it stops"""
+    _fields_ = [("step_frac", C.c_double), ("h_min", C.c_double), ("max_steps", C.c_int), ("tau_stop", C.c_double), ("surface_level", C.c_double)]
+
+
+class Sightlines(C.Structure):
+    """mcrat_hip_sightlines: the per-ray outputs, each [n], and the rays per status"""
+    _fields_ = [("tau", _dp), ("path", _dp), ("steps", _ip), ("status", _ip), ("surface_step", _ip),
+                ("surface_r0", _dp), ("surface_r1", _dp), ("surface_r2", _dp), ("n_status", C.c_longlong * 5)]
+
+
+# a sightline's status (mcrat_hip_sightlines.status)
+SIGHTLINE_SKIPPED, SIGHTLINE_LEFT_MESH, SIGHTLINE_OPAQUE, SIGHTLINE_STEP_CAP, SIGHTLINE_OFF_TABLE = 0, 1, 2, 3, 4
+
 SCIENCE, CYLINDRICAL_OUTFLOW, SPHERICAL_OUTFLOW, STRUCTURED_SPHERICAL_OUTFLOW = 0, 1, 2, 3    # SIMULATION_TYPE, mcrat.h:30-33
 
 # every symbol include/mcrat_hip.h declares: (restype, argtypes)
@@ -295,6 +310,9 @@ SYMBOLS = {
     "mcrat_hip_observe": (C.c_int, [_ctx, C.POINTER(Observer), C.c_double, C.POINTER(Observation)]),
     "mcrat_hip_pool_observe": (C.c_int, [_ctx, C.POINTER(Observer), _dp, C.POINTER(Observation)]),
     "mcrat_hip_observe_path": (C.c_int, [_ctx]),
+    "mcrat_hip_sightline_rays": (C.c_int, [_ctx, _ctx, C.POINTER(SightlineParams), C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(Sightlines)]),
+    "mcrat_hip_sightline_photons": (C.c_int, [_ctx, _ctx, C.POINTER(SightlineParams), C.POINTER(Sightlines)]),
+    "mcrat_hip_pool_sightline_photons": (C.c_int, [_ctx, _ctx, C.POINTER(SightlineParams), C.POINTER(Sightlines)]),
     "mcrat_hip_synchronize": (C.c_int, [_ctx]),
     "mcrat_hip_device_bytes": (C.c_size_t, [_ctx]),
     "mcrat_hip_eval_function": (C.c_int, [_ctx, C.c_int, C.c_int, _dp, _dp, C.c_uint64]),
@@ -1006,6 +1024,46 @@ class Engine:
     def observe_path(self):
         """how the last observation of this context was accumulated: OBSERVE_PATH_LDS, OBSERVE_PATH_GLOBAL, 0: none yet"""
         return int(self.lib.mcrat_hip_observe_path(self.ctx))
+
+    # ---- line-of-sight optical depths and photospheres (include/mcrat_hip.h)
+    def _sightlines(self, what, n, call, step_frac, h_min, max_steps, tau_stop, surface_level):
+        par = SightlineParams(float(step_frac), float(h_min), int(max_steps), float(tau_stop), float(surface_level))
+        m = max(int(n), 0)
+        res = {"tau": np.zeros(m), "path": np.zeros(m), "steps": np.zeros(m, dtype=np.int32), "status": np.zeros(m, dtype=np.int32),
+               "surface_step": np.zeros(m, dtype=np.int32), "surface_r": np.zeros((3, m))}
+        out = Sightlines(res["tau"].ctypes.data_as(_dp), res["path"].ctypes.data_as(_dp), res["steps"].ctypes.data_as(_ip),
+                         res["status"].ctypes.data_as(_ip), res["surface_step"].ctypes.data_as(_ip),
+                         *[res["surface_r"][k].ctypes.data_as(_dp) for k in range(3)])
+        self._check(call(C.byref(par), C.byref(out)), what)
+        res["n_status"] = np.array(list(out.n_status), dtype=np.int64)
+        return res
+
+    def sightline_rays(self, r, p, step_frac, h_min, max_steps, tau_stop=np.inf, surface_level=-1.0, hydro=None):
+        """optical depth along straight rays through the staged frame (mcrat_hip_sightline_rays).  r: the starting points (r0, r1, r2), p: the
+        4-momenta (p0, p1, p2, p3), each a sequence of arrays of one length.  hydro: another Engine whose staged frame the rays cross (None: this
+        one's).  -> dict of per-ray arrays tau, path, steps, status (SIGHTLINE_*), surface_step, surface_r (3, n) and n_status (5,)"""
+        cols = [_f8(a).ravel() for a in list(r) + list(p)]
+        if len(cols) != 7 or any(len(a) != len(cols[0]) for a in cols):
+            raise ValueError("sightline_rays: r needs three and p four arrays of one length")
+        n, h = len(cols[0]), hydro.ctx if hydro is not None else None
+        ptrs = [a.ctypes.data_as(_dp) for a in cols]
+        return self._sightlines("sightline_rays", n, lambda par, out: self.lib.mcrat_hip_sightline_rays(self.ctx, h, par, n, *ptrs, out),
+                                step_frac, h_min, max_steps, tau_stop, surface_level)
+
+    def sightline_photons(self, step_frac, h_min, max_steps, tau_stop=np.inf, surface_level=-1.0, hydro=None):
+        """the same for this list's resident photons, one entry per slot; slots that are not observable come back SIGHTLINE_SKIPPED
+        (mcrat_hip_sightline_photons)"""
+        h = hydro.ctx if hydro is not None else None
+        n = int(self.lib.mcrat_hip_num_photon_slots(self.ctx))
+        return self._sightlines("sightline_photons", n, lambda par, out: self.lib.mcrat_hip_sightline_photons(self.ctx, h, par, out),
+                                step_frac, h_min, max_steps, tau_stop, surface_level)
+
+    def pool_sightline_photons(self, step_frac, h_min, max_steps, tau_stop=np.inf, surface_level=-1.0, hydro=None):
+        """every slot of the pool in one launch, list r from r * (slots per list) on (mcrat_hip_pool_sightline_photons)"""
+        h = hydro.ctx if hydro is not None else None
+        n = int(self.lib.mcrat_hip_num_photon_slots(self.ctx))
+        return self._sightlines("pool_sightline_photons", n, lambda par, out: self.lib.mcrat_hip_pool_sightline_photons(self.ctx, h, par, out),
+                                step_frac, h_min, max_steps, tau_stop, surface_level)
 
     def synchronize(self):
         self._check(self.lib.mcrat_hip_synchronize(self.ctx), "synchronize")
