@@ -15,20 +15,21 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmcrat_hip.so")
 ABI_HEADER = os.path.join("..", "..", "include", "mcrat_hip.h")        # the C ABI, relative to csrc
 KERNEL_TUS = ["kernels%s_d%d.hip" % (m, d) for m in ("", "_table") for d in (0, 1, 2)]   # kernels.hip per TAU_CALCULATION x DIMENSIONS
-SOURCES = KERNEL_TUS + ["launchers.hip", "grid_build.hip", "staging.hip", "inject.hip", "ingest.hip", "hot_table.hip", "functions.hip", "observe.hip", "sightline.hip", "engine.hip"]
-HEADERS = ["kernels.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp", "hydro_plan.hpp", "observe_plan.hpp", "sightline_plan.hpp", "photon_plan.hpp", "physics.hpp", "rng.hpp", "cs_device.hpp", ABI_HEADER]
+SOURCES = KERNEL_TUS + ["launchers.hip", "rank_launch.hip", "grid_build.hip", "staging.hip", "inject.hip", "ingest.hip", "hot_table.hip", "functions.hip", "observe.hip", "sightline.hip", "engine.hip"]
+HEADERS = ["kernels.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp", "hydro_plan.hpp", "rank_form_plan.hpp", "observe_plan.hpp", "sightline_plan.hpp", "photon_plan.hpp", "physics.hpp", "rng.hpp", "cs_device.hpp", ABI_HEADER]
 # -amdgpu-prealloc-sgpr-spill-vgprs: the loop kernels sit at 256 VGPRs with hundreds of scalar registers spilled to lanes of vector registers; with the
 #   compiler's default (those vector registers chosen after everything else is allocated) single instantiations wrote a wrong Stokes V -- another
 #   instantiation after every larger edit (round 3: 3-D spherical; round 4: 3-D polar; without the shadow draws: 3-D spherical again), every time cured
 #   by keeping the spilled scalars elsewhere (profiles/r04_s3_corruption_probe.txt).  Reserving the lane-spill registers up front costs nothing
 #   measurable (headline 0.493 vs 0.493 ms per frame, cfg5 the same, cfg3 3 %) and tests/test_gpu_instantiations.py is green in all 36 tuples x forms.
-# --offload-compress: the device code of ~420 instantiations of the loop kernel is 53 MB; compressed in the bundle 8 MB (the HIP runtime unpacks it
+# --offload-compress: the device code of 456 instantiations of the loop kernel is 53 MB; compressed in the bundle 8 MB (the HIP runtime unpacks it
 #   when the library is loaded).
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-fvisibility=hidden",
          "-mllvm", "-amdgpu-prealloc-sgpr-spill-vgprs=1", "--offload-compress"]
 OBJDIR = os.path.join(HERE, "_obj")
 _KERNEL_DEPS = ["kernels.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp", "hydro_plan.hpp", "physics.hpp", "rng.hpp", "cs_device.hpp"]
 DEPS = {"launchers.hip": ["launchers.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp", "hydro_plan.hpp"],
+        "rank_launch.hip": ["rank_launch.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp", "hydro_plan.hpp"],
         "grid_build.hip": ["grid_build.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp", "hydro_plan.hpp"],
         "staging.hip": ["staging.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp", "hydro_plan.hpp", ABI_HEADER],
         "inject.hip": ["inject.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp", "hydro_plan.hpp", "physics.hpp", "rng.hpp", "cs_device.hpp"],
@@ -42,9 +43,10 @@ DEPS = {"launchers.hip": ["launchers.hip", "device_types.hpp", "launch.hpp", "fr
                        ABI_HEADER]}
 for _tu in KERNEL_TUS:
     DEPS[_tu] = _KERNEL_DEPS + [_tu]
-for _deps in DEPS.values():       # hydro_plan.hpp reads the ABI's structs, so every unit that includes launch.hpp does
+for _deps in DEPS.values():       # hydro_plan.hpp reads the ABI's structs, so every unit that includes launch.hpp does; launch.hpp includes rank_form_plan.hpp
     if ABI_HEADER not in _deps:
         _deps.append(ABI_HEADER)
+    _deps.append("rank_form_plan.hpp")
 
 def hipcc():
     for c in (os.environ.get("HIPCC"), shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):

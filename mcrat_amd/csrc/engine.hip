@@ -2586,11 +2586,6 @@ template <class Launch>
 static int profiled(mcrat_hip_ctx *c, int launches, Launch &&launch) { return profiled(c, launches, launch, [] { return MCRAT_HIP_OK; }); }
 
 // virtual-rank mode: every launch gives each unfinished list up to `per_launch` passes of its own loop
-// Threads per list (launch.hpp).  Lists per CU is what the virtual-rank kernel's throughput hangs on (kernels.hip), so many
-// lists get 128-thread workgroups, four to a CU -- unless there are too few lists to fill the device that way, or the lists
-// are too long to keep in LDS, or the frames are optically thin: a thin frame is a dozen passes in which half the photons
-// change cell, i.e. slow-path throughput per list, and there 256 threads per list do better.  The engine cannot know the
-// optical depth before it has run a frame; it looks at the previous one (passes per list).
 // the device as the context has known it since its creation (a view asks its pool's)
 static const RankDeviceInfo *device_info(const mcrat_hip_ctx *c)
 {
@@ -2605,30 +2600,19 @@ static int device_cus(const mcrat_hip_ctx *c)
     return cus;
 }
 
+// MCRAT_HIP_RANK_BLOCK and MCRAT_HIP_RANK_FUSE as the block rules read them
+static RankEnv rank_env()
+{
+    RankEnv env;
+    if (const char *e = getenv("MCRAT_HIP_RANK_BLOCK")) { env.block_set = true; env.block = atoi(e); }
+    if (const char *e = getenv("MCRAT_HIP_RANK_FUSE")) { env.fuse_set = true; env.fuse = atoi(e); }
+    return env;
+}
+// threads per list and the fused pass for the next launches (rank_form_plan.hpp, rank_block_rule)
 static void choose_rank_block(mcrat_hip_ctx *c)
 {
-    if (const char *e = getenv("MCRAT_HIP_RANK_BLOCK")) {
-        c->rank_block = (atoi(e) == 128) ? 128 : (atoi(e) == 512 ? 512 : 256);
-        c->rank_fuse = c->rank_passes_per_list < 48.0;
-        if (const char *f = getenv("MCRAT_HIP_RANK_FUSE")) c->rank_fuse = atoi(f) != 0;
-        return;
-    }
-    const int cus = device_cus(c);
-    const bool many = c->n_ranks > 2 * cus && longest_rank_list(c) <= 1024;
-    // ... and, whatever the frame looks like, when there are many times more lists than the device holds at once: four lists per CU then
-    // overlap one list's walk with the others' passes all the time (10 246 lists, thin frames: cfg2 5.70 -> 4.96 ms, cfg3 8.44 -> 7.08 ms;
-    // 4098 lists 2.50 -> 2.32 ms; 2049 lists no difference; 1025 lists 0.83 -> 0.85 ms)
-    const bool very_many = c->n_ranks >= 12 * cus && longest_rank_list(c) <= 1024;
-    c->rank_block = ((many && c->rank_passes_per_list >= 48.0) || very_many) ? 128 : 256;
-    // lists of thousands of photons (sample_mc.par:21-22 allows 5000 per rank) of which there are about as many as CUs, or fewer: a list has its
-    // CU to itself whatever the workgroup size, so it gets 512 threads -- a pass takes half the trips (200 lists of 5000 photons, cfg2: 5.2 -> ms)
-    if (longest_rank_list(c) > 1088 && c->n_ranks <= cus + cus / 4) c->rank_block = 512;
-    // the build with the fused pass (kernels.hip, rank_loop_kernel<.., FUSE>) for frames that looked optically thin last time (or
-    // have not been seen yet): there most slots change cell between two events
-    // (not in spherical geometry: two slots' acos / atan2 side by side cost the fused build 50 B of scratch per lane, and the spherical
-    // benchmark frames run 2 % faster without it -- cfg3 at 1e7 photons 8.62 -> 8.43 ms; the cylindrical Stokes frame 1.07 -> 0.94 ms with it)
-    c->rank_fuse = c->rank_passes_per_list < 48.0 && c->kc.geometry != GEOM_SPHERICAL;
-    if (const char *e = getenv("MCRAT_HIP_RANK_FUSE")) c->rank_fuse = atoi(e) != 0;
+    const RankBlock b = rank_block_rule(c->n_ranks, device_cus(c), longest_rank_list(c), c->rank_passes_per_list, c->kc.geometry, rank_env());
+    c->rank_block = b.threads; c->rank_fuse = b.fuse;
 }
 
 // passes one list may take per launch: bounds one launch to a second or two even for the densest lists (4096: the first 60 frames of
@@ -2645,6 +2629,7 @@ static RankLaunch rank_launch_of(const mcrat_hip_ctx *c, const RankDesc *desc, l
     RankLaunch rl;
     rl.n_ranks = c->n_ranks; rl.rank_stride = c->rank_stride; rl.longest_list = longest_rank_list(c); rl.desc = desc;
     rl.threads = c->rank_block; rl.fuse = c->rank_fuse;
+    rl.no_lds_lists = getenv("MCRAT_HIP_NO_LDS_LISTS") != nullptr;    // (read per launch: tests flip it between the launches of one process)
     rl.max_passes = max_passes;
     rl.dev = device_info(c);
     return rl;
@@ -2857,7 +2842,8 @@ static int frames_queue_dev(mcrat_hip_ctx *c, const mcrat_hip_frame_plan *p, con
 }
 
 // Queue launches until every list is through its last frame: order the open items, one copy up, the launch, one copy down, and what the launch left
-// (frame_queue.hpp).  *unsupported: the launch form has no queue build (kernels.hip) and nothing has run.
+// (frame_queue.hpp).  The caller has asked the rule that the launch form has a queue build; *unsupported (hipErrorNotSupported from the first launch)
+// is left for the runtime refusing that build its LDS: nothing has run then.
 static int frames_run_queue(mcrat_hip_ctx *c, const FrameQueueLayout &lay, FrameQueueDev &fq, RankLaunch rl, bool host_records, QueueMarks &tm, bool *unsupported)
 {
     const int R = c->n_ranks, F = fq.n_frames;
@@ -3038,8 +3024,9 @@ extern "C" int mcrat_hip_pool_run_frames(mcrat_hip_ctx *c, const mcrat_hip_frame
     // passes one list may take per frame and launch (run_ranks' bound on a launch's duration)
     const RankLaunch rl = rank_launch_of(c, nullptr, rank_launch_cap());
     c->prof_step_ms = 0; c->prof_launches = 0;
-    // (MCRAT_HIP_NO_FRAME_QUEUE=1, A/B: the plan frame by frame; a pool that holds tapes: the tape build has no queue form)
-    bool one_by_one = env_flag("MCRAT_HIP_NO_FRAME_QUEUE") || c->d_pool_tapes != nullptr;
+    // (MCRAT_HIP_NO_FRAME_QUEUE=1, A/B: the plan frame by frame; a pool that holds tapes: the tape build has no queue form; nor have the 128- and
+    // 512-thread lists and those whose columns stay in HBM/L2: rank_form_plan.hpp)
+    bool one_by_one = env_flag("MCRAT_HIP_NO_FRAME_QUEUE") || c->d_pool_tapes != nullptr || rank_form_resolve(rank_form_request(c->kc, rl, true)).no_queue_build;
     if (!one_by_one && (rc = frames_run_queue(c, lay, fq, rl, host_records, tm, &one_by_one))) return rc;
     if (one_by_one && (rc = frames_run_one_by_one(c, p, lay, rl))) return rc;
     frames_publish(c, p, lay.records(c->h_fq), stats);
@@ -3609,18 +3596,11 @@ static int pcs_upload_hooks(PoolCsFrames &F)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return MCRAT_HIP_OK;
 }
-// 5. lists that change length: columns stay in HBM/L2 (longest = the window), so LDS does not limit the lists per CU; with more than
-// two lists per CU the 128-thread workgroups put four on one (cfg5 at 1e7 photons: 420 -> 380 ms per frame)
+// 5. threads per list (rank_form_plan.hpp, cs_rank_block_rule)
 static void pcs_choose_block(PoolCsFrames &F)
 {
-    mcrat_hip_ctx *c = F.c;
-    const int cus = device_cus(c);
-    c->rank_block = F.R > 2 * cus ? 128 : 256;
-    // ... and with eight and more per CU one wavefront per list (eight on a CU): no wave ever waits at a barrier for the one that walks
-    // the event (cfg5: 250 -> 230 ms per frame); only with the hook inside the loop (the hook kernel is written for 128 threads and more)
-    if (F.R > 8 * cus && !F.hook_kernel) c->rank_block = 64;
-    c->rank_fuse = false;
-    if (const char *e = getenv("MCRAT_HIP_RANK_BLOCK")) c->rank_block = (atoi(e) == 64) ? 64 : (atoi(e) == 128) ? 128 : 256;
+    const RankBlock b = cs_rank_block_rule(F.R, device_cus(F.c), F.hook_kernel, rank_env());
+    F.c->rank_block = b.threads; F.c->rank_fuse = b.fuse;
 }
 // 6. the loop.  The hook runs inside rank_loop_kernel (its CSH build: cs_hook_body right after the pass, the list goes on in the same launch); with
 // hook_kernel the lists park after such a pass instead and cs_replace_pool_kernel runs it between two launches.  Either way a list only stays

@@ -6,6 +6,8 @@
 // The entries from RCP_NR on evaluate the loop's OWN arithmetic forms (cell_staged_operands, kf_of_gamma, boost_with, optical_depth_staged,
 // the Newton reciprocal / reciprocal root, the azimuth selects, hydro_coords, the table look-up) -- each case calls the function the loop
 // calls, never a copy of its body -- for tests/test_gpu_loop_arithmetic.py, which compares them with extended precision.
+// Two more of physics.hpp's functions on arrays live here, used by the engine itself: exp(x) K_2(x) per hydro cell (k2e_kernel) and the cell
+// look-up of given coordinates (lookup_kernel; mcrat_hip_lookup_cell).
 #include <hip/hip_runtime.h>
 #include "../../include/mcrat_hip.h"
 #include "device_types.hpp"
@@ -22,7 +24,7 @@ __device__ __forceinline__ EventStream item_stream(uint64_t seed, uint32_t strea
 
 __device__ __forceinline__ double k2e_of(double temp)
 {
-    return temp >= 1e7 ? phys::bessel_k2_scaled((M_EL * C_LIGHT * C_LIGHT) / (K_B * temp)) : 0.0;     // k2e_kernel, kernels.hip
+    return temp >= 1e7 ? phys::bessel_k2_scaled((M_EL * C_LIGHT * C_LIGHT) / (K_B * temp)) : 0.0;     // k2e_kernel, below
 }
 
 // hydro_coords<DIMS, GEOM> for the context's switches: a run-time switch over the pairs the engine accepts (engine.hip, geometry_supported)
@@ -174,7 +176,44 @@ __global__ __launch_bounds__(64) void eval_kernel(int fn, int n, const double *_
     }
 }
 
+// ------------------------------------------------------------------ per-cell exp(x) K_2(x)
+__global__ void k2e_kernel(const double *__restrict__ temp, double *__restrict__ k2e, int M)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= M) return;
+    const double T = temp[c];
+    double v = 0.0;
+    if (T >= 1e7) v = phys::bessel_k2_scaled((M_EL * C_LIGHT * C_LIGHT) / (K_B * T));
+    k2e[c] = v;
+}
+
+// ------------------------------------------------------------------ cell lookup (A/B of findContainingBlock)
+template <int DIMS>
+__global__ void lookup_kernel(HydroDev hy, int n, const double *a0, const double *a1, const double *a2, int *out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = phys::find_containing_block<DIMS>(hy, a0[i], a1[i], (DIMS == DIM_THREE) ? a2[i] : 0.0);
+}
+
 }  // namespace
+
+hipError_t launch_k2e(const double *temp, double *k2e, int M, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k2e_kernel, dim3((M + 255) / 256), dim3(256), 0, stream, temp, k2e, M);
+    return hipGetLastError();
+}
+
+hipError_t launch_lookup(const KernelConfig &kc, const HydroDev &hy, int n, const double *a0, const double *a1,
+                         const double *a2, int *out, hipStream_t stream)
+{
+    const int blocks = (n + 255) / 256;
+    if (kc.dimensions == DIM_THREE)
+        hipLaunchKernelGGL((lookup_kernel<DIM_THREE>), dim3(blocks), dim3(256), 0, stream, hy, n, a0, a1, a2, out);
+    else
+        hipLaunchKernelGGL((lookup_kernel<DIM_TWO>), dim3(blocks), dim3(256), 0, stream, hy, n, a0, a1, a2, out);
+    return hipGetLastError();
+}
 
 hipError_t launch_eval_function(const KernelConfig &kc, const HydroDev &hy, int fn, int n, const double *in, double *out, uint64_t seed, uint32_t stream_id,
                                 hipStream_t stream)

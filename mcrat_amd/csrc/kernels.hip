@@ -12,16 +12,12 @@
 //   event_kernel   one workgroup: sorts the iteration's shortlist of early candidates, walks it as
 //                  photonEvent does (mclib.c:1107-1356), scatters at most one photon and does the time
 //                  bookkeeping of mcrat.c:777-846.
-//   flush_kernel   applies the advance still pending when a run stops.
+// (flush_kernel, which applies the advance still pending when a run stops, and the reductions do not depend on the unit: staging.hip.)
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
 #include <stdio.h>
-#include <stdlib.h>
-#include <algorithm>
-#include <mutex>
 #include <type_traits>
-#include <vector>
 #include "device_types.hpp"
 #include "launch.hpp"
 #include "sc_exchange.hpp"
@@ -1203,7 +1199,7 @@ struct TapeLds {
 // 40 KB per list.  1000 lists of 1000 photons are then resident all at once.
 // The workgroup size is a template parameter: 256 threads per list when there are few lists (each list then gets the CU
 // it sits on) or the frame is optically thin (its cost is slow-path throughput per list), 128 otherwise; engine.hip picks.
-constexpr int rank_lds_bytes_per_slot(int block) { return block == 256 ? 7 * (int)sizeof(double) + (int)sizeof(int) + 1 : 4 * (int)sizeof(double); }
+// (what a resident slot costs in LDS: rank_lds_bytes_per_slot, rank_form_plan.hpp)
 #ifndef RANK_WAVES_PER_SIMD
 #define RANK_WAVES_PER_SIMD 2
 #endif
@@ -2410,140 +2406,7 @@ __global__ __launch_bounds__(EVENT_BLOCK) void sc_resolve_kernel(PhotonDev ph, H
     }
 }
 
-// ------------------------------------------------------------------ flush
-__global__ __launch_bounds__(STEP_BLOCK) void flush_kernel(PhotonDev ph, const LoopState *__restrict__ st)
-{
-    const int nseg = st->nseg;
-    if (nseg <= 0) return;
-    const int skip = st->skip_idx;
-    for (int i = blockIdx.x * STEP_BLOCK + threadIdx.x; i < ph.n; i += gridDim.x * STEP_BLOCK) {
-        if ((ph.flags[i] & FLAG_MOVES) && i != skip) {
-            const double u0 = ph.u0[i], u1 = ph.u1[i], u2 = ph.u2[i];
-            double r0 = ph.r0[i], r1 = ph.r1[i], r2 = ph.r2[i];
-            for (int s = 0; s < nseg; ++s) {
-                const double t = st->seg[s];
-                r0 += u0 * t;
-                r1 += u1 * t;
-                r2 += u2 * t;
-            }
-            ph.r0[i] = r0; ph.r1[i] = r1; ph.r2[i] = r2;
-        }
-    }
-}
-
-__global__ void clear_pending_kernel(LoopState *st)
-{
-    st->nseg = 0;
-    st->skip_idx = -1;
-}
-
-// ------------------------------------------------------------------ per-cell exp(x) K_2(x)
-__global__ void k2e_kernel(const double *__restrict__ temp, double *__restrict__ k2e, int M)
-{
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= M) return;
-    const double T = temp[c];
-    double v = 0.0;
-    if (T >= 1e7) v = phys::bessel_k2_scaled((M_EL * C_LIGHT * C_LIGHT) / (K_B * T));
-    k2e[c] = v;
-}
-
-// ------------------------------------------------------------------ per-frame reductions (phMinMax, phScattStats, averagePhotonEnergy)
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_min(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, 64));
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
-__global__ __launch_bounds__(256) void reduce_kernel(PhotonDev ph, ReducePartial *__restrict__ out)
-{
-    __shared__ double s[4][10];
-    __shared__ long long s_cnt[4];
-    double r_min = 1.7976931348623157e308, r_max = 0, th_min = 1.7976931348623157e308, th_max = 0;
-    double sum_scatt = 0, sum_r = 0, e_sum = 0, w_sum = 0, max_s = 0, min_s = 2147483647.0;
-    long long count = 0;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < ph.n; i += gridDim.x * 256) {
-        if (!(ph.flags[i] & FLAG_VALID)) continue;                      // a rank pool's unused slots belong to no list
-        const double x = ph.r0[i], y = ph.r1[i], z = ph.r2[i], w = ph.weight[i];
-        const double r = sqrt(x * x + y * y + z * z);
-        if (w != 0) {                                                   // mclib.c:1479
-            const double th = acos(z / r);
-            r_max = fmax(r_max, r); r_min = fmin(r_min, r);
-            th_max = fmax(th_max, th); th_min = fmin(th_min, th);
-        }
-        const double ns = ph.num_scatt[i];                              // mclib.c:1405-1421 (CYCLOSYNCHROTRON off: no filter)
-        sum_scatt += ns; sum_r += r;
-        max_s = fmax(max_s, ns); min_s = fmin(min_s, ns);
-        e_sum += ph.p0[i] * w; w_sum += w;                              // mclib.c:1377-1378
-        count += 1;
-    }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    r_min = wave_min(r_min); r_max = wave_max(r_max); th_min = wave_min(th_min); th_max = wave_max(th_max);
-    sum_scatt = wave_sum(sum_scatt); sum_r = wave_sum(sum_r); e_sum = wave_sum(e_sum); w_sum = wave_sum(w_sum);
-    max_s = wave_max(max_s); min_s = wave_min(min_s);
-    double cd = wave_sum((double)count);
-    if (lane == 0) {
-        s[wv][0] = r_min; s[wv][1] = r_max; s[wv][2] = th_min; s[wv][3] = th_max; s[wv][4] = sum_scatt;
-        s[wv][5] = sum_r; s[wv][6] = e_sum; s[wv][7] = w_sum; s[wv][8] = max_s; s[wv][9] = min_s;
-        s_cnt[wv] = (long long)cd;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        ReducePartial p;
-        p.r_min = fmin(fmin(s[0][0], s[1][0]), fmin(s[2][0], s[3][0]));
-        p.r_max = fmax(fmax(s[0][1], s[1][1]), fmax(s[2][1], s[3][1]));
-        p.th_min = fmin(fmin(s[0][2], s[1][2]), fmin(s[2][2], s[3][2]));
-        p.th_max = fmax(fmax(s[0][3], s[1][3]), fmax(s[2][3], s[3][3]));
-        p.sum_scatt = (s[0][4] + s[1][4]) + (s[2][4] + s[3][4]);
-        p.sum_r = (s[0][5] + s[1][5]) + (s[2][5] + s[3][5]);
-        p.e_sum = (s[0][6] + s[1][6]) + (s[2][6] + s[3][6]);
-        p.w_sum = (s[0][7] + s[1][7]) + (s[2][7] + s[3][7]);
-        p.max_scatt = fmax(fmax(s[0][8], s[1][8]), fmax(s[2][8], s[3][8]));
-        p.min_scatt = fmin(fmin(s[0][9], s[1][9]), fmin(s[2][9], s[3][9]));
-        p.count = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-        out[blockIdx.x] = p;
-    }
-}
-
-// ------------------------------------------------------------------ cell lookup (A/B of findContainingBlock)
-template <int DIMS>
-__global__ void lookup_kernel(HydroDev hy, int n, const double *a0, const double *a1, const double *a2, int *out)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    out[i] = phys::find_containing_block<DIMS>(hy, a0[i], a1[i], (DIMS == DIM_THREE) ? a2[i] : 0.0);
-}
-
 // ------------------------------------------------------------------ launchers
-int step_grid_blocks(int n_pad)
-{
-    const int pairs = n_pad / 2;
-    int blocks = (pairs + STEP_BLOCK - 1) / STEP_BLOCK;
-    // all workgroups resident at once: every workgroup streams its chunks back to back and pays the
-    // latency-bound slow path once.  MCRAT_HIP_STEP_BLOCKS overrides the cap (tuning).
-    int cap = 768;                        // 3 workgroups per CU, all resident at the kernel's register budget
-    if (const char *e = getenv("MCRAT_HIP_STEP_BLOCKS")) { const int v = atoi(e); if (v > 0) cap = v; }
-    if (blocks > cap) {                   // balance: every workgroup gets the same number of chunks
-        const int per_block = (blocks + cap - 1) / cap;
-        blocks = (blocks + per_block - 1) / per_block;
-    }
-    if (blocks < 1) blocks = 1;
-    return blocks;
-}
-
 // run f(integral_constant<DIMS>, integral_constant<GEOM>) for the (DIMENSIONS, GEOMETRY) pairs the reference
 // supports (mcrat.h:196-204): 2-D / 2.5-D cartesian, cylindrical, spherical; 3-D cartesian, spherical, polar
 template <int V> using ic = std::integral_constant<int, V>;
@@ -2579,7 +2442,7 @@ static hipError_t dispatch(const KernelConfig &kc, F &&f)
     return hipGetLastError();
 }
 
-hipError_t launch_step(const KernelConfig &kc, bool force_relocate, const PhotonDev &ph, const HydroDev &hy,
+static hipError_t launch_step(const KernelConfig &kc, bool force_relocate, const PhotonDev &ph, const HydroDev &hy,
                        LoopState *st, RngKey key, Cand *block_min, int blocks, Shortlist *sl, hipStream_t stream)
 {
     return dispatch(kc, [&](auto D, auto G) {
@@ -2591,7 +2454,7 @@ hipError_t launch_step(const KernelConfig &kc, bool force_relocate, const Photon
     });
 }
 
-hipError_t launch_event(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, RngKey key,
+static hipError_t launch_event(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, RngKey key,
                         const Cand *block_min, int n_blocks, Shortlist *sl, hipStream_t stream)
 {
     return dispatch(kc, [&](auto D, auto G) {
@@ -2604,7 +2467,7 @@ hipError_t launch_event(const KernelConfig &kc, const PhotonDev &ph, const Hydro
 }
 
 // the second half of a pass with the caller's tape: the free-path draws in slot order, then the event reading on from where they stopped
-hipError_t launch_tape_pass(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, RngKey key, const TapeDev &tape,
+static hipError_t launch_tape_pass(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, RngKey key, const TapeDev &tape,
                             Cand *block_min, int n_blocks, Shortlist *sl, hipStream_t stream)
 {
     tape_draw_kernel<<<dim3(1), dim3(TAPE_BLOCK), 0, stream>>>(ph, st, tape, block_min, n_blocks, sl);
@@ -2619,74 +2482,8 @@ hipError_t launch_tape_pass(const KernelConfig &kc, const PhotonDev &ph, const H
     });
 }
 
-#ifndef RANK_SMALL
-#define RANK_SMALL 128                 // threads of the small workgroup (block == 128 below); -DRANK_SMALL=64 for the A/B of one-wave lists
-#endif
-// What the runtime has been asked about a kernel of this translation unit on a device.  The dynamic-LDS limit is the kernel's, not a context's: every
-// context of the process launches the same kernel, so the note is the process's (a context's own note would go stale when another context set a smaller
-// size).  The limit is only ever raised -- a launch may use less than the limit -- and the occupancy is kept for the LDS size it was asked for last.
-struct KernelNote { const void *kernel; int device, max_dyn, occ_dyn, per_cu; };
-static std::mutex g_kernel_notes_lock;
-static std::vector<KernelNote> g_kernel_notes;
-static KernelNote &kernel_note(const void *kernel, int device)      // (with the lock held)
-{
-    for (KernelNote &k : g_kernel_notes)
-        if (k.kernel == kernel && k.device == device) return k;
-    g_kernel_notes.push_back(KernelNote{kernel, device, -1, -1, 0});
-    return g_kernel_notes.back();
-}
-static int launch_device(const RankDeviceInfo *dev)
-{
-    int d = 0;
-    if (dev) return dev->device;
-    if (hipGetDevice(&d) != hipSuccess) { (void)hipGetLastError(); d = 0; }
-    return d;
-}
-// hipFuncSetAttribute(.., hipFuncAttributeMaxDynamicSharedMemorySize, dyn), unless the kernel's limit on this device is known to be at least dyn
-static hipError_t allow_dynamic_lds(const void *kernel, int device, int dyn)
-{
-    std::lock_guard<std::mutex> hold(g_kernel_notes_lock);
-    KernelNote &k = kernel_note(kernel, device);
-    if (k.max_dyn >= dyn) return hipSuccess;
-    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, dyn);
-    if (e == hipSuccess) k.max_dyn = dyn;
-    return e;
-}
-// workgroups of `threads` threads and `dyn` bytes of dynamic LDS that one CU holds (0: the runtime would not say)
-static int resident_per_cu(const void *kernel, int device, int threads, size_t dyn)
-{
-    std::lock_guard<std::mutex> hold(g_kernel_notes_lock);
-    KernelNote &k = kernel_note(kernel, device);
-    if (k.occ_dyn == (int)dyn) return k.per_cu;
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, dyn) != hipSuccess || per_cu <= 0) { (void)hipGetLastError(); return 0; }
-    k.occ_dyn = (int)dyn; k.per_cu = per_cu;
-    return per_cu;
-}
-
-// Which builds of rank_loop_kernel exist -- per (DIMS, GEOM, STOKES) of this translation unit -- and why not the others (about 420 instantiations,
-// 53 MB of device code, minutes per translation unit; every form costs 36 of them):
-//   tape     256 threads, columns in HBM/L2, no fused pass, no hook, no queue: a validation mode, one launch form for every list length.
-//   hook     (CSH, the cyclo-synchrotron hook inside the loop) 64, RANK_SMALL or 256 threads; lists that change length: columns in HBM/L2, no fused
-//            pass, no queue (such lists go to the host between passes: one frame per launch).  64 threads -- one wavefront per list, eight lists per
-//            CU: every resident wave is always at work (no barrier waits) -- exist with the hook only.
-//   fused    where engine.hip's choose_rank_block can ask for it: DIRECT optical depths, not in spherical geometry (there it measured slower), 256 or
-//            512 threads (128: it measured no gain on thin frames, round 2).  Everything else has the queue form of a pass only.
-//   queue    256-thread lists with their columns in LDS, with or without the fused pass: carrying the queue's paths costs a build registers (see
-//            rank_loop_kernel); every other launch form runs a plan frame by frame (engine.hip, mcrat_hip_pool_run_frames).
-//   the rest RANK_SMALL, 256 or 512 threads, columns in LDS or in HBM/L2.
-template <int GEOM>
-constexpr bool rank_build_exists(bool resident, int threads, bool fuse, bool hook, bool queue, bool tape)
-{
-    if (tape) return threads == 256 && !resident && !fuse && !hook && !queue;
-    if (hook) return (threads == 64 || threads == RANK_SMALL || threads == 256) && !resident && !fuse && !queue;
-    if (fuse && (TABLE_MODE || GEOM == GEOM_SPHERICAL || (threads != 256 && threads != 512))) return false;
-    if (queue) return threads == 256 && resident;
-    return threads == RANK_SMALL || threads == 256 || threads == 512;
-}
-// A launch's form: the template arguments of rank_loop_kernel that are chosen at run time.
-struct RankForm { bool stokes, resident; int threads; bool fuse, hook, queue; };
-// f(kernel) with the build of this form; false, and no call, if there is none.  This is the one place that names a keyed build of the kernel.
+// f(kernel) with the build of this form (rank_form_plan.hpp); false, and no call, if there is none.  This is the one place that names a keyed build
+// of the kernel.
 template <int DIMS, int GEOM, class F>
 static bool with_rank_kernel(const RankForm &w, F &&f)
 {
@@ -2699,7 +2496,7 @@ static bool with_rank_kernel(const RankForm &w, F &&f)
     as_bool(w.fuse, [&](auto FU) { as_bool(w.hook, [&](auto H) { as_bool(w.queue, [&](auto Q) {
         constexpr bool SV = decltype(S)::value, RV = decltype(R)::value, FV = decltype(FU)::value, HV = decltype(H)::value, QV = decltype(Q)::value;
         constexpr int TV = decltype(T)::value;
-        if constexpr (rank_build_exists<GEOM>(RV, TV, FV, HV, QV, false)) {
+        if constexpr (rank_build_exists(GEOM, TABLE_MODE, RV, TV, FV, HV, QV, false)) {
             f(rank_loop_kernel<DIMS, GEOM, SV, RV, TV, FV, HV, QV>);
             found = true;
         }
@@ -2707,59 +2504,30 @@ static bool with_rank_kernel(const RankForm &w, F &&f)
     return found;
 }
 
-hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, const RankLaunch &rl,
-                            hipStream_t stream)
+static hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, const RankLaunch &rl,
+                                   hipStream_t stream)
 {
     RankLayout lay = {rl.n_ranks, rl.rank_stride, ph.n, rl.desc, rl.cs, rl.hook, FrameQueueDev{}};
-    const bool queued = rl.fq && rl.fq->n_frames > 0;
+    const bool queued = rank_launch_queued(rl);
     if (queued) {
         if (rl.cs || rl.n_open <= 0) return hipErrorInvalidValue;   // (cyclo-synchrotron lists go to the host between passes: one frame per launch)
         lay.fq = *rl.fq;
     }
-    RankForm form{kc.stokes != 0, false, 256, false, rl.cs && rl.hook && rl.desc, queued};
-    // threads per list: an unknown count runs 256 (64 is known with the hook only, 512 without it only)
-    const int block = (rl.threads == 128 || (rl.threads == 64 && form.hook) || (rl.threads == 512 && !form.hook)) ? rl.threads : 256;
-    form.threads = block == 128 ? RANK_SMALL : block;
-    int lds_slots = 0;
-    if (!form.hook) {
-        // per-pass columns in LDS (32 B per slot with 128 threads, 61 B with 256: rank_loop_kernel) for lists of up to 1024 photons
-        // (two 256-thread lists per CU: 13 KB of static LDS and 61 B per slot each within 160 KB -> 1088 slots; four 128-thread ones at 32 B: 1024)
-        // (512 threads -- lists of thousands of photons, one list per CU: 27 KB of static LDS and 32 B per slot within 160 KB -> 4096 slots)
-        const int lds_limit = (block == 128) ? 1024 : (block == 512 ? 4096 : 1088);
-        if (!getenv("MCRAT_HIP_NO_LDS_LISTS") && rl.longest_list <= lds_limit) lds_slots = (rl.longest_list + 15) & ~15;
-        form.resident = lds_slots > 0;
-    }
-    const size_t dyn = (size_t)lds_slots * rank_lds_bytes_per_slot(block);
+    const RankFormPlan plan = rank_form_resolve(rank_form_request(kc, rl, queued));
     bool launched = false;
     const hipError_t e = dispatch(kc, [&](auto D, auto G) {
         constexpr int DV = decltype(D)::value, GV = decltype(G)::value;
-        // a fused request where no fused build exists runs unfused
-        form.fuse = rl.fuse && rank_build_exists<GV>(form.resident, form.threads, true, form.hook, form.queue, false);
-        const int device = form.resident ? launch_device(rl.dev) : 0;
-        // static + dynamic LDS may exceed the 64 KiB default: the kernel must be told
         bool lds_refused = false;
-        launched = with_rank_kernel<DV, GV>(form, [&](auto kernel) {
-            int grid = rl.n_ranks;
-            if (form.resident && allow_dynamic_lds(reinterpret_cast<const void *>(kernel), device, (int)dyn) != hipSuccess) {
-                (void)hipGetLastError();
-                lds_refused = true;
-                return;
-            }
-            if (queued) {
-                // persistent workgroups: as many as the device holds at once (they are dealt to the XCDs round-robin, an eighth each); more would only
-                // start, find their queue empty and leave
-                int cus = rl.dev ? rl.dev->cus : 0;
-                const int per_cu = resident_per_cu(reinterpret_cast<const void *>(kernel), device, form.threads, dyn);
-                if (cus <= 0 && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) { (void)hipGetLastError(); cus = 0; }
-                grid = (per_cu > 0 && cus > 0) ? std::min(rl.n_open, per_cu * cus) : rl.n_open;
-            }
-            kernel<<<dim3(grid), dim3(form.threads), dyn, stream>>>(ph, hy, states, key, lay, rl.max_passes, lds_slots);
+        launched = with_rank_kernel<DV, GV>(plan.form, [&](auto kernel) {
+            const int grid = rank_launch_grid(reinterpret_cast<const void *>(kernel), rl, plan);
+            if (grid < 0) { lds_refused = true; return; }
+            kernel<<<dim3(grid), dim3(plan.form.threads), plan.dyn_bytes, stream>>>(ph, hy, states, key, lay, rl.max_passes, plan.lds_slots);
         });
         if (lds_refused) {             // the runtime refuses the LDS: the lists simply stay in global memory (a queue launch has no such build)
-            RankForm global = form;
+            RankForm global = plan.form;
             global.resident = false;
             launched = with_rank_kernel<DV, GV>(global, [&](auto kernel) {
-                kernel<<<dim3(rl.n_ranks), dim3(form.threads), 0, stream>>>(ph, hy, states, key, lay, rl.max_passes, 0);
+                kernel<<<dim3(rl.n_ranks), dim3(global.threads), 0, stream>>>(ph, hy, states, key, lay, rl.max_passes, 0);
             });
         }
     });
@@ -2768,7 +2536,7 @@ hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const H
 }
 
 // the tape build: one launch form for every list length (256 threads, columns in HBM/L2, no fused pass)
-hipError_t launch_rank_loop_tape(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, int n_ranks, int rank_stride,
+static hipError_t launch_rank_loop_tape(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, int n_ranks, int rank_stride,
                                  const RankDesc *desc, const double *u, TapeList *tapes, long long max_passes, hipStream_t stream)
 {
     if (!desc || !u || !tapes) return hipErrorInvalidValue;
@@ -2778,13 +2546,13 @@ hipError_t launch_rank_loop_tape(const KernelConfig &kc, const PhotonDev &ph, co
     lay.tapes = tapes;
     return dispatch(kc, [&](auto D, auto G) {
         constexpr int DV = decltype(D)::value, GV = decltype(G)::value;
-        static_assert(rank_build_exists<GV>(false, 256, false, false, false, true), "the tape build");
+        static_assert(rank_build_exists(GV, TABLE_MODE, false, 256, false, false, false, true), "the tape build");
         if (kc.stokes) rank_loop_kernel<DV, GV, true, false, 256, false, false, false, true><<<dim3(n_ranks), dim3(256), 0, stream>>>(ph, hy, states, key, lay, max_passes, 0);
         else rank_loop_kernel<DV, GV, false, false, 256, false, false, false, true><<<dim3(n_ranks), dim3(256), 0, stream>>>(ph, hy, states, key, lay, max_passes, 0);
     });
 }
 
-hipError_t launch_fast_frame(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, RngKey key, double remaining_time, int windows,
+static hipError_t launch_fast_frame(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, RngKey key, double remaining_time, int windows,
                              int max_passes, FastCounts *counts, const FastLists &lists, hipStream_t stream)
 {
     if (lists.desc && (lists.stride <= 0 || lists.stride % (2 * FAST_BLOCK) != 0)) return hipErrorInvalidValue;
@@ -2796,7 +2564,7 @@ hipError_t launch_fast_frame(const KernelConfig &kc, const PhotonDev &ph, const 
     });
 }
 
-hipError_t launch_sc_propose(const KernelConfig &kc, bool force_relocate, const PhotonDev &ph, const HydroDev &hy, LoopState *st,
+static hipError_t launch_sc_propose(const KernelConfig &kc, bool force_relocate, const PhotonDev &ph, const HydroDev &hy, LoopState *st,
                              ScState *sc, RngKey key, Cand *block_min, int blocks, Shortlist *sl, ScProposal *out, const ScFold &fold, hipStream_t stream)
 {
     hipError_t e = MCRAT_TU_NS::launch_step(kc, force_relocate, ph, hy, st, key, block_min, blocks, sl, stream);
@@ -2807,7 +2575,7 @@ hipError_t launch_sc_propose(const KernelConfig &kc, bool force_relocate, const 
     return hipGetLastError();
 }
 
-hipError_t launch_sc_resolve(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, ScState *sc, RngKey key,
+static hipError_t launch_sc_resolve(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *st, ScState *sc, RngKey key,
                              const ScProposal *all, int world, const ScFold &fold, hipStream_t stream)
 {
     return dispatch(kc, [&](auto D, auto G) {
@@ -2824,34 +2592,12 @@ extern "C" __attribute__((visibility("default"))) int mcrat_hip_diag_set(int bit
 }
 #endif
 
-hipError_t launch_flush(const PhotonDev &ph, LoopState *st, int blocks, hipStream_t stream)
+// this translation unit's launchers, as launchers.hip finds them (launch.hpp, TuLaunchers)
+const TuLaunchers &launchers()
 {
-    hipLaunchKernelGGL(flush_kernel, dim3(blocks), dim3(STEP_BLOCK), 0, stream, ph, st);
-    hipLaunchKernelGGL(clear_pending_kernel, dim3(1), dim3(1), 0, stream, st);
-    return hipGetLastError();
-}
-
-hipError_t launch_k2e(const double *temp, double *k2e, int M, hipStream_t stream)
-{
-    hipLaunchKernelGGL(k2e_kernel, dim3((M + 255) / 256), dim3(256), 0, stream, temp, k2e, M);
-    return hipGetLastError();
-}
-
-hipError_t launch_reduce(const PhotonDev &ph, ReducePartial *out, int blocks, hipStream_t stream)
-{
-    hipLaunchKernelGGL(reduce_kernel, dim3(blocks), dim3(256), 0, stream, ph, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_lookup(const KernelConfig &kc, const HydroDev &hy, int n, const double *a0, const double *a1,
-                         const double *a2, int *out, hipStream_t stream)
-{
-    const int blocks = (n + 255) / 256;
-    if (kc.dimensions == DIM_THREE)
-        hipLaunchKernelGGL((lookup_kernel<DIM_THREE>), dim3(blocks), dim3(256), 0, stream, hy, n, a0, a1, a2, out);
-    else
-        hipLaunchKernelGGL((lookup_kernel<DIM_TWO>), dim3(blocks), dim3(256), 0, stream, hy, n, a0, a1, a2, out);
-    return hipGetLastError();
+    static const TuLaunchers table = {launch_step, launch_event, launch_tape_pass, launch_rank_loop, launch_rank_loop_tape, launch_sc_propose,
+                                      launch_sc_resolve, launch_fast_frame};
+    return table;
 }
 
 }  // namespace MCRAT_TU_NS

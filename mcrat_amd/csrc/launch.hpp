@@ -5,6 +5,7 @@
 #include "frame_queue.hpp"
 #include "list_plan.hpp"
 #include "hydro_plan.hpp"
+#include "rank_form_plan.hpp"
 
 namespace mcrat {
 
@@ -48,7 +49,8 @@ struct RankLaunch {
     int longest_list = 0;                // sizes the LDS copy of the per-pass columns; RANK_COLUMNS_GLOBAL: the columns stay in HBM/L2
     const RankDesc *desc = nullptr;
     int threads = 256;                   // per list: 64 (with the hook only), 128, 256 or 512; anything else runs 256
-    bool fuse = false;                   // the build with the fused pass, where one exists (kernels.hip, rank_build_exists); unfused where not
+    bool fuse = false;                   // the build with the fused pass, where one exists (rank_form_plan.hpp, rank_build_exists); unfused where not
+    bool no_lds_lists = false;           // MCRAT_HIP_NO_LDS_LISTS is set: the columns stay in HBM/L2 whatever longest_list says
     long long max_passes = 0;            // per list and launch
     struct CsFrame *cs = nullptr;        // cyclo-synchrotron lists ...
     const struct CsHookArgs *hook = nullptr;   // ... and the hook inside the loop (above)
@@ -56,9 +58,18 @@ struct RankLaunch {
     int n_open = 0;                      //   the items in fq->order.  A form without a queue build: hipErrorNotSupported, and nothing is launched
     const RankDeviceInfo *dev = nullptr;
 };
-constexpr int RANK_COLUMNS_GLOBAL = 1 << 30;      // RankLaunch::longest_list of lists that change length: no list is short enough for LDS
+// The launch as rank_form_plan.hpp's rule sees it: the engine asks rank_form_resolve whether a queued launch has a build before it plans one, the
+// launcher asks it for the form it launches.
+inline bool rank_launch_queued(const RankLaunch &rl) { return rl.fq && rl.fq->n_frames > 0; }
+inline RankFormRequest rank_form_request(const KernelConfig &kc, const RankLaunch &rl, bool queued)
+{
+    return RankFormRequest{rl.threads, rl.fuse, rl.cs && rl.hook && rl.desc, queued, rl.longest_list, kc.stokes != 0, kc.geometry, kc.table != 0, rl.no_lds_lists};
+}
 // The launcher asks the runtime once per kernel: the dynamic-LDS limit it has set for a kernel and the occupancy it was told for a (kernel, LDS size)
-// are remembered (kernels.hip, KernelNote), so a second launch of the same form makes no hipFuncSetAttribute and no occupancy query.
+// are remembered (rank_launch.hip, KernelNote), so a second launch of the same form makes no hipFuncSetAttribute and no occupancy query.
+// rank_launch_grid: the workgroups of the launch of `kernel`, the plan's build, after the kernel has been allowed the plan's dynamic LDS; -1: the runtime
+// refuses the LDS.
+int rank_launch_grid(const void *kernel, const RankLaunch &rl, const RankFormPlan &plan);
 hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, const RankLaunch &rl,
                             hipStream_t stream);
 // The tape build of the rank pool (mcrat_hip_pool_set_rng_tapes): every list of a pool that holds tapes goes through it, whatever choose_rank_block
@@ -346,6 +357,18 @@ hipError_t grid_build(const GridPlan &p, const CellGeom *geom, const CellGeom2 *
                       long long total, hipStream_t stream);
 hipError_t launch_lookup(const KernelConfig &kc, const HydroDev &hy, int n, const double *a0, const double *a1,
                          const double *a2, int *out, hipStream_t stream);
+// The launchers that every kernels translation unit (kernels.hip: one per TAU_CALCULATION and DIMENSIONS) defines for itself; launchers.hip picks the
+// unit's table and calls through it.
+struct TuLaunchers {
+    decltype(&launch_step) step;
+    decltype(&launch_event) event;
+    decltype(&launch_tape_pass) tape_pass;
+    decltype(&launch_rank_loop) rank_loop;
+    decltype(&launch_rank_loop_tape) rank_loop_tape;
+    decltype(&launch_sc_propose) sc_propose;
+    decltype(&launch_sc_resolve) sc_resolve;
+    decltype(&launch_fast_frame) fast_frame;
+};
 // physics.hpp's functions on arrays (functions.hip; mcrat_hip_eval_function)
 // (hy: the context's cross-section table for THERMAL_CROSS_SECTION; kc: STOKES, and DIMENSIONS / geometry for HYDRO_COORDS)
 hipError_t launch_eval_function(const KernelConfig &kc, const HydroDev &hy, int fn, int n, const double *in, double *out, uint64_t seed, uint32_t stream_id,

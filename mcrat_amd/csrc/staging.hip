@@ -2,6 +2,8 @@
 // The caller's photon list crosses PCIe once as it lies in memory; the transposition, the derived columns
 // (device_types.hpp: u = (p_k (1/p0)) c as mclib.c:1074-1080 forms it, -1/tau as mclib.c:680) and the flag byte are
 // produced here instead of in a host loop over 10^6 - 10^8 records.
+// Also the small kernels on the columns that no TAU_CALCULATION or DIMENSIONS changes: the pending advance applied when a run stops (flush_kernel), the
+// per-frame reductions, clearing slots.
 #include <hip/hip_runtime.h>
 #include "../../include/mcrat_hip.h"
 #include "device_types.hpp"
@@ -352,6 +354,103 @@ __global__ __launch_bounds__(256) void rank_reduce_kernel(PhotonDev ph, int stri
     }
 }
 
+// ------------------------------------------------------------------ flush
+__global__ __launch_bounds__(STEP_BLOCK) void flush_kernel(PhotonDev ph, const LoopState *__restrict__ st)
+{
+    const int nseg = st->nseg;
+    if (nseg <= 0) return;
+    const int skip = st->skip_idx;
+    for (int i = blockIdx.x * STEP_BLOCK + threadIdx.x; i < ph.n; i += gridDim.x * STEP_BLOCK) {
+        if ((ph.flags[i] & FLAG_MOVES) && i != skip) {
+            const double u0 = ph.u0[i], u1 = ph.u1[i], u2 = ph.u2[i];
+            double r0 = ph.r0[i], r1 = ph.r1[i], r2 = ph.r2[i];
+            for (int s = 0; s < nseg; ++s) {
+                const double t = st->seg[s];
+                r0 += u0 * t;
+                r1 += u1 * t;
+                r2 += u2 * t;
+            }
+            ph.r0[i] = r0; ph.r1[i] = r1; ph.r2[i] = r2;
+        }
+    }
+}
+
+__global__ void clear_pending_kernel(LoopState *st)
+{
+    st->nseg = 0;
+    st->skip_idx = -1;
+}
+
+// ------------------------------------------------------------------ per-frame reductions (phMinMax, phScattStats, averagePhotonEnergy)
+__device__ __forceinline__ double wave_sum(double v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+__device__ __forceinline__ double wave_min(double v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, 64));
+    return v;
+}
+__device__ __forceinline__ double wave_max(double v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
+    return v;
+}
+
+__global__ __launch_bounds__(256) void reduce_kernel(PhotonDev ph, ReducePartial *__restrict__ out)
+{
+    __shared__ double s[4][10];
+    __shared__ long long s_cnt[4];
+    double r_min = 1.7976931348623157e308, r_max = 0, th_min = 1.7976931348623157e308, th_max = 0;
+    double sum_scatt = 0, sum_r = 0, e_sum = 0, w_sum = 0, max_s = 0, min_s = 2147483647.0;
+    long long count = 0;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < ph.n; i += gridDim.x * 256) {
+        if (!(ph.flags[i] & FLAG_VALID)) continue;                      // a rank pool's unused slots belong to no list
+        const double x = ph.r0[i], y = ph.r1[i], z = ph.r2[i], w = ph.weight[i];
+        const double r = sqrt(x * x + y * y + z * z);
+        if (w != 0) {                                                   // mclib.c:1479
+            const double th = acos(z / r);
+            r_max = fmax(r_max, r); r_min = fmin(r_min, r);
+            th_max = fmax(th_max, th); th_min = fmin(th_min, th);
+        }
+        const double ns = ph.num_scatt[i];                              // mclib.c:1405-1421 (CYCLOSYNCHROTRON off: no filter)
+        sum_scatt += ns; sum_r += r;
+        max_s = fmax(max_s, ns); min_s = fmin(min_s, ns);
+        e_sum += ph.p0[i] * w; w_sum += w;                              // mclib.c:1377-1378
+        count += 1;
+    }
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    r_min = wave_min(r_min); r_max = wave_max(r_max); th_min = wave_min(th_min); th_max = wave_max(th_max);
+    sum_scatt = wave_sum(sum_scatt); sum_r = wave_sum(sum_r); e_sum = wave_sum(e_sum); w_sum = wave_sum(w_sum);
+    max_s = wave_max(max_s); min_s = wave_min(min_s);
+    double cd = wave_sum((double)count);
+    if (lane == 0) {
+        s[wv][0] = r_min; s[wv][1] = r_max; s[wv][2] = th_min; s[wv][3] = th_max; s[wv][4] = sum_scatt;
+        s[wv][5] = sum_r; s[wv][6] = e_sum; s[wv][7] = w_sum; s[wv][8] = max_s; s[wv][9] = min_s;
+        s_cnt[wv] = (long long)cd;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        ReducePartial p;
+        p.r_min = fmin(fmin(s[0][0], s[1][0]), fmin(s[2][0], s[3][0]));
+        p.r_max = fmax(fmax(s[0][1], s[1][1]), fmax(s[2][1], s[3][1]));
+        p.th_min = fmin(fmin(s[0][2], s[1][2]), fmin(s[2][2], s[3][2]));
+        p.th_max = fmax(fmax(s[0][3], s[1][3]), fmax(s[2][3], s[3][3]));
+        p.sum_scatt = (s[0][4] + s[1][4]) + (s[2][4] + s[3][4]);
+        p.sum_r = (s[0][5] + s[1][5]) + (s[2][5] + s[3][5]);
+        p.e_sum = (s[0][6] + s[1][6]) + (s[2][6] + s[3][6]);
+        p.w_sum = (s[0][7] + s[1][7]) + (s[2][7] + s[3][7]);
+        p.max_scatt = fmax(fmax(s[0][8], s[1][8]), fmax(s[2][8], s[3][8]));
+        p.min_scatt = fmin(fmin(s[0][9], s[1][9]), fmin(s[2][9], s[3][9]));
+        p.count = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+        out[blockIdx.x] = p;
+    }
+}
+
 // rank pool: a new frame for the lists with open[r] != 0 -- their own clocks -- in one launch (cf. init_states_kernel)
 __global__ __launch_bounds__(256) void init_states_multi_kernel(LoopState *__restrict__ ranks, int n_ranks, const int *__restrict__ open,
                                                                 const double *__restrict__ time_now, const double *__restrict__ remaining)
@@ -369,6 +468,19 @@ __global__ __launch_bounds__(256) void init_states_multi_kernel(LoopState *__res
 }
 
 }  // namespace
+
+hipError_t launch_flush(const PhotonDev &ph, LoopState *st, int blocks, hipStream_t stream)
+{
+    hipLaunchKernelGGL(flush_kernel, dim3(blocks), dim3(STEP_BLOCK), 0, stream, ph, st);
+    hipLaunchKernelGGL(clear_pending_kernel, dim3(1), dim3(1), 0, stream, st);
+    return hipGetLastError();
+}
+
+hipError_t launch_reduce(const PhotonDev &ph, ReducePartial *out, int blocks, hipStream_t stream)
+{
+    hipLaunchKernelGGL(reduce_kernel, dim3(blocks), dim3(256), 0, stream, ph, out);
+    return hipGetLastError();
+}
 
 hipError_t launch_init_states_multi(LoopState *ranks, int n_ranks, const int *open, const double *time_now, const double *remaining, hipStream_t stream)
 {
