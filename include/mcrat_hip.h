@@ -522,13 +522,16 @@ int mcrat_hip_rank_stats(mcrat_hip_ctx *ctx, int rank, mcrat_hip_frame_stats *st
  *                           totals; mcrat_hip_frame_statistics(view) gives a list's own.  mcrat_hip_begin_frame(pool)
  *                           opens a frame for all lists at once with one seed and clock.
  *   mcrat_hip_pool_summaries  phMinMax, phScattStats, averagePhotonEnergy and printPhotons' photon count for every list in
- *                           one launch (lists that do not exist: list_capacity 0).
+ *                           one launch (lists that do not exist: list_capacity 0 and every other member 0).  With the pool's
+ *                           cyclosynchrotron_switch on, max_scatt, min_scatt, avg_scatt, avg_r and avg_energy are over the photons
+ *                           with weight != 0 only, as mcrat_hip_scatt_stats and mcrat_hip_avg_energy say below; min_r .. max_theta,
+ *                           num_output and list_capacity do not depend on the switch.
  * mcrat_host_run_ranks (mcrat_amd/host) is main()'s rank logic on top of this; INTEGRATION.md shows the edit. */
 typedef struct mcrat_hip_rank_summary {
     double min_r, max_r, min_theta, max_theta;   /* phMinMax, mclib.c:1465 */
-    double avg_scatt, avg_r;                     /* phScattStats, mclib.c:1385 */
-    double avg_energy;                           /* averagePhotonEnergy, mclib.c:1358 */
-    int    max_scatt, min_scatt;
+    double avg_scatt, avg_r;                     /* phScattStats, mclib.c:1385; switch on: photons with weight != 0 only (:1401) */
+    double avg_energy;                           /* averagePhotonEnergy, mclib.c:1358; switch on: the same filter (:1373) */
+    int    max_scatt, min_scatt;                 /* phScattStats; switch on and no weighted photon: 0 and INT_MAX */
     int    num_output;                           /* photons with weight != 0: what printPhotons writes (mcrat_io.c:137-181) */
     int    list_capacity;                        /* photon_list->list_capacity of this rank (0: no list) */
 } mcrat_hip_rank_summary;
@@ -783,7 +786,14 @@ int mcrat_hip_pool_rng_tape_positions(mcrat_hip_ctx *pool, long long *position /
 #define MCRAT_HIP_FN_COUNT                 20   /* one past the last code */
 int mcrat_hip_eval_function(mcrat_hip_ctx *ctx, int fn, int n, const double *in, double *out, uint64_t seed);
 
-/* per-frame reductions on the resident photons ------------------------------- */
+/* per-frame reductions on the resident photons -------------------------------
+ * They follow mcrat_hip_config.cyclosynchrotron_switch as the reference's follow CYCLOSYNCHROTRON_SWITCH (a view: its pool's switch):
+ *   mcrat_hip_ph_minmax    photons with weight != 0 only, under either setting (mclib.c:1479); none: (DBL_MAX, 0, DBL_MAX, 0)
+ *   mcrat_hip_scatt_stats  switch off: every slot of the list; on: photons with weight != 0 only (mclib.c:1401-1403), so null slots
+ *                          and absorbed photons take no part in the extremes, the sums or the count -- none left: max_scatt = 0,
+ *                          min_scatt = INT_MAX, both averages NaN (0/0), as in the reference
+ *   mcrat_hip_avg_energy   the same rule for both of its sums (mclib.c:1373-1375); none left: NaN
+ * (phScattStats' per-type "Avg r for i type ..." log line is not computed.) */
 int mcrat_hip_ph_minmax(mcrat_hip_ctx *ctx, double *min_r, double *max_r, double *min_theta, double *max_theta); /* mclib.c:1465 */
 int mcrat_hip_scatt_stats(mcrat_hip_ctx *ctx, int *max_scatt, int *min_scatt, double *avg_scatt, double *avg_r); /* mclib.c:1385 */
 int mcrat_hip_avg_energy(mcrat_hip_ctx *ctx, double *erg);                                                    /* mclib.c:1358 */

@@ -2356,7 +2356,7 @@ extern "C" int mcrat_hip_pool_summaries(mcrat_hip_ctx *c, mcrat_hip_rank_summary
     RankDesc *d_desc = reinterpret_cast<RankDesc *>(d_part + R);
     int *d_nout = reinterpret_cast<int *>(d_desc + R);
     HIPCHK(c, hipMemcpyAsync(d_desc, c->h_desc, sizeof(RankDesc) * (size_t)R, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, launch_rank_reduce(c->ph, c->rank_stride, R, d_desc, d_part, d_nout, c->stream));
+    HIPCHK(c, launch_rank_reduce(c->ph, c->rank_stride, R, d_desc, d_part, d_nout, c->cfg.cyclosynchrotron_switch, c->stream));
     std::vector<ReducePartial> part((size_t)R);
     std::vector<int> nout((size_t)R);
     HIPCHK(c, hipMemcpyAsync(part.data(), d_part, sizeof(ReducePartial) * (size_t)R, hipMemcpyDeviceToHost, c->stream));
@@ -4003,7 +4003,7 @@ static int run_reduce(mcrat_hip_ctx *c, ReducePartial &t)
     int rc = flush_pending(c);
     if (rc) return rc;
     const int blocks = std::min(mcrat_hip_ctx::RED_BLOCKS, std::max(1, (c->ph.n + 255) / 256));
-    HIPCHK(c, launch_reduce(c->ph, c->d_red, blocks, c->stream));
+    HIPCHK(c, launch_reduce(c->ph, c->d_red, blocks, c->cfg.cyclosynchrotron_switch, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->h_red, c->d_red, sizeof(ReducePartial) * blocks, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     t = c->h_red[0];

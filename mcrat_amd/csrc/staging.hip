@@ -296,9 +296,10 @@ __global__ __launch_bounds__(256) void clear_slots_kernel(PhotonDev ph, int firs
 }
 
 // rank pool: phMinMax (mclib.c:1465), phScattStats (mclib.c:1385), averagePhotonEnergy (mclib.c:1358) and printPhotons' count of
-// photons with weight != 0 (mcrat_io.c:137-181) for every list in one launch, one workgroup per list
+// photons with weight != 0 (mcrat_io.c:137-181) for every list in one launch, one workgroup per list.  cs_switch: CYCLOSYNCHROTRON_SWITCH,
+// as in reduce_kernel below
 __global__ __launch_bounds__(256) void rank_reduce_kernel(PhotonDev ph, int stride, const RankDesc *__restrict__ desc, ReducePartial *__restrict__ out,
-                                                          int *__restrict__ n_out)
+                                                          int *__restrict__ n_out, int cs_switch)
 {
     __shared__ double s[4][10];
     __shared__ long long s_cnt[4][2];
@@ -316,6 +317,7 @@ __global__ __launch_bounds__(256) void rank_reduce_kernel(PhotonDev ph, int stri
             th_max = fmax(th_max, th); th_min = fmin(th_min, th);
             kept += 1;
         }
+        if (cs_switch && !(w != 0)) continue;                           // mclib.c:1401-1403, :1373-1375
         const double ns = ph.num_scatt[i];
         sum_scatt += ns; sum_r += r;
         max_s = fmax(max_s, ns); min_s = fmin(min_s, ns);
@@ -382,6 +384,10 @@ __global__ void clear_pending_kernel(LoopState *st)
 }
 
 // ------------------------------------------------------------------ per-frame reductions (phMinMax, phScattStats, averagePhotonEnergy)
+// cs_switch is the context's CYCLOSYNCHROTRON_SWITCH.  On: phScattStats (mclib.c:1401-1403) and averagePhotonEnergy (mclib.c:1373-1375) pass
+// over every photon with weight == 0 -- null slots and absorbed photons -- so their sums, extremes and count are of the weighted photons
+// alone, and a list without any gives 0/0 and (max, min) = (0, INT_MAX) as the reference does.  Off: every slot counts.  phMinMax filters on
+// weight != 0 under either switch (mclib.c:1479).
 __device__ __forceinline__ double wave_sum(double v)
 {
 #pragma unroll
@@ -401,7 +407,7 @@ __device__ __forceinline__ double wave_max(double v)
     return v;
 }
 
-__global__ __launch_bounds__(256) void reduce_kernel(PhotonDev ph, ReducePartial *__restrict__ out)
+__global__ __launch_bounds__(256) void reduce_kernel(PhotonDev ph, ReducePartial *__restrict__ out, int cs_switch)
 {
     __shared__ double s[4][10];
     __shared__ long long s_cnt[4];
@@ -417,7 +423,8 @@ __global__ __launch_bounds__(256) void reduce_kernel(PhotonDev ph, ReducePartial
             r_max = fmax(r_max, r); r_min = fmin(r_min, r);
             th_max = fmax(th_max, th); th_min = fmin(th_min, th);
         }
-        const double ns = ph.num_scatt[i];                              // mclib.c:1405-1421 (CYCLOSYNCHROTRON off: no filter)
+        if (cs_switch && !(w != 0)) continue;                           // mclib.c:1401-1403, :1373-1375 (CYCLOSYNCHROTRON on)
+        const double ns = ph.num_scatt[i];                              // mclib.c:1405-1421
         sum_scatt += ns; sum_r += r;
         max_s = fmax(max_s, ns); min_s = fmin(min_s, ns);
         e_sum += ph.p0[i] * w; w_sum += w;                              // mclib.c:1377-1378
@@ -476,9 +483,9 @@ hipError_t launch_flush(const PhotonDev &ph, LoopState *st, int blocks, hipStrea
     return hipGetLastError();
 }
 
-hipError_t launch_reduce(const PhotonDev &ph, ReducePartial *out, int blocks, hipStream_t stream)
+hipError_t launch_reduce(const PhotonDev &ph, ReducePartial *out, int blocks, int cs_switch, hipStream_t stream)
 {
-    hipLaunchKernelGGL(reduce_kernel, dim3(blocks), dim3(256), 0, stream, ph, out);
+    hipLaunchKernelGGL(reduce_kernel, dim3(blocks), dim3(256), 0, stream, ph, out, cs_switch);
     return hipGetLastError();
 }
 
@@ -501,9 +508,10 @@ hipError_t launch_clear_slots(const PhotonDev &ph, int first, int count, hipStre
     return hipGetLastError();
 }
 
-hipError_t launch_rank_reduce(const PhotonDev &ph, int stride, int n_ranks, const RankDesc *desc, ReducePartial *out, int *n_out, hipStream_t stream)
+hipError_t launch_rank_reduce(const PhotonDev &ph, int stride, int n_ranks, const RankDesc *desc, ReducePartial *out, int *n_out, int cs_switch,
+                              hipStream_t stream)
 {
-    rank_reduce_kernel<<<dim3(n_ranks), dim3(256), 0, stream>>>(ph, stride, desc, out, n_out);
+    rank_reduce_kernel<<<dim3(n_ranks), dim3(256), 0, stream>>>(ph, stride, desc, out, n_out, cs_switch);
     return hipGetLastError();
 }
 

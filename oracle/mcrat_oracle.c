@@ -994,24 +994,31 @@ double orc_photonEvent(const orc_config *c, orc_photon_list *l, double dt_max, c
     return scatt_time;
 }
 
-/* mclib.c:1358-1383 (CYCLOSYNCHROTRON_SWITCH OFF: no weight filter) */
-double orc_averagePhotonEnergy(const orc_photon_list *l)
+/* mclib.c:1358-1383.  cs_switch is CYCLOSYNCHROTRON_SWITCH: when it is on the two sums are over the photons that carry weight only (:1373-1375),
+ * so null slots and absorbed photons stay out; when it is off every slot of the list is added, a weight of 0 included. */
+double orc_averagePhotonEnergy_cs(const orc_photon_list *l, int cs_switch)
 {
     double e_sum = 0, w_sum = 0;
     for (int i = 0; i < l->list_capacity; i++) {
-        e_sum += l->photons[i].p0 * l->photons[i].weight;
-        w_sum += l->photons[i].weight;
+        const orc_photon *ph = &l->photons[i];
+        if (cs_switch && !(ph->weight != 0)) continue;
+        e_sum += ph->p0 * ph->weight;
+        w_sum += ph->weight;
     }
     return (e_sum * ORC_C_LIGHT) / w_sum;
 }
 
-/* mclib.c:1385-1462 (CYCLOSYNCHROTRON_SWITCH OFF) */
-void orc_phScattStats(const orc_photon_list *l, int *max, int *min, double *avg, double *r_avg)
+double orc_averagePhotonEnergy(const orc_photon_list *l) { return orc_averagePhotonEnergy_cs(l, 0); }
+
+/* mclib.c:1385-1462, with the same switch (:1401-1403): on, a photon without weight takes no part in the sums, the extremes or the count, and a
+ * list with no weighted photon leaves max = 0, min = INT_MAX and both averages 0/0.  (The per-type "Avg r" line, :1423-1453, is not restated.) */
+void orc_phScattStats_cs(const orc_photon_list *l, int cs_switch, int *max, int *min, double *avg, double *r_avg)
 {
     int temp_max = 0, temp_min = INT_MAX, count = 0;
     double sum = 0, avg_r_sum = 0;
     for (int i = 0; i < l->list_capacity; i++) {
         const orc_photon *ph = &l->photons[i];
+        if (cs_switch && !(ph->weight != 0)) continue;
         sum += ph->num_scatt;
         avg_r_sum += sqrt(ph->r0 * ph->r0 + ph->r1 * ph->r1 + ph->r2 * ph->r2);
         if (ph->num_scatt > temp_max) temp_max = (int)ph->num_scatt;
@@ -1024,7 +1031,9 @@ void orc_phScattStats(const orc_photon_list *l, int *max, int *min, double *avg,
     *min = temp_min;
 }
 
-/* mclib.c:1465-1515 */
+void orc_phScattStats(const orc_photon_list *l, int *max, int *min, double *avg, double *r_avg) { orc_phScattStats_cs(l, 0, max, min, avg, r_avg); }
+
+/* mclib.c:1465-1515: weight != 0 under either setting of the switch (:1479) */
 void orc_phMinMax(const orc_photon_list *l, double *min, double *max, double *min_theta, double *max_theta)
 {
     double r_max = 0, r_min = DBL_MAX, th_max = 0, th_min = DBL_MAX;

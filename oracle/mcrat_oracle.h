@@ -199,6 +199,9 @@ double orc_photonEvent(const orc_config *c, orc_photon_list *l, double dt_max, c
                        int *scattered_ph_index, long long *frame_scatt_cnt, orc_rng *rng, orc_stats *st); /* mclib.c:1107 */
 double orc_averagePhotonEnergy(const orc_photon_list *l);                                         /* mclib.c:1358 */
 void   orc_phScattStats(const orc_photon_list *l, int *max, int *min, double *avg, double *r_avg); /* mclib.c:1385 */
+/* the same two with CYCLOSYNCHROTRON_SWITCH as an argument: on, photons with weight == 0 are passed over (mclib.c:1373-1375, :1401-1403) */
+double orc_averagePhotonEnergy_cs(const orc_photon_list *l, int cs_switch);
+void   orc_phScattStats_cs(const orc_photon_list *l, int cs_switch, int *max, int *min, double *avg, double *r_avg);
 void   orc_phMinMax(const orc_photon_list *l, double *min, double *max, double *min_theta, double *max_theta); /* mclib.c:1465 */
 
 /* while (remaining_time>0) of mcrat.c:754-851, optionally bounded by max_iterations (<=0: unbounded).

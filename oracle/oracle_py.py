@@ -237,6 +237,8 @@ def lib():
             "orc_photonEvent": (d, [cfgp, lp, d, hp, C.POINTER(i), C.POINTER(C.c_longlong), rp, sp]),
             "orc_averagePhotonEnergy": (d, [lp]),
             "orc_phScattStats": (None, [lp, C.POINTER(i), C.POINTER(i), _dp, _dp]),
+            "orc_averagePhotonEnergy_cs": (d, [lp, i]),
+            "orc_phScattStats_cs": (None, [lp, i, C.POINTER(i), C.POINTER(i), _dp, _dp]),
             "orc_phMinMax": (None, [lp, _dp, _dp, _dp, _dp]),
             "orc_photon_loop": (None, [cfgp, lp, hp, rp, _dp, _dp, C.POINTER(i), C.c_longlong, C.c_uint64, sp]),
             "orc_flash_select": (i, [cfgp, C.POINTER(FlashBlocks), C.POINTER(Slab), i, C.POINTER(Frame), C.POINTER(i)]),

@@ -6,11 +6,13 @@ conversion.  Against the oracle doing every rank's steps on its own: the ingest 
 with the counter main() carries from frame to frame, saveCheckpoint's conversion."""
 import ctypes as C
 import os
+import re
 
 import numpy as np
 import pytest
 
 from mcrat_amd import synth
+from tests import reductions_checker
 
 pytestmark = pytest.mark.gpu
 FPS, LAST = 5.0, 2
@@ -44,9 +46,14 @@ def test_chombo_3d_simulation_field_cyclosynchrotron_stokes_through_the_rank_poo
     o_jet = oracle.outflow(3, lumi=5e53, theta_j=0.3)
     R, base_seed, max_photons = 2, 4242, 1500
     ranks = (B.HostRank * R)()
+    libc = C.CDLL(None)
+    libc.fopen.restype = C.c_void_p
+    libc.fopen.argtypes = [C.c_char_p, C.c_char_p]
+    libc.fclose.argtypes = [C.c_void_p]
     for r, k in enumerate(ranks):
         d = str(tmp_path / ("rank%d" % r)) + "/"
         os.makedirs(d)
+        k.fPtr = libc.fopen((d + "mc_output_%d.log" % r).encode(), b"a")
         k.myid, k.angle_id, k.angle_procs = r, r, R
         k.mc_dir = d.encode()
         k.theta_jmin_thread, k.theta_jmax_thread, k.inj_radius, k.ph_weight_suggest = 0.0, 0.25, 1e12, 1e46
@@ -69,6 +76,8 @@ def test_chombo_3d_simulation_field_cyclosynchrotron_stokes_through_the_rank_poo
     cfg.write_checkpoints, cfg.cyclosynchrotron_switch = 1, 1
     cfg.cs = hip.Cyclosynch(2, 0.5, 0.1, 0.5, 45.0, 0, 0)                                # B_FIELD_CALC == SIMULATION
     assert host.mcrat_host_run_ranks(pool.ctx, ranks, R, C.byref(cfg)) == 0, pool.lib.mcrat_hip_last_error(pool.ctx)
+    for k in ranks:
+        libc.fclose(k.fPtr)
     assert [f for f, s in slabs if s["ph_inj_switch"] == 0] == [0, 1, 2]
 
     ocfg = oracle.make_config(synth.THREE, synth.SPHERICAL, 1)
@@ -129,6 +138,18 @@ def test_chombo_3d_simulation_field_cyclosynchrotron_stokes_through_the_rank_poo
             err = np.abs(got[f] - want[f]) / scale
             assert np.all(err <= 1e-9), (r, f, float(err.max()))
         assert k.time_now == pytest.approx(t.value, rel=1e-12) and k.scatt_cyclosynch_num_ph == carry
+        # the rank's log: phScattStats' lines of its last frame carry the reference's numbers for CYCLOSYNCHROTRON_SWITCH on -- over the photons
+        # with weight != 0 only (mclib.c:1401-1403; tests/reductions_checker.py on the list read back, which only changed types since).  They are
+        # printed with %d, %lf and %e: the integers exactly, the averages to half a unit of the last printed digit.
+        log = open(k.mc_dir.decode() + "mc_output_%d.log" % k.angle_id).read()
+        line = lambda text: re.findall(re.escape(text) + r" *(\S+)", log)[-1]
+        on, off = reductions_checker.reductions(got, 1), reductions_checker.reductions(got, 0)
+        assert on["count"] < off["count"] and on["avg_scatt"] > off["avg_scatt"] + 1e-3        # null slots are there: the switch matters
+        assert int(line("The maximum number of scatterings for a photon is:")) == on["max_scatt"]
+        assert int(line("The minimum number of scatterings for a photon is:")) == on["min_scatt"]
+        assert abs(float(line("The average number of scatterings thus far is:")) - on["avg_scatt"]) <= 0.5e-6 * (1 + 1e-6)
+        assert float(line("The average position of photons is")) == pytest.approx(on["avg_r"], rel=5e-7 * (1 + 1e-6))
+        assert abs(off["avg_r"] / on["avg_r"] - 1) > 1e-3                                      # (the unfiltered value would not pass)
         # the checkpoint the rank left for its last scatter frame ('i' layout): the list after the conversion, 'k' gone
         old = open(k.mc_dir.decode() + "mc_chkpt_%d.dat_old" % k.angle_id, "rb").read()
         rec = np.frombuffer(old[4 + 1 + 4 + 4:], dtype=hip.PHOTON_DTYPE)
