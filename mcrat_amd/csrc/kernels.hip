@@ -143,6 +143,22 @@ __device__ __forceinline__ void wave_min_pair_dpp(double &t, int &i)
     i = __builtin_amdgcn_readlane(i, 63);
 }
 
+// wave64 sum of an int on the same path: inclusive prefix sum inside each row (a lane without a DPP source adds 0), then row 0 into row 1 and
+// row 2 into row 3 (row_bcast 15, rows 1 and 3 enabled), then rows 0+1 into rows 2 and 3 (row_bcast 31).  ONLY LANE 63 ends with the wave's sum.
+template <int CTRL, int ROWS>
+__device__ __forceinline__ int dpp_add_step(int v) { return v + __builtin_amdgcn_update_dpp(0, v, CTRL, ROWS, 0xf, false); }
+
+__device__ __forceinline__ int wave_sum_lane63_dpp(int v)
+{
+    v = dpp_add_step<0x111, 0xf>(v);   // row_shr:1
+    v = dpp_add_step<0x112, 0xf>(v);   // row_shr:2
+    v = dpp_add_step<0x114, 0xf>(v);   // row_shr:4
+    v = dpp_add_step<0x118, 0xf>(v);   // row_shr:8
+    v = dpp_add_step<0x142, 0xa>(v);   // row_bcast:15
+    v = dpp_add_step<0x143, 0xc>(v);   // row_bcast:31
+    return v;
+}
+
 // the K smallest of all lanes' lists -> out[0..K) (ascending).  NW = waves in the workgroup, NW*TOPK <= 64.
 template <int NW>
 __device__ __forceinline__ void block_topk(TopK &mine, Cand (*s_w)[TOPK], Cand *out)
@@ -1348,7 +1364,8 @@ __global__ __launch_bounds__(RANK_BLOCK, RANK_WAVES_PER_SIMD) void rank_loop_ker
     };
     if (lay.cs) settle_pass_limit();
 #ifdef MCRAT_DIAG
-    long long dg[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // ticks: load, forced step, step, event, store; [5] passes
+    long long dg[16] = {};   // ticks: load, forced step, step, event, store; [5] passes; [6] phase 1, [7] the barrier behind it;
+                             // [8..13] the serial stretch of a non-forced pass: top-of-pass barrier, phase 2, wave minimum, counters, barrier, merge; [14] such passes
     long long dg_t = (long long)__builtin_amdgcn_s_memtime();
     const bool dg_clock = (g_diag & 1024) != 0;      // only the list's start and end on the 100 MHz clock (and its length in shader-clock ticks)
     const long long dg_real0 = (long long)__builtin_amdgcn_s_memrealtime(), dg_tick0 = dg_t;
@@ -1439,8 +1456,12 @@ __global__ __launch_bounds__(RANK_BLOCK, RANK_WAVES_PER_SIMD) void rank_loop_ker
         // instead of queueing them: no hand-over through LDS, and the chains of its slots overlap.  Where few do (dense frames), the
         // queue keeps the lanes of the slow path dense.  Same arithmetic either way.
         const bool fused = FUSE && !TABLE_MODE && (force || RANK_FUSE_DEN * prev_rel > n_pass);
+        // (clearing them in thread 0's bookkeeping at the end of the pass instead, which makes this barrier unnecessary, was measured: the stamp
+        // below did not shrink and the headline queue build went from 80 to 96 B of scratch; so was one barrier for phase 1 and the minima when
+        // the queue is empty -- DESIGN_NOTEBOOK.md)
         if (tid == 0) { s_qn = 0; s_sln = 0; s_nrel = 0; s_ndefer = 0; }
         __syncthreads();
+        if (!force) RANK_TICK(8);
         int n_rel = 0;
 
         MinCand best;
@@ -1645,10 +1666,8 @@ __global__ __launch_bounds__(RANK_BLOCK, RANK_WAVES_PER_SIMD) void rank_loop_ker
             if (!force) RANK_TICK(6);
             if constexpr (FUSE) {                            // how many slots changed cell this pass: the next pass's form
                 if (c0 + RANK_QCAP >= n_pass) {
-                    int w = n_rel;
-#pragma unroll
-                    for (int off = 32; off > 0; off >>= 1) w += __shfl_xor(w, off, 64);
-                    if (lane == 0 && w) atomicAdd(&s_nrel, w);
+                    const int w = wave_sum_lane63_dpp(n_rel);
+                    if (lane == 63 && w) atomicAdd(&s_nrel, w);
                 }
             }
             __syncthreads();
@@ -1728,11 +1747,22 @@ __global__ __launch_bounds__(RANK_BLOCK, RANK_WAVES_PER_SIMD) void rank_loop_ker
                 if (tid == 0) tl->cursor = pos;
             }
         }
+        if (!force) RANK_TICK(9);
         wave_min_pair_dpp(best.t, best.i);
         if (lane == 0) { sh.wt[tid >> 6] = best.t; sh.wi[tid >> 6] = best.i; }
-        if (relocated) atomicAdd(reinterpret_cast<unsigned long long *>(&st.n_relocated), (unsigned long long)relocated);
-        if (not_found) atomicAdd(reinterpret_cast<unsigned long long *>(&st.not_found), (unsigned long long)not_found);
+        if (!force) RANK_TICK(10);
+        // the pass's counts: summed within the wave, then one LDS atomic per wave (integer sums: any order) -- an atomic per thread put some 250
+        // 64-bit adds on ONE address per list and pass, 6.3 k of the 10.4 k ticks between the barrier behind phase 1 and the walk
+        {
+            const int w_rel = wave_sum_lane63_dpp(relocated), w_nf = wave_sum_lane63_dpp(not_found);
+            if (lane == 63) {
+                if (w_rel) atomicAdd(reinterpret_cast<unsigned long long *>(&st.n_relocated), (unsigned long long)w_rel);
+                if (w_nf) atomicAdd(reinterpret_cast<unsigned long long *>(&st.not_found), (unsigned long long)w_nf);
+            }
+        }
+        if (!force) RANK_TICK(11);
         __syncthreads();
+        if (!force) RANK_TICK(12);
         prev_rel = s_nrel;                                   // (complete since the barrier after phase 1; reset after the next ones)
         MinCand g;
         g.init();
@@ -1740,7 +1770,7 @@ __global__ __launch_bounds__(RANK_BLOCK, RANK_WAVES_PER_SIMD) void rank_loop_ker
         for (int wv = 0; wv < EVENT_BLOCK / 64; ++wv) g.offer(sh.wt[wv], sh.wi[wv]);
         Cand gmin;
         gmin.t = g.t; gmin.idx = g.i; gmin.pad = 0;
-        if (force) RANK_TICK(1); else RANK_TICK(2);
+        if (force) RANK_TICK(1); else RANK_TICK(13);
         // ---- the event half and the bookkeeping
         const bool frame_goes_on = gmin.t < st.remaining_time;          // (else this pass ends the frame, mcrat.c:834: nobody needs further draws)
         // the wavefronts that do not walk draw for the next pass now; they join the others at the barrier behind the walk (event_block)
@@ -1801,6 +1831,7 @@ __global__ __launch_bounds__(RANK_BLOCK, RANK_WAVES_PER_SIMD) void rank_loop_ker
         RANK_TICK(3);
 #ifdef MCRAT_DIAG
         dg[5] += 1;
+        if (!force) dg[14] += 1;
 #endif
         if (st.done) break;
     }
@@ -1823,7 +1854,8 @@ __global__ __launch_bounds__(RANK_BLOCK, RANK_WAVES_PER_SIMD) void rank_loop_ker
 #ifdef MCRAT_DIAG
         __syncthreads();
         RANK_TICK(4);
-        if (tid == 0) for (int k = 0; k < 8; ++k) st.stamps[k] = dg[k];
+        dg[2] = dg[9] + dg[10] + dg[11] + dg[12] + dg[13];         // ("phase 2 + minimum" as one figure, as before the stretch was split)
+        if (tid == 0) for (int k = 0; k < 8; ++k) st.stamps[k] = (g_diag & 2048) ? (k < 6 ? dg[8 + k] : dg[k == 6 ? 5 : 14]) : dg[k];   // 2048: the serial stretch's stamps instead
         if (tid == 0 && dg_clock) {
             st.stamps[0] = dg_real0; st.stamps[1] = (long long)__builtin_amdgcn_s_memrealtime();
             st.stamps[2] = (long long)__builtin_amdgcn_s_memtime() - dg_tick0;
