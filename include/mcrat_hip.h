@@ -891,6 +891,10 @@ int mcrat_hip_pool_sightline_photons(mcrat_hip_ctx *pool, const mcrat_hip_ctx *h
 int mcrat_hip_synchronize(mcrat_hip_ctx *ctx);
 size_t mcrat_hip_device_bytes(const mcrat_hip_ctx *ctx);   /* HBM held by the context */
 int mcrat_hip_lookup_cell(mcrat_hip_ctx *ctx, int n, const double *a0, const double *a1, const double *a2, int *cell_out); /* device cell search == findContainingBlock geometry.c:350 */
+/* The staged frame's covered-octant table (one int per lookup bucket and octant, bucket-major: the cell that covers the octant, or -1): returns its
+ * number of entries -- 0: the frame's grid has none (a log-mapped axis, above the size cap, MCRAT_HIP_NO_COVERED), negative: an MCRAT_HIP_E* code --
+ * and copies the first min(entries, cap) to out (out may be NULL with cap 0). */
+long long mcrat_hip_covered_octants(mcrat_hip_ctx *ctx, int *out, long long cap);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

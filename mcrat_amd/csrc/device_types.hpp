@@ -142,6 +142,12 @@ struct alignas(16) BucketDir {
     unsigned pad;
 };
 
+// The covered-octant table (hydro_plan.hpp, octant_covered): one int per (bucket, octant), the cell index where the octant, shrunk by half the
+// accept margin of a bucket code, lies so far inside its one hinted cell that every point with GRID_CODE_HINT_OK passes well_in_fat_cell there; -1
+// elsewhere.  A lookup reads this entry first and, where it names a cell, that cell's CellFluid record -- no BucketDir, no FatCell, no in-cell test.
+// It lies in the grid buffer right in front of `dir`, cov_back ints back (0: there is no table and every lookup goes through `dir`), so that a
+// kernel needs no pointer of its own for it.
+constexpr double GRID_ACCEPT_MARGIN = 1e-6;  // of a bucket width: how far a point with GRID_CODE_HINT_OK lies from its octant's faces
 struct GridDev {
     const BucketDir *dir;        // [nb]
     const FatCell *cells;        // bucket lists, ascending in cell index inside each bucket
@@ -150,7 +156,15 @@ struct GridDev {
     int dim[3];
     int logmap[3];
     int naxes;
+    int cov_back;                // the covered-octant table starts this many ints in front of dir: [nb << naxes]
 };
+static_assert(sizeof(GridDev) == 96, "cov_back fills what was padding");
+constexpr long long GRID_COVERED_MAX_INTS = 1ll << 26;   // no table above 256 MiB (hydro_plan.hpp, covered_table_ints)
+// the table's entry of a bucket code (an int: the table holds no more than GRID_COVERED_MAX_INTS)
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline int covered_index(int code, int naxes) { return ((code & GRID_CODE_BUCKET_MASK) << naxes) | ((code >> GRID_CODE_OCT_SHIFT) & ((1 << naxes) - 1)); }
 
 struct HydroDev {
     const CellGeom *geom;

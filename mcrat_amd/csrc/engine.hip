@@ -589,6 +589,7 @@ struct HydroStage {
     GridScale scale{};                // device build: the grid up to its scale factor, from the staging kernel's statistics
     GridPlan plan{};                  // the grid that is built, with its buckets and list entries
     long long nb = 0, entries = 0;
+    size_t covered_ints = 0;          // the covered-octant table's ints (covered_table_ints); 0: the grid has none
     bool any_hot = false;             // a cell has T >= 1e7 K: the frame gets the k2e column
     template <class T> T *cell_at(size_t o) const { return reinterpret_cast<T *>(static_cast<char *>(c->hy_buf) + o); }
     template <class T> T *grid_at(size_t o) const { return reinterpret_cast<T *>(static_cast<char *>(c->grid_buf) + o); }
@@ -717,9 +718,13 @@ int choose_scale_device(HydroStage &s)
     return MCRAT_HIP_OK;
 }
 
+// (MCRAT_HIP_NO_COVERED in the environment: the grid without its covered-octant table, every lookup through the bucket records -- for A/B runs)
 int ensure_grid_buffer(HydroStage &s)
 {
-    s.grid = grid_layout(s.nb, s.entries, grid_scan_scratch_ints(s.nb));
+    s.covered_ints = covered_table_ints(s.plan, s.nb, getenv("MCRAT_HIP_NO_COVERED") == nullptr);
+    s.grid = grid_layout(s.nb, s.entries, grid_scan_scratch_ints(s.nb), s.covered_ints);
+    if (getenv("MCRAT_HIP_VERBOSE"))
+        fprintf(stderr, "mcrat_hip: covered-octant table %zu B of the grid's %zu B\n", s.grid.dir - s.grid.covered, s.grid.total);
     return ensure_device_bytes(s.c, &s.c->grid_buf, &s.c->grid_bytes, s.grid.total);
 }
 
@@ -728,7 +733,8 @@ int build_grid_device(HydroStage &s)
     mcrat_hip_ctx *c = s.c;
     const GridLayout &g = s.grid;
     HIPCHK(c, grid_build(s.plan, c->hy.geom, c->hy.geom2, c->hy.fluid, c->hy.fluid_c, s.M, c->grid_count, s.grid_at<int>(g.start), s.grid_at<int>(g.scan),
-                         s.grid_at<int>(g.entries), s.grid_at<FatCell>(g.cells), s.grid_at<BucketDir>(g.dir), s.nb, s.entries, c->stream));
+                         s.grid_at<int>(g.entries), s.grid_at<FatCell>(g.cells), s.grid_at<BucketDir>(g.dir),
+                         s.covered_ints ? s.grid_at<int>(g.covered) : nullptr, s.nb, s.entries, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return MCRAT_HIP_OK;
 }
@@ -745,6 +751,7 @@ int upload_host_grid(HydroStage &s, const HostFrame &hf)
     for (size_t b = 0; b < (size_t)s.nb; ++b) {
         dir[b].e0 = g.start[b]; dir[b].n = g.start[b + 1] - g.start[b]; dir[b].hints = g.hints[b]; dir[b].pad = 0;
     }
+    if (s.covered_ints) memcpy(gh.data() + s.grid.covered, g.covered.data(), sizeof(int) * s.covered_ints);   // (the same size rule: build_grid)
     FatCell *fat = reinterpret_cast<FatCell *>(gh.data() + s.grid.cells);
     for (size_t e = 0; e < g.cells.size(); ++e) {
         const int ci = g.cells[e];
@@ -760,6 +767,7 @@ void publish_grid(HydroStage &s)
     hy.grid.dir = s.grid_at<const BucketDir>(s.grid.dir);
     hy.grid.cells = s.grid_at<const FatCell>(s.grid.cells);
     grid_plan_to_dev(s.plan, hy.grid);
+    hy.grid.cov_back = s.covered_ints ? (int)((s.grid.dir - s.grid.covered) / sizeof(int)) : 0;
     apply_hot_table(s.c);
 }
 
@@ -4244,6 +4252,23 @@ extern "C" int mcrat_hip_eval_function(mcrat_hip_ctx *c, int fn, int n, const do
     (void)hipFree(d_out);
     HIPCHK(c, e);
     return MCRAT_HIP_OK;
+}
+
+extern "C" long long mcrat_hip_covered_octants(mcrat_hip_ctx *c, int *out, long long cap)
+{
+    if (!c || cap < 0 || (cap > 0 && !out)) return MCRAT_HIP_EINVAL;
+    if (!c->have_hydro) return MCRAT_HIP_ESTATE;
+    const GridDev &g = c->hy.grid;
+    if (!g.cov_back) return 0;
+    const long long n = ((long long)g.dim[0] * g.dim[1] * g.dim[2]) << g.naxes;
+    if (std::min(n, cap) > 0) {
+        if (hipStreamSynchronize(c->stream) != hipSuccess ||
+            hipMemcpy(out, reinterpret_cast<const int *>(g.dir) - g.cov_back, sizeof(int) * (size_t)std::min(n, cap), hipMemcpyDeviceToHost) != hipSuccess) {
+            c->last_error = "covered_octants failed";
+            return MCRAT_HIP_EHIP;
+        }
+    }
+    return n;
 }
 
 extern "C" int mcrat_hip_lookup_cell(mcrat_hip_ctx *c, int n, const double *a0, const double *a1, const double *a2, int *out)

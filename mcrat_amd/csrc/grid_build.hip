@@ -190,10 +190,11 @@ __global__ __launch_bounds__(256) void grid_records_kernel(int naxes, long long 
     cells[e] = fc;
 }
 
-// one thread per bucket: order its entries by cell index and find the octant hints (from the cells' geometry records)
+// one thread per bucket: order its entries by cell index and find the octant hints (from the cells' geometry records) and, where the grid has
+// the table (covered != nullptr), which octants their hinted cells cover (hydro_plan.hpp, octant_covered)
 __global__ __launch_bounds__(256) void grid_finish_kernel(GridPlan p, long long nb, const int *__restrict__ start, int *__restrict__ entries,
                                                           const CellGeom *__restrict__ geom, const CellGeom2 *__restrict__ geom2,
-                                                          BucketDir *__restrict__ dir)
+                                                          BucketDir *__restrict__ dir, int *__restrict__ covered)
 {
     const long long b = (long long)blockIdx.x * 256 + threadIdx.x;
     if (b >= nb) return;
@@ -219,6 +220,7 @@ __global__ __launch_bounds__(256) void grid_finish_kernel(GridPlan p, long long 
         half[k] = 0.5 * w;
     }
     unsigned char cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0}, first[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int cov[8] = {-1, -1, -1, -1, -1, -1, -1, -1};     // the first entry reaching into an octant, where it covers it: the hinted one if it stays the only one
     for (int e = 0; e < n; ++e) {
         const int ci = entries[e0 + e];
         const CellGeom g = geom[ci];
@@ -234,7 +236,10 @@ __global__ __launch_bounds__(256) void grid_finish_kernel(GridPlan p, long long 
         for (int o = 0; o < nocts; ++o) {
             const bool reaches = r[0][o & 1] && r[1][(o >> 1) & 1] && r[2][(o >> 2) & 1];
             if (reaches) {
-                if (cnt[o] == 0) first[o] = (unsigned char)(e < (int)GRID_NO_HINT ? e : GRID_NO_HINT);
+                if (cnt[o] == 0) {
+                    first[o] = (unsigned char)(e < (int)GRID_NO_HINT ? e : GRID_NO_HINT);
+                    if (covered && e < (int)GRID_NO_HINT && octant_covered(p, bi, o, cc, ss)) cov[o] = ci;
+                }
                 if (cnt[o] < 2) cnt[o] += 1;
             }
         }
@@ -247,6 +252,8 @@ __global__ __launch_bounds__(256) void grid_finish_kernel(GridPlan p, long long 
     BucketDir d;
     d.e0 = e0; d.n = n; d.hints = hints; d.pad = 0;
     dir[b] = d;
+    if (covered)
+        for (int o = 0; o < nocts; ++o) covered[(b << p.naxes) + o] = cnt[o] == 1 ? cov[o] : -1;
 }
 
 }  // namespace
@@ -274,7 +281,7 @@ hipError_t launch_exclusive_scan(const unsigned *count, long long n, int *start,
 }
 
 hipError_t grid_build(const GridPlan &p, const CellGeom *geom, const CellGeom2 *geom2, const CellFluid *fluid, const double *fluid_c, int M,
-                      unsigned *count, int *start, int *scan_scratch, int *entries, FatCell *cells, BucketDir *dir, long long nb,
+                      unsigned *count, int *start, int *scan_scratch, int *entries, FatCell *cells, BucketDir *dir, int *covered, long long nb,
                       long long total, hipStream_t stream)
 {
     hipError_t e = launch_exclusive_scan(count, nb, start, scan_scratch, total, stream);
@@ -282,7 +289,7 @@ hipError_t grid_build(const GridPlan &p, const CellGeom *geom, const CellGeom2 *
     e = hipMemsetAsync(count, 0, sizeof(unsigned) * (size_t)nb, stream);      // now the fill cursors
     if (e != hipSuccess) return e;
     grid_fill_kernel<<<dim3((M + 255) / 256), dim3(256), 0, stream>>>(p, geom, geom2, M, start, count, entries);
-    grid_finish_kernel<<<dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, stream>>>(p, nb, start, entries, geom, geom2, dir);
+    grid_finish_kernel<<<dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, stream>>>(p, nb, start, entries, geom, geom2, dir, covered);
     if (total > 0)
         grid_records_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream>>>(p.naxes, total, entries, geom, geom2, fluid, fluid_c, cells);
     return hipGetLastError();

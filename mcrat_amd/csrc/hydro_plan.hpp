@@ -208,6 +208,7 @@ struct GridHost {
     long long nb = 0;
     std::vector<int> start, cells;    // bucket b's list: cells[start[b] .. start[b + 1])
     std::vector<unsigned> hints;      // per bucket, see BucketDir
+    std::vector<int> covered;         // per bucket and octant, see GridDev::cov_back; empty: the plan gets no table (covered_table_ints)
 };
 // the buckets [b0, b1] of axis k that cell i's closed extent, widened by 1e-9 of (|centre| + width), touches
 inline void cell_bucket_range(const GridPlan &p, int k, double c, double s, int &b0, int &b1)
@@ -248,6 +249,58 @@ inline unsigned bucket_hints(const GridPlan &p, const int bi[3], const int *list
         h |= pick << (4 * o);
     }
     return h;
+}
+// The covered rule, once for the host build and for grid_build.hip (GridDev::cov_back, device_types.hpp): octant o of bucket bi is covered by
+// its hinted cell (centre c, width s per axis) when on every axis
+//   (a) the cell's extent [c - s/2, c + s/2] holds the octant shrunk inward by m = 0.5e-6 w, half the accept margin of a bucket code (w = the
+//       bucket's width), and
+//   (b) m >= 1e-8 s + 64 DBL_EPSILON (|c| + s).
+// Then every point whose code carries GRID_CODE_HINT_OK for this octant passes well_in_fat_cell on that cell: the point lies 1e-6 w inside the
+// octant's faces (grid_bucket_axes), so by (a) at least m inside the cell's, and well_in asks for 0.5e-8 s.  (b) leaves m - 0.5e-8 s >= 0.5e-8 s
+// + 64 ulp of the largest coordinate in play for what the roundings can move: the bucket coordinate x = (u - org) inv of at most 65 537 carries
+// 2 roundings (1.5e-11 w), the faces org + (b + h/2) w of this function 4 (2^-52 (65 537 w + |c| + s)), the cell's faces c -+ s/2 one each,
+// well_in's own 2 |a - c| - s two of at most 2^-53 s -- under 8 ulp of |c| + s and 4e-11 w together, and s > 0.49 w in a cell that holds an
+// octant.  A NaN fails a comparison, and a log-mapped axis is never covered: in the mapped coordinate the margins are no fixed part of a width.
+constexpr double GRID_COVER_GUARD = 64 * 2.220446049250313e-16;
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline bool octant_covered(const GridPlan &p, const int bi[3], int o, const double c[3], const double s[3])
+{
+    bool covered = true;
+    for (int k = 0; k < p.naxes; ++k) {
+        const double w = 1.0 / p.inv[k];
+        const double olo = p.org[k] + (bi[k] + 0.5 * ((o >> k) & 1)) * w, ohi = olo + 0.5 * w;      // as bucket_hints has them
+        const double m = 0.5 * GRID_ACCEPT_MARGIN * w;
+        const bool holds = (c[k] - 0.5 * s[k] <= olo + m) & (c[k] + 0.5 * s[k] >= ohi - m);
+        const bool implied = m >= 1e-8 * s[k] + GRID_COVER_GUARD * (fabs(c[k]) + s[k]);
+        covered = covered & holds & implied & (p.logmap[k] == 0);
+    }
+    return covered;
+}
+// The size rule: the ints of a plan's table, one per bucket and octant -- or 0, no table, when it is switched off (MCRAT_HIP_NO_COVERED), when
+// an axis is log-mapped (nothing would be covered), or above GRID_COVERED_MAX_INTS (256 MiB; the benchmark's 2.6 M buckets take 42 MB, a 3-D
+// grid 32 B per bucket, and the lists of a grid that size weigh gigabytes already).
+inline size_t covered_table_ints(const GridPlan &p, long long nb, bool enabled)
+{
+    if (!enabled || nb <= 0) return 0;
+    for (int k = 0; k < p.naxes; ++k)
+        if (p.logmap[k]) return 0;
+    const long long ints = nb << p.naxes;
+    return ints > GRID_COVERED_MAX_INTS ? 0 : (size_t)ints;
+}
+// a bucket's 2^naxes table entries from its hints (bucket_hints): out[o] = the hinted cell where it covers octant o, else -1
+inline void bucket_covered(const GridPlan &p, const int bi[3], const int *list, unsigned hints, const double *const c[3], const double *const s[3], int *out)
+{
+    for (int o = 0; o < (1 << p.naxes); ++o) {
+        const unsigned pick = (hints >> (4 * o)) & 15u;
+        out[o] = -1;
+        if (pick == GRID_NO_HINT) continue;
+        const int ci = list[pick];
+        double cc[3] = {0, 0, 0}, ss[3] = {0, 0, 0};
+        for (int k = 0; k < p.naxes; ++k) { cc[k] = c[k][ci]; ss[k] = s[k][ci]; }
+        if (octant_covered(p, bi, o, cc, ss)) out[o] = ci;
+    }
 }
 // The grid of a mesh given as host columns (c, s as for mesh_stats_from_columns).  false: a degenerate mesh, or no scale fits it.  The counting
 // pass of an attempt ends as soon as the total is over the limit.  MCRAT_HIP_VERBOSE in the environment: two lines on stderr.
@@ -293,12 +346,20 @@ inline bool build_grid(const double *const c[3], const double *const s[3], int M
         const int e0 = g.start[(size_t)b];
         g.hints[(size_t)b] = bucket_hints(p, bi, g.cells.data() + e0, g.start[(size_t)b + 1] - e0, c, s);
     }
+    g.covered.assign(covered_table_ints(p, nb, true), -1);
+    for (long long b = 0; b < nb && !g.covered.empty(); ++b) {
+        const int bi[3] = {(int)(b % p.dim[0]), (int)((b / p.dim[0]) % p.dim[1]), (int)(b / ((long long)p.dim[0] * p.dim[1]))};
+        bucket_covered(p, bi, g.cells.data() + g.start[(size_t)b], g.hints[(size_t)b], c, s, g.covered.data() + ((size_t)b << naxes));
+    }
     if (getenv("MCRAT_HIP_VERBOSE")) {
         const int nocts = 1 << naxes;
         long long hinted = 0;
         for (long long b = 0; b < nb; ++b)
             for (int o = 0; o < nocts; ++o) hinted += ((g.hints[(size_t)b] >> (4 * o)) & 15u) != GRID_NO_HINT;
         fprintf(stderr, "mcrat_hip: %.1f %% of the bucket octants have a single-cell hint\n", 100.0 * hinted / ((double)nb * nocts));
+        long long cov = 0;
+        for (int e : g.covered) cov += e >= 0;
+        fprintf(stderr, "mcrat_hip: %.1f %% of the bucket octants are covered by their hinted cell\n", 100.0 * cov / ((double)nb * nocts));
     }
     return true;
 }
@@ -366,16 +427,18 @@ inline CellLayout cell_layout(int dimensions, int M, bool reserve_k2e)
     l.total = off;
     return l;
 }
-// The grid buffer of nb buckets and `entries` list entries: the bucket records and the lists (room for one entry where there is none), which
+// The grid buffer of nb buckets and `entries` list entries: the covered-octant table (covered_ints of covered_table_ints; none: offset 0 like the
+// bucket records, which then open the buffer), the bucket records and the lists (room for one entry where there is none), which
 // the lookup reads, then what only the device build uses -- the lists' starts (nb + 1), the scan's scratch (scan_scratch_ints: the launcher's
 // grid_scan_scratch_ints(nb)) and the entries' cell indices.  The host build uploads [0, start).
 struct GridLayout {
-    size_t dir, cells, start, scan, entries, total;
+    size_t dir, cells, start, scan, entries, total, covered;
 };
-inline GridLayout grid_layout(long long nb, long long entries, size_t scan_scratch_ints)
+inline GridLayout grid_layout(long long nb, long long entries, size_t scan_scratch_ints, size_t covered_ints = 0)
 {
     GridLayout l{};
     size_t off = 0;
+    l.covered = layout_take(off, sizeof(int) * covered_ints);
     l.dir = layout_take(off, sizeof(BucketDir) * (size_t)nb);
     l.cells = layout_take(off, sizeof(FatCell) * std::max<size_t>((size_t)entries, 1));
     l.start = layout_take(off, sizeof(int) * ((size_t)nb + 1));

@@ -315,7 +315,7 @@ __device__ __forceinline__ double slow_one(const PH &ph, const HydroDev &hy, int
     if (relocate) {
         phys::hydro_coords<DIMS, GEOM>(r0, r1, r2, a0, a1, a2);
         FatCell hit;
-        cell = phys::find_in_bucket<DIMS>(hy.grid, bucket, a0, a1, a2, hit);     // mclib.c:534
+        cell = phys::find_in_bucket<DIMS>(hy, bucket, a0, a1, a2, hit);     // mclib.c:534
         ph.idx(i) = cell;                                                        // mclib.c:536
         if (cell != -1) {
             fa = hit.a; fb = hit.b; fc = hit.c; fw = hit.w; fnsig = hit.nsig; fgam = hit.gam; fkf = phys::kf_of_gamma(hit.gam);
@@ -400,35 +400,57 @@ struct LockstepProbe {
     bool *same;                  // [K] out: settled, and still in its cached cell
 };
 
-template <int DIMS, int GEOM, int K, bool LOGS = false, class PH>
-__device__ __forceinline__ void relocate_lockstep(const PH &ph, const HydroDev &hy, const int (&slot)[K], bool (&todo)[K],
-                                                  const double (&r0)[K], const double (&r1)[K], const double (&a0)[K], const double (&a1)[K],
-                                                  const double (&a2)[K], const int (&code)[K], const uint64_t (&bits)[K], const unsigned (&fl)[K],
-                                                  bool count_it, double (&t)[K], int &relocated, const LockstepProbe *probe = nullptr)
+// COVERED: the grid has the covered-octant table (device_types.hpp, GridDev::cov_back).  The first gather is then its 4-B entry and the second
+// the covered cell's own record in three pieces {a,b} {c,w} {nsig,gam} -- the bits the hinted entry copies; the in-cell test that entry would
+// pass is the table's premise (hydro_plan.hpp, octant_covered).  Slots in octants that are not covered stay `todo`, as slots without a hint do.
+// (Two instantiations and one wave-uniform branch around them, relocate_lockstep below.  Written as ONE function with the two gather stages as the
+// arms of a branch in front of the common arithmetic, the headline ran 8-10 % slower than before on a grid without a table and 4 % slower than
+// this form on one with it -- profiles/covered_lookup_before_after.txt: each path wants its loads and its arithmetic in one straight-line block.)
+template <int DIMS, int GEOM, int K, bool LOGS, bool COVERED, class PH>
+__device__ __forceinline__ void relocate_lockstep_impl(const PH &ph, const HydroDev &hy, const int (&slot)[K], bool (&todo)[K],
+                                                       const double (&r0)[K], const double (&r1)[K], const double (&a0)[K], const double (&a1)[K],
+                                                       const double (&a2)[K], const int (&code)[K], const uint64_t (&bits)[K], const unsigned (&fl)[K],
+                                                       bool count_it, double (&t)[K], int &relocated, const LockstepProbe *probe)
 {
     static_assert(!TABLE_MODE, "DIRECT optical depths");
     const GridDev &g = hy.grid;
-    BucketDir d[K];
     double p0[K], p1[K], p2[K], p3[K];
     bool take[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        take[k] = todo[k] && code[k] >= 0;
-        d[k] = g.dir[take[k] ? (code[k] & GRID_CODE_BUCKET_MASK) : 0];
-        const int i = slot[k];
-        p0[k] = ph.p0(i); p1[k] = ph.p1(i); p2[k] = ph.p2(i); p3[k] = ph.p3(i);
-    }
     FatCell f[K];
+    if constexpr (COVERED) {
+        int cell[K];
 #pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const unsigned hint = (d[k].hints >> (4 * ((code[k] >> GRID_CODE_OCT_SHIFT) & 7))) & 15u;
-        take[k] = take[k] & (d[k].n > 0) & ((code[k] & GRID_CODE_HINT_OK) != 0) & (hint != GRID_NO_HINT);
-        f[k] = g.cells[take[k] ? d[k].e0 + (int)hint : 0];
+        for (int k = 0; k < K; ++k) {
+            take[k] = todo[k] && code[k] >= 0 && (code[k] & GRID_CODE_HINT_OK) != 0;
+            cell[k] = phys::covered_cell<DIMS>(g, take[k] ? code[k] : 0);
+            const int i = slot[k];
+            p0[k] = ph.p0(i); p1[k] = ph.p1(i); p2[k] = ph.p2(i); p3[k] = ph.p3(i);
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            take[k] = take[k] & (cell[k] >= 0);
+            phys::fat_from_fluid(hy.fluid, take[k] ? cell[k] : 0, f[k]);
+        }
+    } else {
+        BucketDir d[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            take[k] = todo[k] && code[k] >= 0;
+            d[k] = g.dir[take[k] ? (code[k] & GRID_CODE_BUCKET_MASK) : 0];
+            const int i = slot[k];
+            p0[k] = ph.p0(i); p1[k] = ph.p1(i); p2[k] = ph.p2(i); p3[k] = ph.p3(i);
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const unsigned hint = (d[k].hints >> (4 * ((code[k] >> GRID_CODE_OCT_SHIFT) & 7))) & 15u;
+            take[k] = take[k] & (d[k].n > 0) & ((code[k] & GRID_CODE_HINT_OK) != 0) & (hint != GRID_NO_HINT);
+            f[k] = g.cells[take[k] ? d[k].e0 + (int)hint : 0];
+        }
     }
     double comv[K][4], tau[K], ntau[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        take[k] = take[k] & phys::well_in_fat_cell<DIMS>(f[k], a0[k], a1[k], a2[k]);
+        if constexpr (!COVERED) take[k] = take[k] & phys::well_in_fat_cell<DIMS>(f[k], a0[k], a1[k], a2[k]);
         double cphi, sphi;
         phys::relocation_azimuth<DIMS, GEOM>(r0[k], r1[k], a0[k], cphi, sphi);  // photon azimuth, mclib.c:549-552
         double beta[3];
@@ -461,6 +483,15 @@ __device__ __forceinline__ void relocate_lockstep(const PH &ph, const HydroDev &
         if (count_it) relocated += 1;                                            // mclib.c:579,608-611
         todo[k] = false;
     }
+}
+template <int DIMS, int GEOM, int K, bool LOGS = false, class PH>
+__device__ __forceinline__ void relocate_lockstep(const PH &ph, const HydroDev &hy, const int (&slot)[K], bool (&todo)[K],
+                                                  const double (&r0)[K], const double (&r1)[K], const double (&a0)[K], const double (&a1)[K],
+                                                  const double (&a2)[K], const int (&code)[K], const uint64_t (&bits)[K], const unsigned (&fl)[K],
+                                                  bool count_it, double (&t)[K], int &relocated, const LockstepProbe *probe = nullptr)
+{
+    if (hy.grid.cov_back) relocate_lockstep_impl<DIMS, GEOM, K, LOGS, true>(ph, hy, slot, todo, r0, r1, a0, a1, a2, code, bits, fl, count_it, t, relocated, probe);
+    else relocate_lockstep_impl<DIMS, GEOM, K, LOGS, false>(ph, hy, slot, todo, r0, r1, a0, a1, a2, code, bits, fl, count_it, t, relocated, probe);
 }
 
 // the streaming loads of one slot pair

@@ -355,8 +355,8 @@ size_t rebin_pool_scratch_bytes(int n, int total_bins);
 hipError_t launch_rebin_pool_range(const PhotonDev &pool, int three, const RebinPoolList *lists, int n_lists, RebinRange *out, hipStream_t stream);
 hipError_t launch_rebin_pool(const PhotonDev &pool, RebinPoolList *lists, int n_lists, char *scratch, hipStream_t stream);
 hipError_t grid_build(const GridPlan &p, const CellGeom *geom, const CellGeom2 *geom2, const CellFluid *fluid, const double *fluid_c, int M,
-                      unsigned *count, int *start, int *scan_scratch, int *entries, FatCell *cells, BucketDir *dir, long long nb,
-                      long long total, hipStream_t stream);
+                      unsigned *count, int *start, int *scan_scratch, int *entries, FatCell *cells, BucketDir *dir, int *covered, long long nb,
+                      long long total, hipStream_t stream);      // covered: the covered-octant table, or nullptr where the grid has none
 hipError_t launch_lookup(const KernelConfig &kc, const HydroDev &hy, int n, const double *a0, const double *a1,
                          const double *a2, int *out, hipStream_t stream);
 // The launchers that every kernels translation unit (kernels.hip: one per TAU_CALCULATION and DIMENSIONS) defines for itself; launchers.hip picks the

@@ -224,11 +224,31 @@ __device__ __forceinline__ int walk_bucket(const GridDev &g, int e0, int n, doub
 // the bucket, so the first hit of the list walk equals the reference's linear first match; the hinted entry
 // (BucketDir) short-cuts the walk only where it provably gives the same answer.  Two dependent loads: the
 // bucket's record, then one entry -- each entry a complete copy of the cell's records.  `hit` receives the entry.
+// Where the grid has the covered-octant table (GridDev::cov_back) that is read first: a code with GRID_CODE_HINT_OK whose octant is covered is
+// settled by the 4-B entry -- the cell the hinted entry would give, provably (hydro_plan.hpp, octant_covered) -- and `hit` receives the cell's
+// own CellFluid record, the bits the entry copies (a, b, c, w, nsig, gam, cell; its geometry members are not set).
 template <int DIMS>
-__device__ __forceinline__ int find_in_bucket(const GridDev &g, int code, double a0, double a1, double a2, FatCell &hit)
+__device__ __forceinline__ int covered_cell(const GridDev &g, int code)
 {
+    return reinterpret_cast<const int *>(g.dir)[covered_index(code, DIMS == DIM_THREE ? 3 : 2) - g.cov_back];   // (three axes in 3-D, two otherwise)
+}
+__device__ __forceinline__ void fat_from_fluid(const CellFluid *fluid, int cell, FatCell &hit)
+{
+    const double2 ab = *reinterpret_cast<const double2 *>(&fluid[cell].a), cw = *reinterpret_cast<const double2 *>(&fluid[cell].c),
+                  ng = *reinterpret_cast<const double2 *>(&fluid[cell].nsig);
+    hit.a = ab.x; hit.b = ab.y; hit.c = cw.x; hit.w = cw.y; hit.nsig = ng.x; hit.gam = ng.y;
+    hit.cell = cell;
+}
+template <int DIMS>
+__device__ __forceinline__ int find_in_bucket(const HydroDev &h, int code, double a0, double a1, double a2, FatCell &hit)
+{
+    const GridDev &g = h.grid;
     hit.cell = -1;
     if (code < 0) return -1;
+    if (g.cov_back && (code & GRID_CODE_HINT_OK)) {
+        const int cell = covered_cell<DIMS>(g, code);
+        if (cell >= 0) { fat_from_fluid(h.fluid, cell, hit); return cell; }
+    }
     const BucketDir d = g.dir[code & GRID_CODE_BUCKET_MASK];
     if (d.n <= 0) return -1;
     const unsigned hint = (d.hints >> (4 * ((code >> GRID_CODE_OCT_SHIFT) & 7))) & 15u;
@@ -243,7 +263,7 @@ template <int DIMS>
 __device__ __forceinline__ int find_containing_block(const HydroDev &h, double a0, double a1, double a2)
 {
     FatCell hit;
-    return find_in_bucket<DIMS>(h.grid, grid_bucket_of<DIMS>(h.grid, a0, a1, a2), a0, a1, a2, hit);
+    return find_in_bucket<DIMS>(h, grid_bucket_of<DIMS>(h.grid, a0, a1, a2), a0, a1, a2, hit);
 }
 
 // geometry.c:189-253 on a staged record (see cell_beta below)

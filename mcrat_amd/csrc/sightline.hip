@@ -146,7 +146,7 @@ __global__ __launch_bounds__(SIGHTLINE_BLOCK) void sightline_kernel(PhotonDev ph
                 FatCell hit;
                 hit.cell = -1;
                 if (phys::in_domain<DIMS>(hy, a0, a1, a2))
-                    phys::find_in_bucket<DIMS>(hy.grid, phys::grid_bucket_of<DIMS>(hy.grid, a0, a1, a2), a0, a1, a2, hit);
+                    phys::find_in_bucket<DIMS>(hy, phys::grid_bucket_of<DIMS>(hy.grid, a0, a1, a2), a0, a1, a2, hit);
                 if (hit.cell < 0) {
                     status = SIGHTLINE_LEFT_MESH;
                 } else {

@@ -317,6 +317,7 @@ SYMBOLS = {
     "mcrat_hip_device_bytes": (C.c_size_t, [_ctx]),
     "mcrat_hip_eval_function": (C.c_int, [_ctx, C.c_int, C.c_int, _dp, _dp, C.c_uint64]),
     "mcrat_hip_lookup_cell": (C.c_int, [_ctx, C.c_int, _dp, _dp, _dp, _ip]),
+    "mcrat_hip_covered_octants": (C.c_longlong, [_ctx, _ip, C.c_longlong]),
 }
 
 _lib = None
@@ -1084,6 +1085,15 @@ class Engine:
         a = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, wi)
         out = np.empty((a.shape[0], wo))
         self._check(self.lib.mcrat_hip_eval_function(self.ctx, fn, a.shape[0], a.ctypes.data_as(_dp), out.ctypes.data_as(_dp), int(seed)), "eval_function")
+        return out
+
+    def covered_octants(self):
+        """the staged frame's covered-octant table, one int32 per lookup bucket and octant (cell index or -1); empty: the frame's grid has none"""
+        n = int(self.lib.mcrat_hip_covered_octants(self.ctx, None, 0))
+        self._check(min(n, 0), "covered_octants")
+        out = np.empty(n, dtype=np.int32)
+        if n:
+            self._check(min(int(self.lib.mcrat_hip_covered_octants(self.ctx, out.ctypes.data_as(_ip), n)), 0), "covered_octants")
         return out
 
     def lookup_cell(self, a0, a1, a2=None):
