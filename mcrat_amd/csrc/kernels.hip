@@ -2121,9 +2121,16 @@ __global__ __launch_bounds__(FAST_BLOCK, 2) void fast_frame_kernel(PhotonDev ph,
                     } else {
                         adv = limit;
                         t_left[k] -= adv;
-                        w_left[k] = window;                                 // a window boundary: the next pass re-locates and redraws
+                        // a window boundary: the next pass re-locates and redraws.  There are `windows` windows: the last one ends with the frame,
+                        // so it is as long as the clock has left (t_left is k windows but for the roundings of the flights, k = 1 below 1.5).
+                        // With `window` again the two clocks of the last window are equal up to those roundings, and where t_left came out
+                        // an ulp above, the photon took one pass more through a sliver of a window, with a draw of its own (seven in ten did)
+                        w_left[k] = t_left[k] < 1.5 * window ? t_left[k] : window;
                     }
                 }
+                // time_to_scatter is the free time of the photon's last draw (mclib.c:687 stores it in every pass; only the slow path does here):
+                // a photon's last pass is the one that ends its frame, so one store per photon and frame leaves the column as the reference would
+                if (done[k]) ph.tts[i] = t[k];
                 if (moves[k]) {
                     const double u0 = ph.u0[i], u1 = ph.u1[i], u2 = ph.u2[i];
                     ph.r0[i] = r0[k] + u0 * adv; ph.r1[i] = r1[k] + u1 * adv; ph.r2[i] = r2[k] + u2 * adv;

@@ -377,6 +377,11 @@ double orc_kleinNishinaCrossSection(double e)
     return (1. - 2. * e);
 }
 
+/* the Klein-Nishina acceptance test is the one decision of an event that a single rounding of the device's logarithm could turn: while *min_margin
+ * is watched it is lowered to the smallest |uniform - acceptance ratio| / ratio of the tests made (NULL: not watched) */
+static _Thread_local double *kn_margin_watch = NULL;
+void orc_kn_margin_watch(double *min_margin) { kn_margin_watch = min_margin; }
+
 /* mcrat_scattering.c:509-595 */
 int orc_kleinNishinaScatter(const orc_config *c, double *theta, double *phi, double p0, double q, double u, orc_rng *rng)
 {
@@ -386,6 +391,10 @@ int orc_kleinNishinaScatter(const orc_config *c, double *theta, double *phi, dou
     double kn = orc_kleinNishinaCrossSection(energy_ratio);
     double rand_num = orc_rng_uniform(rng);
 
+    if (kn_margin_watch) {                         /* (a read-out for the tests; the draws and the decision are as before) */
+        const double d = fabs(rand_num - kn) / kn;
+        if (d < *kn_margin_watch) *kn_margin_watch = d;
+    }
     if (!(rand_num <= kn)) return 0;
 
     while (cos_theta_y_dum > f_cos_theta_dum) {
@@ -797,51 +806,59 @@ int orc_findContainingHydroCell(const orc_config *c, orc_photon_list *l, const o
     return orc_findContainingHydroCell_keyed(c, l, h, find_nearest_block_switch, st, NULL);
 }
 
+/* the body of findContainingHydroCell's loop for one photon (mclib.c:447-604); `slot` keys a look-up off the table.  Returns 1 when the photon was
+ * put into a cell by the search (mclib.c:579), 0 otherwise.  orc_fast_frame (oracle_fast.c) walks one photon at a time through this. */
+int orc_locatePhoton(const orc_config *c, orc_photon *ph, uint32_t slot, const orc_hydro *h, int find_nearest_block_switch, orc_stats *st,
+                     const orc_rng *rng)
+{
+    int n_new = 0;
+    int ph_block_index = (find_nearest_block_switch == 0) ? ph->nearest_block_index : 0;
+    double hc[3];
+    orc_mcratCoordinateToHydroCoordinate(c, hc, ph->r0, ph->r1, ph->r2);
+
+    int inside;
+    if (c->dimensions == ORC_TWO || c->dimensions == ORC_TWO_POINT_FIVE)
+        inside = (hc[1] < h->r1_domain[1]) && (hc[1] > h->r1_domain[0]) &&
+                 (hc[0] < h->r0_domain[1]) && (hc[0] > h->r0_domain[0]);
+    else
+        inside = (hc[2] < h->r2_domain[1]) && (hc[2] > h->r2_domain[0]) &&
+                 (hc[1] < h->r1_domain[1]) && (hc[1] > h->r1_domain[0]) &&
+                 (hc[0] < h->r0_domain[1]) && (hc[0] > h->r0_domain[0]);
+
+    if (inside && (ph->nearest_block_index != -1)) {
+        int is_in_block = orc_checkInBlock(c, hc[0], hc[1], hc[2], h, ph_block_index);
+        if (find_nearest_block_switch == 1 || !is_in_block) {
+            int min_index = orc_findContainingBlock(c, hc[0], hc[1], hc[2], h);
+            ph->nearest_block_index = min_index;
+            if (min_index != -1) {
+                double ph_p[4] = {ph->p0, ph->p1, ph->p2, ph->p3}, ph_p_comv[4], fluid_beta[3];
+                double ph_phi = atan2(ph->r1, ph->r0);
+                cell_beta_cartesian(c, h, min_index, ph_phi, fluid_beta);
+                orc_lorentzBoost(fluid_beta, ph_p, ph_p_comv, 'p');
+                ph->comv_p0 = ph_p_comv[0];
+                ph->comv_p1 = ph_p_comv[1];
+                ph->comv_p2 = ph_p_comv[2];
+                ph->comv_p3 = ph_p_comv[3];
+                orc_calculateOpticalDepth_keyed(c, ph, h, rng, slot);
+                if (ph->recalc_properties == 1) ph->recalc_properties = 0;
+                n_new += 1;
+            } else if (st) {
+                st->not_found += 1;
+            }
+        }
+    } else {
+        ph->nearest_block_index = -1;
+    }
+    return n_new;
+}
+
 /* (the reference's takes gsl_rng *rand for the look-ups off the table, mclib.c:436; `rng` here keys them) */
 int orc_findContainingHydroCell_keyed(const orc_config *c, orc_photon_list *l, const orc_hydro *h,
                                       int find_nearest_block_switch, orc_stats *st, const orc_rng *rng)
 {
     int n_new = 0;
-    for (int i = 0; i < l->list_capacity; i++) {
-        orc_photon *ph = &l->photons[i];
-        int ph_block_index = (find_nearest_block_switch == 0) ? ph->nearest_block_index : 0;
-        double hc[3];
-        orc_mcratCoordinateToHydroCoordinate(c, hc, ph->r0, ph->r1, ph->r2);
-
-        int inside;
-        if (c->dimensions == ORC_TWO || c->dimensions == ORC_TWO_POINT_FIVE)
-            inside = (hc[1] < h->r1_domain[1]) && (hc[1] > h->r1_domain[0]) &&
-                     (hc[0] < h->r0_domain[1]) && (hc[0] > h->r0_domain[0]);
-        else
-            inside = (hc[2] < h->r2_domain[1]) && (hc[2] > h->r2_domain[0]) &&
-                     (hc[1] < h->r1_domain[1]) && (hc[1] > h->r1_domain[0]) &&
-                     (hc[0] < h->r0_domain[1]) && (hc[0] > h->r0_domain[0]);
-
-        if (inside && (ph->nearest_block_index != -1)) {
-            int is_in_block = orc_checkInBlock(c, hc[0], hc[1], hc[2], h, ph_block_index);
-            if (find_nearest_block_switch == 1 || !is_in_block) {
-                int min_index = orc_findContainingBlock(c, hc[0], hc[1], hc[2], h);
-                ph->nearest_block_index = min_index;
-                if (min_index != -1) {
-                    double ph_p[4] = {ph->p0, ph->p1, ph->p2, ph->p3}, ph_p_comv[4], fluid_beta[3];
-                    double ph_phi = atan2(ph->r1, ph->r0);
-                    cell_beta_cartesian(c, h, min_index, ph_phi, fluid_beta);
-                    orc_lorentzBoost(fluid_beta, ph_p, ph_p_comv, 'p');
-                    ph->comv_p0 = ph_p_comv[0];
-                    ph->comv_p1 = ph_p_comv[1];
-                    ph->comv_p2 = ph_p_comv[2];
-                    ph->comv_p3 = ph_p_comv[3];
-                    orc_calculateOpticalDepth_keyed(c, ph, h, rng, (uint32_t)i);
-                    if (ph->recalc_properties == 1) ph->recalc_properties = 0;
-                    n_new += 1;
-                } else if (st) {
-                    st->not_found += 1;
-                }
-            }
-        } else {
-            ph->nearest_block_index = -1;
-        }
-    }
+    for (int i = 0; i < l->list_capacity; i++)
+        n_new += orc_locatePhoton(c, &l->photons[i], (uint32_t)i, h, find_nearest_block_switch, st, rng);
     if (find_nearest_block_switch != 0) n_new = 0;   /* mclib.c:608-611 */
     return n_new;
 }
@@ -929,6 +946,55 @@ void orc_updatePhotonPosition(orc_photon_list *l, double t)
     }
 }
 
+/* what photonEvent does to ONE candidate at the end of its flight (mclib.c:1144-1322): fluid frame at the photon's azimuth, Stokes rotation,
+ * electron draw, singleScatter, and on success the boost back and the stores.  `slot` opens the candidate's event stream in the current
+ * iteration.  Returns event_did_occur; a Klein-Nishina rejection changes nothing on the photon and is counted in st->kn_rejections.
+ * One copy for the event-driven loop (orc_photonEvent) and the photon-by-photon one (orc_fast_frame, oracle_fast.c). */
+int orc_scatterCandidate(const orc_config *c, orc_photon *ph, uint32_t slot, const orc_hydro *h, long long *frame_scatt_cnt, orc_rng *rng,
+                         orc_stats *st)
+{
+    int event_did_occur = 0;
+    int index = ph->nearest_block_index;
+    if (index != -1) {   /* documented deviation: see header */
+        double fluid_temp = h->temp[index];
+        double ph_phi = atan2(ph->r1, ph->r0);
+        double fluid_beta[3], negative_fluid_beta[3];
+        cell_beta_cartesian(c, h, index, ph_phi, fluid_beta);
+
+        double ph_p[4] = {ph->p0, ph->p1, ph->p2, ph->p3};
+        double ph_p_comov[4] = {ph->comv_p0, ph->comv_p1, ph->comv_p2, ph->comv_p3};
+        double s[4] = {ph->s0, ph->s1, ph->s2, ph->s3};
+        double el_p_comov[4];
+
+        if (c->stokes_switch) orc_stokesRotation(fluid_beta, ph_p + 1, ph_p_comov + 1, s); /* :1227 */
+
+        orc_rng_event_begin(rng, slot);
+        orc_singleThermalElectron(el_p_comov, fluid_temp, ph_p_comov, rng);            /* :1234 */
+        event_did_occur = orc_singleScatter(c, el_p_comov, ph_p_comov, s, rng);        /* :1245 */
+        if (st) st->event_draws += (long long)rng->n_draws;
+
+        if (event_did_occur == 1) {
+            negative_fluid_beta[0] = -1 * fluid_beta[0];
+            negative_fluid_beta[1] = -1 * fluid_beta[1];
+            negative_fluid_beta[2] = -1 * fluid_beta[2];
+            orc_lorentzBoost(negative_fluid_beta, ph_p_comov, ph_p, 'p');             /* :1265 */
+            if (c->stokes_switch) {
+                orc_stokesRotation(negative_fluid_beta, ph_p_comov + 1, ph_p + 1, s);  /* :1280 */
+                ph->s0 = s[0]; ph->s1 = s[1]; ph->s2 = s[2]; ph->s3 = s[3];
+            }
+            ph->p0 = ph_p[0]; ph->p1 = ph_p[1]; ph->p2 = ph_p[2]; ph->p3 = ph_p[3];
+            ph->comv_p0 = ph_p_comov[0]; ph->comv_p1 = ph_p_comov[1];
+            ph->comv_p2 = ph_p_comov[2]; ph->comv_p3 = ph_p_comov[3];
+            ph->num_scatt += 1;
+            *frame_scatt_cnt += 1;
+            ph->recalc_properties = 1;
+        } else if (st) {
+            st->kn_rejections += 1;
+        }
+    }
+    return event_did_occur;
+}
+
 /* mclib.c:1107-1356 */
 double orc_photonEvent(const orc_config *c, orc_photon_list *l, double dt_max, const orc_hydro *h,
                        int *scattered_ph_index, long long *frame_scatt_cnt, orc_rng *rng, orc_stats *st)
@@ -944,44 +1010,7 @@ double orc_photonEvent(const orc_config *c, orc_photon_list *l, double dt_max, c
 
         if (scatt_time < dt_max) {
             orc_updatePhotonPosition(l, scatt_time - old_scatt_time);
-            int index = ph->nearest_block_index;
-            if (index != -1) {   /* documented deviation: see header */
-                double fluid_temp = h->temp[index];
-                double ph_phi = atan2(ph->r1, ph->r0);
-                double fluid_beta[3], negative_fluid_beta[3];
-                cell_beta_cartesian(c, h, index, ph_phi, fluid_beta);
-
-                double ph_p[4] = {ph->p0, ph->p1, ph->p2, ph->p3};
-                double ph_p_comov[4] = {ph->comv_p0, ph->comv_p1, ph->comv_p2, ph->comv_p3};
-                double s[4] = {ph->s0, ph->s1, ph->s2, ph->s3};
-                double el_p_comov[4];
-
-                if (c->stokes_switch) orc_stokesRotation(fluid_beta, ph_p + 1, ph_p_comov + 1, s); /* :1227 */
-
-                orc_rng_event_begin(rng, (uint32_t)ph_index);
-                orc_singleThermalElectron(el_p_comov, fluid_temp, ph_p_comov, rng);            /* :1234 */
-                event_did_occur = orc_singleScatter(c, el_p_comov, ph_p_comov, s, rng);        /* :1245 */
-                if (st) st->event_draws += (long long)rng->n_draws;
-
-                if (event_did_occur == 1) {
-                    negative_fluid_beta[0] = -1 * fluid_beta[0];
-                    negative_fluid_beta[1] = -1 * fluid_beta[1];
-                    negative_fluid_beta[2] = -1 * fluid_beta[2];
-                    orc_lorentzBoost(negative_fluid_beta, ph_p_comov, ph_p, 'p');             /* :1265 */
-                    if (c->stokes_switch) {
-                        orc_stokesRotation(negative_fluid_beta, ph_p_comov + 1, ph_p + 1, s);  /* :1280 */
-                        ph->s0 = s[0]; ph->s1 = s[1]; ph->s2 = s[2]; ph->s3 = s[3];
-                    }
-                    ph->p0 = ph_p[0]; ph->p1 = ph_p[1]; ph->p2 = ph_p[2]; ph->p3 = ph_p[3];
-                    ph->comv_p0 = ph_p_comov[0]; ph->comv_p1 = ph_p_comov[1];
-                    ph->comv_p2 = ph_p_comov[2]; ph->comv_p3 = ph_p_comov[3];
-                    ph->num_scatt += 1;
-                    *frame_scatt_cnt += 1;
-                    ph->recalc_properties = 1;
-                } else if (st) {
-                    st->kn_rejections += 1;
-                }
-            }
+            event_did_occur = orc_scatterCandidate(c, ph, (uint32_t)ph_index, h, frame_scatt_cnt, rng, st);
         } else {
             scatt_time = dt_max;
             orc_updatePhotonPosition(l, scatt_time - old_scatt_time);

@@ -211,6 +211,36 @@ void   orc_photon_loop(const orc_config *c, orc_photon_list *l, const orc_hydro 
                        double *time_now, double *remaining_time, int *find_nearest_grid_switch,
                        long long max_iterations, uint64_t iteration_base, orc_stats *st);
 
+/* one photon of findContainingHydroCell's loop (mclib.c:447-604) and one candidate of photonEvent's (mclib.c:1144-1322): the bodies the two list
+ * functions above run, exposed for the photon-by-photon walk below */
+int    orc_locatePhoton(const orc_config *c, orc_photon *ph, uint32_t slot, const orc_hydro *h, int find_nearest_block_switch, orc_stats *st,
+                        const orc_rng *rng);
+int    orc_scatterCandidate(const orc_config *c, orc_photon *ph, uint32_t slot, const orc_hydro *h, long long *frame_scatt_cnt, orc_rng *rng,
+                            orc_stats *st);
+void   orc_kn_margin_watch(double *min_margin);   /* lowered to the smallest |u - ratio| / ratio of kleinNishinaScatter's acceptance tests; NULL: off */
+
+/* ---- FAST mode (oracle_fast.c): the engine's MCRAT_HIP_MODE_FAST restated one photon at a time ---------------------------------
+ * Within a frozen frame the photons are independent, so every photon goes through the whole frame on its own clock: locate, optical depth,
+ * free-path draw, flight, scattering, again.  Photon slot i draws the free path of its pass p from the keyed block {seed, iteration = p,
+ * word2 = i + slot_base, ORC_PURPOSE_FAST_FREEPATH, stream} (words 0 and 1) and its scattering from the event stream {seed, p, same slot}.  Cell
+ * and optical depth are refreshed at the boundaries of `windows` equal time windows and after the photon's own scatterings. */
+typedef struct orc_fast_counts {
+    long long photon_steps;     /* passes summed over the photons                                   */
+    long long scatterings;
+    long long kn_rejections;
+    long long relocated;        /* put into a cell by a search, the forced one of pass 0 included    */
+    long long not_found;
+    long long passes;           /* the largest number of passes a photon took                        */
+} orc_fast_counts;
+typedef struct orc_fast_margins {   /* how close the walk came to a decision that one rounding could turn (relative; DBL_MAX: never taken) */
+    double flight;              /* min |t - limit| / limit over the flights inside the cells          */
+    double kn;                  /* min |u - ratio| / ratio over the Klein-Nishina acceptance tests    */
+} orc_fast_margins;
+/* rng: orc_rng_init(seed, stream), or a tape (then a list of ONE photon reads the tape in the order orc_photon_loop would).
+ * flown / n_pass: optional [list_capacity] -- the photon's flights summed in the order flown, and its passes. */
+void   orc_fast_frame(const orc_config *c, orc_photon_list *l, const orc_hydro *h, orc_rng *rng, double remaining_time, int windows,
+                      uint32_t slot_base, orc_fast_counts *cnt, orc_fast_margins *mg, double *flown, int *n_pass);
+
 /* ---- hydro ingest (oracle_ingest.c) ---------------------- */
 /* every column of struct hydro_dataframe (Src/mcrat.h:194-244) a thermal build fills; malloc'ed, orc_frame_free() */
 typedef struct orc_frame {

@@ -71,6 +71,16 @@ class Stats(C.Structure):
                 ("remaining_time", C.c_double), ("time_now", C.c_double), ("table_fallbacks", C.c_longlong)]
 
 
+class FastCounts(C.Structure):
+    """orc_fast_counts (oracle_fast.c)"""
+    _fields_ = [("photon_steps", C.c_longlong), ("scatterings", C.c_longlong), ("kn_rejections", C.c_longlong),
+                ("relocated", C.c_longlong), ("not_found", C.c_longlong), ("passes", C.c_longlong)]
+
+
+class FastMargins(C.Structure):
+    _fields_ = [("flight", C.c_double), ("kn", C.c_double)]
+
+
 FRAME_FIELDS = ("r0", "r1", "r2", "r0_size", "r1_size", "r2_size", "v0", "v1", "v2", "dens", "dens_lab", "pres", "temp", "gamma", "r", "theta")
 
 
@@ -159,7 +169,7 @@ class Outflow(C.Structure):
 def build(force=False):
     if force or not os.path.exists(_LIB_PATH) or any(
             os.path.getmtime(os.path.join(_HERE, f)) > os.path.getmtime(_LIB_PATH)
-            for f in ("mcrat_oracle.c", "oracle_ingest.c", "oracle_cyclosynch.c", "mcrat_oracle.h", "oracle_rng.c", "oracle_rng.h")):
+            for f in ("mcrat_oracle.c", "oracle_fast.c", "oracle_ingest.c", "oracle_cyclosynch.c", "mcrat_oracle.h", "oracle_rng.c", "oracle_rng.h")):
         subprocess.run(["make", "-C", _HERE, "-B", "liboracle.so"], check=True, capture_output=True)
     return _LIB_PATH
 
@@ -247,6 +257,12 @@ def lib():
             "orc_frame_free": (None, [C.POINTER(Frame)]),
             "orc_outflow_defaults": (None, [i, C.POINTER(Outflow)]),
             "orc_hydro_post_read": (None, [cfgp, C.POINTER(Outflow), C.POINTER(Frame)]),
+            "orc_locatePhoton": (i, [cfgp, p, C.c_uint32, hp, i, sp, rp]),
+            "orc_scatterCandidate": (i, [cfgp, p, C.c_uint32, hp, C.POINTER(C.c_longlong), rp, sp]),
+            "orc_kn_margin_watch": (None, [_dp]),
+            "orc_rng_fast_freepath_draw": (d, [rp, C.c_uint32]),
+            "orc_rng_init_tape": (None, [rp, _dp, C.c_int64]),
+            "orc_fast_frame": (None, [cfgp, lp, hp, rp, d, i, C.c_uint32, C.POINTER(FastCounts), C.POINTER(FastMargins), _dp, C.POINTER(i)]),
             "orc_sizeof_photon": (i, []),
         }
         for name, (res, args) in sig.items():
@@ -361,6 +377,37 @@ def photon_loop(cfg, photons, hydro, seed, time_now, remaining_time, max_iterati
             raise RuntimeError("the tape ran out after %d uniforms" % rng.tape_pos)
         photon_loop.tape_pos = int(rng.tape_pos)
     return st, tn.value, rem.value, sw.value
+
+
+def fast_frame(cfg, photons, hydro, seed, stream, remaining_time, windows, slot_base=0, tape=None):
+    """orc_fast_frame (oracle_fast.c): the engine's FAST mode, one photon at a time -- photon slot i keyed as slot i + slot_base.  The photons are
+    changed in place; returns (photons, counters, margins).  The photons' flights summed and their passes are left in fast_frame.flown and
+    fast_frame.passes.  cfg.optimised: the cell search goes through the oracle's exact bucket grid (the same cells, faster).
+    tape: uniforms in [0,1) as the random stream (a list of one photon reads them in the order photon_loop does)."""
+    L = lib()
+    rng = Rng()
+    if tape is not None:
+        t = np.ascontiguousarray(tape, dtype=np.float64)
+        L.orc_rng_init_tape(C.byref(rng), t.ctypes.data_as(_dp), int(t.size))
+    else:
+        L.orc_rng_init(C.byref(rng), int(seed), int(stream))
+    n = photons.c.list_capacity
+    cnt, mg = FastCounts(), FastMargins()
+    flown, passes = np.zeros(n), np.zeros(n, dtype=np.int32)
+    if cfg.optimised:
+        L.orc_grid_attach(C.byref(cfg), C.byref(hydro.c))
+    try:
+        L.orc_fast_frame(C.byref(cfg), C.byref(photons.c), C.byref(hydro.c), C.byref(rng), float(remaining_time), int(windows), int(slot_base),
+                         C.byref(cnt), C.byref(mg), flown.ctypes.data_as(_dp), passes.ctypes.data_as(C.POINTER(C.c_int)))
+    finally:
+        if cfg.optimised:
+            L.orc_grid_detach()
+    if tape is not None:
+        if rng.tape_error:
+            raise RuntimeError("the tape ran out after %d uniforms" % rng.tape_pos)
+        fast_frame.tape_pos = int(rng.tape_pos)
+    fast_frame.flown, fast_frame.passes = flown, passes
+    return photons, cnt, mg
 
 
 # ---------------------------------------------------------------------------------------------- hydro ingest (oracle_ingest.c)

@@ -104,6 +104,14 @@ double orc_rng_freepath_upos(const orc_rng *r, uint32_t slot)
     return orc_bits_to_uniform_pos(orc_rng_freepath_bits(r, slot));
 }
 
+double orc_rng_fast_freepath_draw(orc_rng *r, uint32_t slot)
+{
+    uint32_t w[4];
+    if (r->tape) return orc_rng_uniform_pos(r);
+    keyed_block(r, slot, ORC_PURPOSE_FAST_FREEPATH, w);
+    return orc_bits_to_uniform_pos((uint64_t)w[0] | ((uint64_t)w[1] << 32));
+}
+
 void orc_rng_event_begin(orc_rng *r, uint32_t slot)
 {
     uint32_t w[4];

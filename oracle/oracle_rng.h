@@ -45,6 +45,10 @@
 #define ORC_PURPOSE_INJECT_COUNT  2u
 #define ORC_PURPOSE_INJECT_PHOTON 3u
 
+/* FAST mode (oracle_fast.c): the free-path draw of photon slot i in ITS pass p -- {ctr = {p_lo, p_hi, i, FAST_FREEPATH | stream<<8}}, output
+ * words 0 and 1 as one 64-bit value (a block per slot: the photons of a pair are not in the same pass of their frames) */
+#define ORC_PURPOSE_FAST_FREEPATH 8u
+
 typedef struct orc_rng {
     uint64_t seed;       /* frame seed (reference: gsl_rng_get at mcrat.c:701)   */
     uint64_t iteration;  /* global while-loop iteration k (mcrat.c:761)           */
@@ -70,6 +74,8 @@ void   orc_rng_init_tape(orc_rng *r, const double *tape, int64_t n);
 /* the free-path draw of slot i in the loop's ascending pass over the slots: keyed by (iteration, slot), or the next of the tape */
 double orc_rng_freepath_draw(orc_rng *r, uint32_t slot);
 void   orc_rng_set_iteration(orc_rng *r, uint64_t k);
+/* FAST mode's free-path draw of slot i in the current iteration (= the photon's pass), or the next of the tape */
+double orc_rng_fast_freepath_draw(orc_rng *r, uint32_t slot);
 
 /* free-path uniform_pos of photon slot i in the current iteration */
 double orc_rng_freepath_upos(const orc_rng *r, uint32_t slot);

@@ -2,7 +2,9 @@
 its own clock with per-photon keyed random numbers.  It is statistically, not sequence-, equivalent to the event-driven loop of
 mcrat.c:761-851, so it is held against the EXACT mode (itself parity-tested against the oracle) through the distribution gates
 BASELINE.md names -- scatterings per photon, the energy spectrum, the Stokes parameters Q and U -- within Monte-Carlo error, and through
-what must hold exactly: the clock, conservation, null slots, determinism."""
+what must hold exactly: the clock, conservation, null slots, determinism.
+Per photon FAST mode IS deterministic: tests/test_gpu_fast_parity.py holds the kernel photon for photon against a CPU restatement of the mode
+(oracle/oracle_fast.c) in every build; the gates here remain as the check against the exact mode."""
 import numpy as np
 import pytest
 

@@ -10,7 +10,7 @@ cp oracle/liboracle.so /tmp/liboracle.keep; cp mcrat_amd/host/libmcrat_hip_host.
 restore() { cp /tmp/liboracle.keep oracle/liboracle.so; cp /tmp/libhost.keep mcrat_amd/host/libmcrat_hip_host.so; touch oracle/liboracle.so mcrat_amd/host/libmcrat_hip_host.so; }
 trap restore EXIT
 gcc -O1 -g -fPIC -std=gnu11 -ffp-contract=off -fsanitize=address,undefined -fno-omit-frame-pointer -shared -o oracle/liboracle.so \
-    oracle/mcrat_oracle.c oracle/oracle_ingest.c oracle/oracle_cyclosynch.c oracle/oracle_rng.c -lm
+    oracle/mcrat_oracle.c oracle/oracle_fast.c oracle/oracle_ingest.c oracle/oracle_cyclosynch.c oracle/oracle_rng.c -lm
 gcc -std=gnu99 -O1 -g -Wall -fPIC -shared -fsanitize=address,undefined -fno-omit-frame-pointer -I include mcrat_amd/host/mcrat_hip_host.c \
     -o mcrat_amd/host/libmcrat_hip_host.so -L mcrat_amd -lmcrat_hip -Wl,-rpath,'$ORIGIN/..'
 touch oracle/liboracle.so mcrat_amd/host/libmcrat_hip_host.so
