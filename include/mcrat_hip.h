@@ -887,6 +887,59 @@ int mcrat_hip_sightline_rays(mcrat_hip_ctx *ctx, const mcrat_hip_ctx *hydro /* o
 int mcrat_hip_sightline_photons(mcrat_hip_ctx *ctx, const mcrat_hip_ctx *hydro, const mcrat_hip_sightline_params *params, mcrat_hip_sightlines *out);
 int mcrat_hip_pool_sightline_photons(mcrat_hip_ctx *pool, const mcrat_hip_ctx *hydro, const mcrat_hip_sightline_params *params, mcrat_hip_sightlines *out);
 
+/* the radiation field on the hydro mesh: per-cell and per-shell photon moments ---
+ * The resident photons located in ONE staged hydro frame and summed where they are, in one pass on the device, without the HDF5 round trip.  A slot
+ * counts when it is part of a list, weight != 0 and its type is neither 'p' nor 'N' (as the mock observations count it).  For a counted photon, in
+ * exactly this order, in IEEE double with correctly rounded division and square root and without contraction:
+ *     r = sqrt((r0*r0 + r1*r1) + r2*r2);   mu = r2 / r
+ *     (a0, a1, a2) = the loop's hydro coordinates of (r0, r1, r2)
+ *     cell = -1 when (a0, a1, a2) fails the loop's strict domain test, else the lowest-index cell whose closed extent holds the point
+ *            cell < 0: n_unlocated += 1, the photon is in no bin
+ *     beta = that cell's velocity at the azimuth of (r0, r1), as a re-location takes it
+ *     e_lab = p0 * C_LIGHT   [erg]
+ *     e_comv = lorentzBoost(beta, p)[0] * C_LIGHT   (mclib.c:302-407 in the loop's form, with the cell's staged Lorentz factor): the photon's energy
+ *              in the local fluid frame
+ *     terms:  w,  w*e_lab,  w*e_comv,  w*num_scatt,  w*temp[cell]
+ * mode MCRAT_HIP_RADFIELD_CELLS:   bin = cell; n_bins = the frame's num_elements.
+ * mode MCRAT_HIP_RADFIELD_SHELLS:  bin = ir * n_mu + imu, where bin k of an axis holds  edges[k] <= x < edges[k + 1]  for x = r and x = mu, decided
+ *                                  by comparisons only; n_bins = n_r * n_mu.  A located photon outside either range adds to n_outside and to no bin.
+ * Per bin six planes of 8 bytes: count (integer), W = sum w, WE_lab, WE_comv, WNS (w * num_scatt), WT (w * the cell's temperature); beside them
+ * n_observable (counted photons), n_unlocated, n_outside: sum(count) + n_unlocated + n_outside == n_observable.  The photon temperature of a bin is
+ * WE_comv / (W k_B xbar) (xbar = 2.701 for a black body, 3 for a Wien spectrum), the matter temperature the photons see WT / W: the caller's
+ * quotients.  Counts are exact: the same as the same expressions in host code.  The five sums are added with floating-point atomics and are NOT
+ * bit-reproducible from run to run; each is within (m + 2) * 2^-53 * sum|term| of the exact sum of its bin's m terms.
+ *   mcrat_hip_radiation_field_bins  n_bins for these arguments -- what the caller's arrays must hold -- after the checks below (it needs the frame,
+ *                                   not photons).
+ *   mcrat_hip_radiation_field       one list: a stand-alone context, or a view of a pool (that list alone).  A pending advance is flushed first.
+ *   mcrat_hip_pool_radiation_field  every list of a pool in one launch; it reads what mcrat_hip_pool_observe reads, a frame selected with
+ *                                   mcrat_hip_pool_select_frame included.
+ *   mcrat_hip_radiation_field_path  how the context's last call accumulated: 1 a copy of the planes per workgroup in LDS, flushed once (SHELLS whose
+ *                                   edges and planes fit); 2 atomics straight into HBM (CELLS always; larger SHELLS); 0 none yet.
+ *                                   MCRAT_HIP_RADFIELD_PATH=lds|global in the environment forces one (lds is refused where it cannot be had).
+ * hydro: the context whose staged frame the photons are located in; NULL: ctx's own.  In a run that is the photons' slab: a caller who wants the whole
+ * outflow stages the whole frame on a second context and passes it.  It must be on the same device with the same DIMENSIONS and GEOMETRY
+ * (TAU_CALCULATION does not matter here).  No photon column changes; nearest_block_index is not touched.
+ * MCRAT_HIP_EINVAL, with its own text in mcrat_hip_last_error, checked in this order: an unknown mode; SHELLS without r_edges or mu_edges; n_r or n_mu
+ * < 1; n_r * n_mu overflowing an int; r_edges, then mu_edges, not finite; r_edges, then mu_edges, not strictly ascending; more edges than the kernel
+ * can stage (about 10 000 values); MCRAT_HIP_RADFIELD_PATH neither lds nor global, lds with CELLS, lds with planes beyond LDS; a hydro context that does
+ * not match.  Then MCRAT_HIP_ESTATE: no staged frame; no photons; the pool call on a context that is no pool and the one-list call on a pool.
+ * Both calls synchronise before they return. */
+#define MCRAT_HIP_RADFIELD_CELLS 0
+#define MCRAT_HIP_RADFIELD_SHELLS 1
+typedef struct mcrat_hip_radfield_bins {      /* inputs, host pointers; CELLS reads mode alone */
+    int mode;
+    int n_r;  const double *r_edges;          /* [n_r + 1] cm */
+    int n_mu; const double *mu_edges;         /* [n_mu + 1] cosines of the polar angle, ascending */
+} mcrat_hip_radfield_bins;
+typedef struct mcrat_hip_radfield {           /* outputs: host pointers, each [n_bins] (SHELLS: r-major then mu), any may be NULL; and three counters */
+    long long *count; double *w, *we_lab, *we_comv, *w_nscatt, *w_temp;
+    long long n_observable, n_unlocated, n_outside;
+} mcrat_hip_radfield;
+int mcrat_hip_radiation_field_bins(mcrat_hip_ctx *ctx, const mcrat_hip_ctx *hydro /* or NULL */, const mcrat_hip_radfield_bins *bins, int *n_bins);
+int mcrat_hip_radiation_field(mcrat_hip_ctx *ctx, const mcrat_hip_ctx *hydro, const mcrat_hip_radfield_bins *bins, mcrat_hip_radfield *out);
+int mcrat_hip_pool_radiation_field(mcrat_hip_ctx *pool, const mcrat_hip_ctx *hydro, const mcrat_hip_radfield_bins *bins, mcrat_hip_radfield *out);
+int mcrat_hip_radiation_field_path(const mcrat_hip_ctx *ctx);
+
 /* introspection used by bench.py / tests -------------------------------------- */
 int mcrat_hip_synchronize(mcrat_hip_ctx *ctx);
 size_t mcrat_hip_device_bytes(const mcrat_hip_ctx *ctx);   /* HBM held by the context */

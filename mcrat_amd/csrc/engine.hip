@@ -20,6 +20,7 @@
 #include "launch.hpp"
 #include "observe_plan.hpp"
 #include "sightline_plan.hpp"
+#include "radfield_plan.hpp"
 #include "photon_cols.hpp"
 #include "photon_plan.hpp"
 #include "rng.hpp"
@@ -168,6 +169,9 @@ struct mcrat_hip_ctx {
     int obs_path = 0;                 // the accumulation path of the last observation (ObservePath)
     void *sl_buf = nullptr;           // mcrat_hip_sightline_*: the output block and the caller's rays (sightline_plan.hpp); a view uses its pool's
     size_t sl_bytes = 0;
+    void *rf_buf = nullptr;           // mcrat_hip_radiation_field: head, accumulator and staged edges (radfield_plan.hpp); a view uses its pool's
+    size_t rf_bytes = 0;
+    int rf_path = 0;                  // the accumulation path of the last radiation field (ObservePath)
 
     // profiling
     std::vector<hipEvent_t> ev;
@@ -423,6 +427,7 @@ extern "C" void mcrat_hip_destroy(mcrat_hip_ctx *c)
     if (c->h_red) (void)hipHostFree(c->h_red);
     if (c->obs_buf) (void)hipFree(c->obs_buf);
     if (c->sl_buf) (void)hipFree(c->sl_buf);
+    if (c->rf_buf) (void)hipFree(c->rf_buf);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -4228,6 +4233,109 @@ extern "C" int mcrat_hip_pool_sightline_photons(mcrat_hip_ctx *c, const mcrat_hi
     if (rc) return rc;
     return sightline_run(c, hydro, params, c->ph.n, nullptr, out);
 }
+
+// ---------------------------------------------------------------------------------------------- the radiation field on the hydro mesh
+// The checks of radfield_plan.hpp on the caller's bins, then the frame: *h is the context whose staged frame the photons are located in, *plan the
+// block for its cells.  EINVAL comes before ESTATE, in the order the header gives.
+static int radfield_prepare(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_radfield_bins *bins, const mcrat_hip_ctx **h_out, RadfieldPlan *plan)
+{
+    RadfieldShape shape;
+    const RadfieldRefusal why = radfield_check(bins->mode, bins->n_r, bins->r_edges, bins->n_mu, bins->mu_edges, getenv("MCRAT_HIP_RADFIELD_PATH"), &shape);
+    if (why != RADFIELD_OK) { c->last_error = radfield_refusal_text(why); return MCRAT_HIP_EINVAL; }
+    const mcrat_hip_ctx *h = hydro ? hydro : c;
+    if (h != c && (h->kc.dimensions != c->kc.dimensions || h->kc.geometry != c->kc.geometry || h->cfg.device != c->cfg.device)) {
+        c->last_error = radfield_refusal_text(RADFIELD_HYDRO_MISMATCH);
+        return MCRAT_HIP_EINVAL;
+    }
+    if (!h->have_hydro || h->hy.M <= 0) { c->last_error = "radiation_field: no staged hydro frame"; return MCRAT_HIP_ESTATE; }
+    *plan = radfield_layout(shape, h->hy.M);
+    *h_out = h;
+    return MCRAT_HIP_OK;
+}
+
+// The n_slots slots of c->ph located in the frame of `hydro` and summed per bin (radfield_plan.hpp, radfield.hip): one memset, one copy of the
+// edges, one launch (a bin-major build: and the transposition), the planes read back.  The device block belongs to the pool when c is a view.
+static int radfield_run(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_radfield_bins *bins, int n_slots, mcrat_hip_radfield *out)
+{
+    c->rf_path = OBSERVE_PATH_NONE;
+    const mcrat_hip_ctx *h = nullptr;
+    RadfieldPlan plan;
+    int rc = radfield_prepare(c, hydro, bins, &h, &plan);
+    if (rc) return rc;
+    if (n_slots <= 0) { c->last_error = "radiation_field: no photons"; return MCRAT_HIP_ESTATE; }
+
+    mcrat_hip_ctx *owner = c->parent ? c->parent : c;
+    HIPCHK(c, hipStreamSynchronize(c->stream));                  // (the block may be replaced: nothing may still read the old one)
+    if (h != c) HIPCHK(c, hipStreamSynchronize(h->stream));      // ... and the other context's frame is staged on its stream
+    if ((rc = ensure_device_bytes(c, &owner->rf_buf, &owner->rf_bytes, plan.total_bytes))) return rc;
+    char *d = static_cast<char *>(owner->rf_buf);
+    RadfieldDev a{};
+    a.n_slots = n_slots; a.n_r = plan.s.n_r; a.n_mu = plan.s.n_mu; a.n_bins = plan.n_bins;
+    a.staged = reinterpret_cast<const double *>(d + plan.staged_offset);
+    a.head = reinterpret_cast<unsigned long long *>(d);
+    a.acc = reinterpret_cast<double *>(d + RADFIELD_ACC_OFFSET);
+    HIPCHK(c, hipMemsetAsync(d, 0, plan.zeroed_bytes, c->stream));
+    std::vector<double> in;
+    if (plan.s.mode == RADFIELD_SHELLS) {
+        in.insert(in.end(), bins->r_edges, bins->r_edges + plan.s.n_r + 1);
+        in.insert(in.end(), bins->mu_edges, bins->mu_edges + plan.s.n_mu + 1);
+        HIPCHK(c, hipMemcpyAsync(d + plan.staged_offset, in.data(), sizeof(double) * in.size(), hipMemcpyHostToDevice, c->stream));
+    }
+    const int cus = device_cus(c);
+    c->prof_step_ms = 0; c->prof_launches = 0;                   // (cfg.profile: the kernel's own duration, mcrat_hip_profile_totals)
+    rc = profiled(c, 1, [&]() -> int {
+        HIPCHK(c, launch_radfield(c->kc, c->ph, h->hy, a, plan, radfield_grid(plan, n_slots, cus), c->stream));
+        if (plan.bin_major) HIPCHK(c, launch_radfield_transpose(a.acc, reinterpret_cast<double *>(d + plan.planes_offset), plan.n_bins, cus, c->stream));
+        return MCRAT_HIP_OK;
+    });
+    if (rc) return rc;
+    const size_t plane = sizeof(double) * (size_t)plan.n_bins;
+    void *planes[RADFIELD_PLANES] = {out->count, out->w, out->we_lab, out->we_comv, out->w_nscatt, out->w_temp};
+    static_assert(sizeof(long long) == 8, "the count plane and the counters are read back as they are");
+    for (int k = 0; k < RADFIELD_PLANES; ++k)
+        if (planes[k]) HIPCHK(c, hipMemcpyAsync(planes[k], d + plan.planes_offset + plane * (size_t)k, plane, hipMemcpyDeviceToHost, c->stream));
+    long long head[RADFIELD_N_SCALARS];
+    HIPCHK(c, hipMemcpyAsync(head, d, sizeof(head), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    out->n_observable = head[RF_N_OBSERVABLE]; out->n_unlocated = head[RF_N_UNLOCATED]; out->n_outside = head[RF_N_OUTSIDE];
+    c->rf_path = plan.s.path;
+    return MCRAT_HIP_OK;
+}
+
+extern "C" int mcrat_hip_radiation_field_bins(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_radfield_bins *bins, int *n_bins)
+{
+    if (!c || !bins || !n_bins) return MCRAT_HIP_EINVAL;
+    const mcrat_hip_ctx *h = nullptr;
+    RadfieldPlan plan;
+    int rc = radfield_prepare(c, hydro, bins, &h, &plan);
+    if (rc) return rc;
+    *n_bins = plan.n_bins;
+    return MCRAT_HIP_OK;
+}
+
+extern "C" int mcrat_hip_radiation_field(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_radfield_bins *bins, mcrat_hip_radfield *out)
+{
+    if (!c || !bins || !out) return MCRAT_HIP_EINVAL;
+    if (c->is_pool) { c->last_error = "radiation_field: one list is a stand-alone context or a view of a pool (mcrat_hip_pool_radiation_field takes the pool)"; return MCRAT_HIP_ESTATE; }
+    if (c->have_photons) {
+        int rc = flush_pending(c);
+        if (rc) return rc;
+    }
+    return radfield_run(c, hydro, bins, c->have_photons ? c->ph.n : 0, out);
+}
+
+extern "C" int mcrat_hip_pool_radiation_field(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_radfield_bins *bins, mcrat_hip_radfield *out)
+{
+    if (!c || !bins || !out) return MCRAT_HIP_EINVAL;
+    if (!c->is_pool) { c->last_error = "pool_radiation_field: the context is no rank pool"; return MCRAT_HIP_ESTATE; }
+    // every slot of the pool, as mcrat_hip_pool_observe reads them (a selected capture included: c->ph is that capture's columns): slots beyond a
+    // list's length and lists never created are not FLAG_VALID
+    int rc = flush_pending(c);
+    if (rc) return rc;
+    return radfield_run(c, hydro, bins, c->ph.n, out);
+}
+
+extern "C" int mcrat_hip_radiation_field_path(const mcrat_hip_ctx *c) { return c ? c->rf_path : 0; }
 
 extern "C" int mcrat_hip_eval_function(mcrat_hip_ctx *c, int fn, int n, const double *in, double *out, uint64_t seed)
 {

@@ -148,6 +148,19 @@ struct SightlineDev {
     int refill, own_rays;                // lane refill, and the rays of a workgroup's own range (sightline_own_rays)
 };
 hipError_t launch_sightline(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, const SightlineDev &a, int blocks, hipStream_t stream);
+// the radiation field on the hydro mesh (radfield.hip): the n_slots slots of ph located in the frame hy and their moments added per cell or per
+// (r, mu) shell.  Head, accumulator and staged edges are laid out as radfield_plan.hpp says; the caller zeroes head and accumulator and sizes the
+// grid (radfield_grid).  A bin-major accumulator is turned into the caller's planes by launch_radfield_transpose.
+struct RadfieldPlan;
+struct RadfieldDev {
+    int n_slots, n_r, n_mu, n_bins;
+    const double *staged;                // r_edges [n_r + 1], mu_edges [n_mu + 1] (SHELLS)
+    unsigned long long *head;            // n_observable, n_unlocated, n_outside
+    double *acc;                         // RADFIELD_PLANES words per bin, plane- or bin-major; word 0 holds a 64-bit integer count
+};
+hipError_t launch_radfield(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, const RadfieldDev &a, const RadfieldPlan &plan, int blocks,
+                           hipStream_t stream);
+hipError_t launch_radfield_transpose(const double *records, double *planes, int n_bins, int cus, hipStream_t stream);
 hipError_t launch_init_states_multi(LoopState *ranks, int n_ranks, const int *open, const double *time_now, const double *remaining, hipStream_t stream);
 hipError_t launch_aos_to_soa(const void *aos, const PhotonDev &ph, int n, hipStream_t stream);
 // many lists of a rank pool at once: desc = `count` device records {int rank, int n, long long first record in aos}; the rest of each window is cleared

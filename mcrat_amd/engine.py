@@ -211,6 +211,22 @@ class Sightlines(C.Structure):
 # a sightline's status (mcrat_hip_sightlines.status)
 SIGHTLINE_SKIPPED, SIGHTLINE_LEFT_MESH, SIGHTLINE_OPAQUE, SIGHTLINE_STEP_CAP, SIGHTLINE_OFF_TABLE = 0, 1, 2, 3, 4
 
+
+class RadfieldBins(C.Structure):
+    """mcrat_hip_radfield_bins: the binning of a radiation field -- the hydro cells, or (r, mu) shells with their edges"""
+    _fields_ = [("mode", C.c_int), ("n_r", C.c_int), ("r_edges", _dp), ("n_mu", C.c_int), ("mu_edges", _dp)]
+
+
+class Radfield(C.Structure):
+    """mcrat_hip_radfield: the six planes, each [n_bins], and the three counters"""
+    _fields_ = [("count", C.POINTER(C.c_longlong)), ("w", _dp), ("we_lab", _dp), ("we_comv", _dp), ("w_nscatt", _dp), ("w_temp", _dp),
+                ("n_observable", C.c_longlong), ("n_unlocated", C.c_longlong), ("n_outside", C.c_longlong)]
+
+
+RADFIELD_CELLS, RADFIELD_SHELLS = 0, 1            # mcrat_hip_radfield_bins.mode
+RADFIELD_PATH_LDS, RADFIELD_PATH_GLOBAL = 1, 2    # mcrat_hip_radiation_field_path
+RADFIELD_PLANES = ("w", "we_lab", "we_comv", "w_nscatt", "w_temp")
+
 SCIENCE, CYLINDRICAL_OUTFLOW, SPHERICAL_OUTFLOW, STRUCTURED_SPHERICAL_OUTFLOW = 0, 1, 2, 3    # SIMULATION_TYPE, mcrat.h:30-33
 
 # every symbol include/mcrat_hip.h declares: (restype, argtypes)
@@ -313,6 +329,10 @@ SYMBOLS = {
     "mcrat_hip_sightline_rays": (C.c_int, [_ctx, _ctx, C.POINTER(SightlineParams), C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(Sightlines)]),
     "mcrat_hip_sightline_photons": (C.c_int, [_ctx, _ctx, C.POINTER(SightlineParams), C.POINTER(Sightlines)]),
     "mcrat_hip_pool_sightline_photons": (C.c_int, [_ctx, _ctx, C.POINTER(SightlineParams), C.POINTER(Sightlines)]),
+    "mcrat_hip_radiation_field_bins": (C.c_int, [_ctx, _ctx, C.POINTER(RadfieldBins), _ip]),
+    "mcrat_hip_radiation_field": (C.c_int, [_ctx, _ctx, C.POINTER(RadfieldBins), C.POINTER(Radfield)]),
+    "mcrat_hip_pool_radiation_field": (C.c_int, [_ctx, _ctx, C.POINTER(RadfieldBins), C.POINTER(Radfield)]),
+    "mcrat_hip_radiation_field_path": (C.c_int, [_ctx]),
     "mcrat_hip_synchronize": (C.c_int, [_ctx]),
     "mcrat_hip_device_bytes": (C.c_size_t, [_ctx]),
     "mcrat_hip_eval_function": (C.c_int, [_ctx, C.c_int, C.c_int, _dp, _dp, C.c_uint64]),
@@ -364,6 +384,30 @@ def observer_angles(theta_obs_deg, dtheta_deg):
     cos_lo = np.where(lo <= 0.0, np.nextafter(1.0, 2.0), np.cos(np.maximum(lo, 0.0)))
     cos_hi = np.where(hi >= np.pi, -np.nextafter(1.0, 2.0), np.cos(np.minimum(hi, np.pi)))
     return np.cos(th), np.sin(th), cos_lo, cos_hi
+
+
+def shell_edges(r_edges, theta_edges_deg):
+    """(r_edges, mu_edges) for Engine.radiation_field(RADFIELD_SHELLS, ...) from radial edges [cm] and polar-angle edges [degrees from the r2 axis,
+    ascending]: mu = cos(theta) ascending, so shell column j holds theta_edges_deg[n - j - 1] >= theta > theta_edges_deg[n - j].  Where the top
+    edge would be 1 (an angle edge of 0) it lies just above 1, as observer_angles closes its cones at the axis: a photon on the axis is counted."""
+    th = np.radians(_f8(theta_edges_deg).ravel())
+    mu = np.cos(th)[::-1].copy()
+    if len(mu) and mu[-1] >= 1.0:
+        mu[-1] = np.nextafter(1.0, 2.0)
+    return _f8(r_edges).ravel().copy(), mu
+
+
+K_B = 1.380658e-16        # erg / K, the reference's value (mclib.c)
+
+
+def photon_temperature(res, spect="b"):
+    """the photon temperature per bin of a radiation field: we_comv / (w * K_B * xbar), xbar = 2.701 for a black body ('b'), 3 for a Wien spectrum
+    ('w'): the mean comoving photon energy over xbar k_B.  NaN where the bin holds no weight."""
+    xbar = {"b": 2.701, "w": 3.0}[spect.decode() if isinstance(spect, bytes) else spect]
+    w, we = _f8(res["w"]), _f8(res["we_comv"])
+    out = np.full(w.shape, np.nan)
+    np.divide(we, w * K_B * xbar, out=out, where=w != 0)
+    return out
 
 
 class Engine:
@@ -1065,6 +1109,38 @@ class Engine:
         n = int(self.lib.mcrat_hip_num_photon_slots(self.ctx))
         return self._sightlines("pool_sightline_photons", n, lambda par, out: self.lib.mcrat_hip_pool_sightline_photons(self.ctx, h, par, out),
                                 step_frac, h_min, max_steps, tau_stop, surface_level)
+
+    # ---- the radiation field on the hydro mesh: per-cell and per-shell photon moments (include/mcrat_hip.h)
+    def _radiation_field(self, call, what, mode, r_edges, mu_edges, hydro):
+        h = hydro.ctx if hydro is not None else None
+        re_ = _f8(r_edges).ravel() if r_edges is not None else None
+        mu = _f8(mu_edges).ravel() if mu_edges is not None else None
+        n_r, n_mu = (len(re_) - 1 if re_ is not None else 0), (len(mu) - 1 if mu is not None else 0)
+        bins = RadfieldBins(int(mode), n_r, re_.ctypes.data_as(_dp) if re_ is not None else None, n_mu, mu.ctypes.data_as(_dp) if mu is not None else None)
+        n_bins = C.c_int(0)
+        self._check(self.lib.mcrat_hip_radiation_field_bins(self.ctx, h, C.byref(bins), C.byref(n_bins)), what)
+        shape = (n_r, n_mu) if int(mode) == RADFIELD_SHELLS else (n_bins.value,)
+        res = {"count": np.zeros(shape, dtype=np.int64)}
+        for k in RADFIELD_PLANES:
+            res[k] = np.zeros(shape)
+        out = Radfield(res["count"].ctypes.data_as(C.POINTER(C.c_longlong)), *[res[k].ctypes.data_as(_dp) for k in RADFIELD_PLANES])
+        self._check(call(self.ctx, h, C.byref(bins), C.byref(out)), what)
+        res.update(n_observable=int(out.n_observable), n_unlocated=int(out.n_unlocated), n_outside=int(out.n_outside))
+        return res
+
+    def radiation_field(self, mode, r_edges=None, mu_edges=None, hydro=None):
+        """this list's photons located in the staged frame (hydro: another Engine's) and summed per hydro cell (RADFIELD_CELLS) or per (r, mu) shell
+        (RADFIELD_SHELLS; shell_edges gives mu_edges from polar angles) -> dict of arrays count, w, we_lab, we_comv, w_nscatt, w_temp -- (M,) for
+        CELLS, (n_r, n_mu) for SHELLS -- and the counters n_observable, n_unlocated, n_outside (mcrat_hip_radiation_field)"""
+        return self._radiation_field(self.lib.mcrat_hip_radiation_field, "radiation_field", mode, r_edges, mu_edges, hydro)
+
+    def pool_radiation_field(self, mode, r_edges=None, mu_edges=None, hydro=None):
+        """every list of the pool in one launch (mcrat_hip_pool_radiation_field)"""
+        return self._radiation_field(self.lib.mcrat_hip_pool_radiation_field, "pool_radiation_field", mode, r_edges, mu_edges, hydro)
+
+    def radiation_field_path(self):
+        """how the last radiation field of this context was accumulated: RADFIELD_PATH_LDS, RADFIELD_PATH_GLOBAL, 0: none yet"""
+        return int(self.lib.mcrat_hip_radiation_field_path(self.ctx))
 
     def synchronize(self):
         self._check(self.lib.mcrat_hip_synchronize(self.ctx), "synchronize")
