@@ -940,6 +940,60 @@ int mcrat_hip_radiation_field(mcrat_hip_ctx *ctx, const mcrat_hip_ctx *hydro, co
 int mcrat_hip_pool_radiation_field(mcrat_hip_ctx *pool, const mcrat_hip_ctx *hydro, const mcrat_hip_radfield_bins *bins, mcrat_hip_radfield *out);
 int mcrat_hip_radiation_field_path(const mcrat_hip_ctx *ctx);
 
+/* sky observers: mock observations from any direction, with images --------------
+ * mcrat_hip_observe assumes an axisymmetric outflow: its observers are polar rings.  Here an observer is a direction anywhere on the sky with an
+ * acceptance cone about it, the detection time comes from r.n, and the photon's position on the observer's sky plane may be two more axes of the
+ * cube: resolved images.  Photons are 3-D Cartesian whatever the run's DIMENSIONS and GEOMETRY.
+ * A slot counts as for mcrat_hip_observe: part of a list, weight != 0, type neither 'p' nor 'N'.  Observer o has a unit vector n = (n0, n1, n2)[o]
+ * towards the observer, an acceptance cosine cos_acc[o] and, with image axes, two unit vectors ex = (x0, x1, x2)[o], ey = (y0, y1, y2)[o] that span
+ * the sky plane.  In exactly this order, in IEEE double with correctly rounded division and without contraction:
+ *     accepted:  ((p1*n0 + p2*n1) + p3*n2) >= p0*cos_acc        (cones may overlap; a photon counts for every observer that accepts it)
+ *     e = p0 * C_LIGHT   [erg]
+ *     t_det = time_now - (((r0*n0 + r1*n1) + r2*n2) / C_LIGHT)   [s]
+ *     X = (r0*x0 + r1*x1) + r2*x2;   Y = (r0*y0 + r1*y1) + r2*y2   [cm]
+ * Bin k of an axis holds  edges[k] <= x < edges[k + 1], decided by comparisons only.  The axes are time (n_t), energy (n_e) and, optionally, X
+ * (n_x) and Y (n_y).  n_x == 0 && n_y == 0: no image axes -- X and Y are not computed and x0 .. y2, x_edges, y_edges may be NULL.  An accepted
+ * photon outside any axis, or with a coordinate that is not a number, is in no bin and adds to n_outside[o].
+ * The cube: seven planes per bin as mcrat_hip_observe has them -- count (integer), W = sum w, WE = sum w*e, I, Q, U, V = sum w*s0 .. s3 (zero with
+ * stokes_switch off) -- each [n_obs][n_t][n_e][n_y][n_x] with x fastest ([n_obs][n_t][n_e] without image axes); beside it n_accepted[n_obs] and
+ * n_outside[n_obs].  Every output pointer may be NULL.
+ * The Stokes frame: Q and U are summed as the photons store them, as mcrat_hip_observe does.  MCRaT defines a photon's Stokes frame from its own
+ * direction and the polar axis (mcrat_scattering.c, findXY); for photons inside a narrow cone about n those frames coincide to first order in the
+ * cone's half-angle, at any azimuth phi.  The natural sky axes of an observer at (theta, phi) are ey = phi_hat = (-sin phi, cos phi, 0) and
+ * ex = theta_hat = (cos theta cos phi, cos theta sin phi, -sin theta), so that ex x ey = n.
+ * Counts are exact: the same as the same expressions in host code.  The sums are added with floating-point atomics and are NOT bit-reproducible
+ * from run to run; each is within (m + 2) * 2^-53 * sum|term| of the exact sum of its bin's m terms.
+ * MCRAT_HIP_EINVAL, each with its own text in mcrat_hip_last_error, checked in this order: n_obs, n_t or n_e < 1; n_x and n_y neither both 0 nor
+ * both >= 1; the product of the five counts overflowing an int; a direction that is not finite; a direction that is not unit,
+ * |((n0*n0 + n1*n1) + n2*n2) - 1| > 1e-12; cos_acc not finite or outside [-1, 1]; with image axes: the sky-plane vectors NULL, not finite, not
+ * unit, or any of |ex.n|, |ey.n|, |ex.ey| above 1e-12; t_edges not finite, then not strictly ascending, the same for e_edges, x_edges, y_edges; more
+ * edges and observers than the kernel can stage (about 9 000 values together); MCRAT_HIP_SKY_PATH neither lds nor global; lds forced for a cube
+ * that does not fit.  (1e-12 is a condition on the inputs: vectors built from cos and sin in double miss it by three orders of magnitude.)
+ *   mcrat_hip_observe_sky        one list: a stand-alone context, or a view of a pool (that list alone); time_now is the list's clock.  A pending
+ *                                advance is flushed first.  MCRAT_HIP_ESTATE without photons, and on a pool.
+ *   mcrat_hip_pool_observe_sky   every list of a pool in one launch, each with its own clock time_now[r]; it reads exactly what
+ *                                mcrat_hip_pool_observe reads, and like it flushes nothing a view holds pending.  MCRAT_HIP_ESTATE on a context
+ *                                that is no pool.
+ *   mcrat_hip_observe_sky_path   how the context's last sky observation was accumulated: 1 a copy of the cube per workgroup in LDS, flushed once
+ *                                (light curves, small images); 2 atomics straight into the cube in HBM (images); 0 none yet.
+ *                                MCRAT_HIP_SKY_PATH=lds|global in the environment forces one.
+ * Both calls synchronise before they return.  No photon column changes. */
+typedef struct mcrat_hip_sky_observer {  /* inputs, host pointers */
+    int n_obs; const double *n0, *n1, *n2, *cos_acc;               /* [n_obs] */
+    const double *x0, *x1, *x2, *y0, *y1, *y2;                     /* [n_obs]: ex and ey; read with image axes only */
+    int n_t;   const double *t_edges;                              /* [n_t + 1] seconds */
+    int n_e;   const double *e_edges;                              /* [n_e + 1] erg */
+    int n_x;   const double *x_edges;                              /* [n_x + 1] cm; n_x == n_y == 0: no image axes */
+    int n_y;   const double *y_edges;                              /* [n_y + 1] cm */
+} mcrat_hip_sky_observer;
+typedef struct mcrat_hip_sky_observation {   /* outputs, host pointers, each [n_obs * n_t * n_e * max(n_y, 1) * max(n_x, 1)]; any may be NULL */
+    long long *count; double *w, *we, *i, *q, *u, *v;
+    long long *n_accepted, *n_outside;   /* [n_obs] */
+} mcrat_hip_sky_observation;
+int mcrat_hip_observe_sky(mcrat_hip_ctx *ctx, const mcrat_hip_sky_observer *obs, double time_now, mcrat_hip_sky_observation *out);
+int mcrat_hip_pool_observe_sky(mcrat_hip_ctx *pool, const mcrat_hip_sky_observer *obs, const double *time_now /* [n_ranks] */, mcrat_hip_sky_observation *out);
+int mcrat_hip_observe_sky_path(const mcrat_hip_ctx *ctx);
+
 /* introspection used by bench.py / tests -------------------------------------- */
 int mcrat_hip_synchronize(mcrat_hip_ctx *ctx);
 size_t mcrat_hip_device_bytes(const mcrat_hip_ctx *ctx);   /* HBM held by the context */

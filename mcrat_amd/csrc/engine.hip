@@ -19,6 +19,7 @@
 #include "device_types.hpp"
 #include "launch.hpp"
 #include "observe_plan.hpp"
+#include "sky_plan.hpp"
 #include "sightline_plan.hpp"
 #include "radfield_plan.hpp"
 #include "photon_cols.hpp"
@@ -172,6 +173,9 @@ struct mcrat_hip_ctx {
     void *rf_buf = nullptr;           // mcrat_hip_radiation_field: head, accumulator and staged edges (radfield_plan.hpp); a view uses its pool's
     size_t rf_bytes = 0;
     int rf_path = 0;                  // the accumulation path of the last radiation field (ObservePath)
+    void *sky_buf = nullptr;          // mcrat_hip_observe_sky: the cube, the per-observer counters and the staged inputs (sky_plan.hpp); a view uses its pool's
+    size_t sky_bytes = 0;
+    int sky_path = 0;                 // the accumulation path of the last sky observation (ObservePath)
 
     // profiling
     std::vector<hipEvent_t> ev;
@@ -428,6 +432,7 @@ extern "C" void mcrat_hip_destroy(mcrat_hip_ctx *c)
     if (c->obs_buf) (void)hipFree(c->obs_buf);
     if (c->sl_buf) (void)hipFree(c->sl_buf);
     if (c->rf_buf) (void)hipFree(c->rf_buf);
+    if (c->sky_buf) (void)hipFree(c->sky_buf);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -4139,6 +4144,109 @@ extern "C" int mcrat_hip_pool_observe(mcrat_hip_ctx *c, const mcrat_hip_observer
 }
 
 extern "C" int mcrat_hip_observe_path(const mcrat_hip_ctx *c) { return c ? c->obs_path : 0; }
+
+// ---------------------------------------------------------------------------------------------- sky observers: any direction, with images
+// The caller's struct as sky_plan.hpp's checks read it, after the pointers no check may do without.
+static int sky_args(mcrat_hip_ctx *c, const mcrat_hip_sky_observer *obs, SkyArgs *args)
+{
+    if (!obs->n0 || !obs->n1 || !obs->n2 || !obs->cos_acc || !obs->t_edges || !obs->e_edges || (obs->n_x > 0 && !obs->x_edges) || (obs->n_y > 0 && !obs->y_edges)) {
+        c->last_error = "observe_sky: a null array in mcrat_hip_sky_observer";
+        return MCRAT_HIP_EINVAL;
+    }
+    *args = SkyArgs{obs->n_obs, obs->n0, obs->n1, obs->n2, obs->cos_acc, obs->x0, obs->x1, obs->x2, obs->y0, obs->y1, obs->y2,
+                    obs->n_t, obs->t_edges, obs->n_e, obs->e_edges, obs->n_x, obs->x_edges, obs->n_y, obs->y_edges};
+    return MCRAT_HIP_OK;
+}
+
+// The kernel's inputs in the order it stages them (sky_plan.hpp), the lists' clocks behind them.
+static std::vector<double> sky_staged_inputs(const SkyArgs &s, const SkyPlan &plan, const double *clocks, int n_clocks)
+{
+    std::vector<double> in;
+    in.reserve(plan.staged_doubles + (size_t)n_clocks);
+    const size_t n_obs = (size_t)plan.n_obs;
+    for (const double *v : {s.n0, s.n1, s.n2, s.cos_acc}) in.insert(in.end(), v, v + n_obs);
+    if (plan.image)
+        for (const double *v : {s.x0, s.x1, s.x2, s.y0, s.y1, s.y2}) in.insert(in.end(), v, v + n_obs);
+    in.insert(in.end(), s.t_edges, s.t_edges + plan.n_t + 1);
+    in.insert(in.end(), s.e_edges, s.e_edges + plan.n_e + 1);
+    if (plan.image) {
+        in.insert(in.end(), s.x_edges, s.x_edges + plan.n_x + 1);
+        in.insert(in.end(), s.y_edges, s.y_edges + plan.n_y + 1);
+    }
+    if (clocks) in.insert(in.end(), clocks, clocks + n_clocks);
+    return in;
+}
+
+// The cube's planes and the per-observer counters from the device block to wherever the caller wants them.
+static int sky_read_back(mcrat_hip_ctx *c, const SkyPlan &plan, const char *d, mcrat_hip_sky_observation *out)
+{
+    const size_t plane = sizeof(double) * (size_t)plan.n_bins, counters = sizeof(long long) * (size_t)plan.n_obs;
+    void *planes[OBSERVE_PLANES] = {out->count, out->w, out->we, out->i, out->q, out->u, out->v};
+    static_assert(sizeof(long long) == 8, "the count plane and the counters are read back as they are");
+    for (int k = 0; k < OBSERVE_PLANES; ++k)
+        if (planes[k]) HIPCHK(c, hipMemcpyAsync(planes[k], d + plane * (size_t)k, plane, hipMemcpyDeviceToHost, c->stream));
+    if (out->n_accepted) HIPCHK(c, hipMemcpyAsync(out->n_accepted, d + plan.cube_bytes, counters, hipMemcpyDeviceToHost, c->stream));
+    if (out->n_outside) HIPCHK(c, hipMemcpyAsync(out->n_outside, d + plan.cube_bytes + counters, counters, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MCRAT_HIP_OK;
+}
+
+// The photons of c->ph -- n_slots of them -- binned by observer, detection time, energy and sky-plane position (sky_plan.hpp, sky.hip): one memset,
+// one copy of the inputs, one launch, the cube read back.  clocks: one per slots_per_clock slots (a rank pool's lists), or nullptr and time_now for
+// all.  The device block belongs to the pool when c is a view.
+static int sky_run(mcrat_hip_ctx *c, const mcrat_hip_sky_observer *obs, int n_slots, const double *clocks, int n_clocks, int slots_per_clock, double time_now,
+                   mcrat_hip_sky_observation *out)
+{
+    c->sky_path = OBSERVE_PATH_NONE;
+    SkyArgs args;
+    int rc = sky_args(c, obs, &args);
+    if (rc) return rc;
+    SkyPlan plan;
+    const SkyRefusal why = sky_plan(args, getenv("MCRAT_HIP_SKY_PATH"), &plan);
+    if (why != SKY_OK) { c->last_error = sky_refusal_text(why); return MCRAT_HIP_EINVAL; }
+    const std::vector<double> in = sky_staged_inputs(args, plan, clocks, n_clocks);
+
+    mcrat_hip_ctx *owner = c->parent ? c->parent : c;
+    HIPCHK(c, hipStreamSynchronize(c->stream));                  // (the block may be replaced: nothing may still read the old one)
+    if ((rc = ensure_device_bytes(c, &owner->sky_buf, &owner->sky_bytes, plan.out_bytes + sizeof(double) * in.size()))) return rc;
+    char *d = static_cast<char *>(owner->sky_buf);
+    double *d_in = reinterpret_cast<double *>(d + plan.out_bytes);
+    SkyDev a{};
+    a.n_slots = n_slots; a.n_obs = plan.n_obs; a.n_t = plan.n_t; a.n_e = plan.n_e; a.n_x = plan.n_x; a.n_y = plan.n_y; a.n_bins = plan.n_bins;
+    a.staged = d_in;
+    a.clocks = clocks ? d_in + plan.staged_doubles : nullptr;
+    a.slots_per_clock = slots_per_clock;
+    a.time_now = time_now;
+    a.cube = reinterpret_cast<double *>(d);
+    a.n_accepted = reinterpret_cast<unsigned long long *>(d + plan.cube_bytes);
+    a.n_outside = a.n_accepted + plan.n_obs;
+    HIPCHK(c, hipMemsetAsync(d, 0, plan.out_bytes, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_in, in.data(), sizeof(double) * in.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_sky(c->ph, a, plan, c->kc.stokes != 0, sky_grid(plan, n_slots, device_cus(c)), c->stream));
+    if ((rc = sky_read_back(c, plan, d, out))) return rc;
+    c->sky_path = plan.path;
+    return MCRAT_HIP_OK;
+}
+
+extern "C" int mcrat_hip_observe_sky(mcrat_hip_ctx *c, const mcrat_hip_sky_observer *obs, double time_now, mcrat_hip_sky_observation *out)
+{
+    if (!c || !obs || !out) return MCRAT_HIP_EINVAL;
+    if (!c->have_photons) return MCRAT_HIP_ESTATE;
+    if (c->is_pool) { c->last_error = "observe_sky: a rank pool's lists have clocks of their own (mcrat_hip_pool_observe_sky, or mcrat_hip_observe_sky on a view)"; return MCRAT_HIP_ESTATE; }
+    int rc = flush_pending(c);
+    if (rc) return rc;
+    return sky_run(c, obs, c->ph.n, nullptr, 0, 1, time_now, out);
+}
+
+extern "C" int mcrat_hip_pool_observe_sky(mcrat_hip_ctx *c, const mcrat_hip_sky_observer *obs, const double *time_now, mcrat_hip_sky_observation *out)
+{
+    if (!c || !obs || !time_now || !out) return MCRAT_HIP_EINVAL;
+    if (!c->is_pool) { c->last_error = "pool_observe_sky: the context is no rank pool"; return MCRAT_HIP_ESTATE; }
+    // every slot of the pool, exactly as mcrat_hip_pool_observe reads them, and like it without flush_pending
+    return sky_run(c, obs, c->ph.n, time_now, c->n_ranks, c->rank_stride, 0.0, out);
+}
+
+extern "C" int mcrat_hip_observe_sky_path(const mcrat_hip_ctx *c) { return c ? c->sky_path : 0; }
 
 // ---------------------------------------------------------------------------------------------- line-of-sight optical depths
 // n rays marched through a staged frame (sightline_plan.hpp, sightline.hip) and the per-ray results read back.  rays: the caller's seven host

@@ -161,6 +161,20 @@ struct RadfieldDev {
 hipError_t launch_radfield(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, const RadfieldDev &a, const RadfieldPlan &plan, int blocks,
                            hipStream_t stream);
 hipError_t launch_radfield_transpose(const double *records, double *planes, int n_bins, int cus, hipStream_t stream);
+// mock observations from any direction on the sky, with images (sky.hip): the photons binned by observer, detection time, energy and, with image
+// axes (n_x, n_y >= 1; else both 0), sky-plane position in one pass over n_slots slots.  The cube and the staged inputs are laid out as sky_plan.hpp
+// says; clocks as in ObserveDev.  The caller zeroes the cube and the counters and sizes the grid (sky_grid).
+struct SkyPlan;
+struct SkyDev {
+    int n_slots, n_obs, n_t, n_e, n_x, n_y, n_bins;
+    const double *staged;                // n0, n1, n2, cos_acc [n_obs each]; (image) x0 .. x2, y0 .. y2 [n_obs each]; t_edges, e_edges; (image) x_edges, y_edges
+    const double *clocks;
+    int slots_per_clock;
+    double time_now;
+    double *cube;                        // OBSERVE_PLANES planes of n_bins; plane 0 holds 64-bit integer counts
+    unsigned long long *n_accepted, *n_outside;   // [n_obs]
+};
+hipError_t launch_sky(const PhotonDev &ph, const SkyDev &a, const SkyPlan &plan, bool stokes, int blocks, hipStream_t stream);
 hipError_t launch_init_states_multi(LoopState *ranks, int n_ranks, const int *open, const double *time_now, const double *remaining, hipStream_t stream);
 hipError_t launch_aos_to_soa(const void *aos, const PhotonDev &ph, int n, hipStream_t stream);
 // many lists of a rank pool at once: desc = `count` device records {int rank, int n, long long first record in aos}; the rest of each window is cleared

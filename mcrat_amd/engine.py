@@ -197,6 +197,23 @@ class Observation(C.Structure):
 OBSERVE_PATH_LDS, OBSERVE_PATH_GLOBAL = 1, 2      # mcrat_hip_observe_path
 
 
+class SkyObserver(C.Structure):
+    """mcrat_hip_sky_observer: the observers' directions, cones and sky-plane vectors and the bin edges of a sky observation"""
+    _fields_ = [("n_obs", C.c_int), ("n0", _dp), ("n1", _dp), ("n2", _dp), ("cos_acc", _dp),
+                ("x0", _dp), ("x1", _dp), ("x2", _dp), ("y0", _dp), ("y1", _dp), ("y2", _dp),
+                ("n_t", C.c_int), ("t_edges", _dp), ("n_e", C.c_int), ("e_edges", _dp),
+                ("n_x", C.c_int), ("x_edges", _dp), ("n_y", C.c_int), ("y_edges", _dp)]
+
+
+class SkyObservation(C.Structure):
+    """mcrat_hip_sky_observation: the cube's planes, each [n_obs * n_t * n_e * n_y * n_x], and the per-observer counters"""
+    _fields_ = [("count", C.POINTER(C.c_longlong)), ("w", _dp), ("we", _dp), ("i", _dp), ("q", _dp), ("u", _dp), ("v", _dp),
+                ("n_accepted", C.POINTER(C.c_longlong)), ("n_outside", C.POINTER(C.c_longlong))]
+
+
+SKY_PATH_LDS, SKY_PATH_GLOBAL = 1, 2              # mcrat_hip_observe_sky_path
+
+
 class SightlineParams(C.Structure):
     """mcrat_hip_sightline_params: how a sightline is stepped and where it stops"""
     _fields_ = [("step_frac", C.c_double), ("h_min", C.c_double), ("max_steps", C.c_int), ("tau_stop", C.c_double), ("surface_level", C.c_double)]
@@ -333,6 +350,9 @@ SYMBOLS = {
     "mcrat_hip_radiation_field": (C.c_int, [_ctx, _ctx, C.POINTER(RadfieldBins), C.POINTER(Radfield)]),
     "mcrat_hip_pool_radiation_field": (C.c_int, [_ctx, _ctx, C.POINTER(RadfieldBins), C.POINTER(Radfield)]),
     "mcrat_hip_radiation_field_path": (C.c_int, [_ctx]),
+    "mcrat_hip_observe_sky": (C.c_int, [_ctx, C.POINTER(SkyObserver), C.c_double, C.POINTER(SkyObservation)]),
+    "mcrat_hip_pool_observe_sky": (C.c_int, [_ctx, C.POINTER(SkyObserver), _dp, C.POINTER(SkyObservation)]),
+    "mcrat_hip_observe_sky_path": (C.c_int, [_ctx]),
     "mcrat_hip_synchronize": (C.c_int, [_ctx]),
     "mcrat_hip_device_bytes": (C.c_size_t, [_ctx]),
     "mcrat_hip_eval_function": (C.c_int, [_ctx, C.c_int, C.c_int, _dp, _dp, C.c_uint64]),
@@ -384,6 +404,19 @@ def observer_angles(theta_obs_deg, dtheta_deg):
     cos_lo = np.where(lo <= 0.0, np.nextafter(1.0, 2.0), np.cos(np.maximum(lo, 0.0)))
     cos_hi = np.where(hi >= np.pi, -np.nextafter(1.0, 2.0), np.cos(np.minimum(hi, np.pi)))
     return np.cos(th), np.sin(th), cos_lo, cos_hi
+
+
+def sky_observers(theta, phi, half_angle):
+    """observers at polar angle theta and azimuth phi [radians], each accepting photons whose direction lies within half_angle [radians] of the
+    direction towards it  ->  (n, cos_acc, ex, ey) for Engine.observe_sky: n, ex, ey are (3, n_obs) and cos_acc (n_obs,), with
+    n = (sin theta cos phi, sin theta sin phi, cos theta), ex = theta_hat = (cos theta cos phi, cos theta sin phi, -sin theta),
+    ey = phi_hat = (-sin phi, cos phi, 0): ex x ey = n, and for an observer on the r2 axis at phi = 0 ex and ey are the r0 and r1 axes."""
+    th, ph, half = np.broadcast_arrays(np.atleast_1d(_f8(theta)), np.atleast_1d(_f8(phi)), np.atleast_1d(_f8(half_angle)))
+    ct, st, cp, sp = np.cos(th), np.sin(th), np.cos(ph), np.sin(ph)
+    n = np.stack([st * cp, st * sp, ct])
+    ex = np.stack([ct * cp, ct * sp, -st])
+    ey = np.stack([-sp, cp, np.zeros_like(sp)])
+    return n, np.cos(half), ex, ey
 
 
 def shell_edges(r_edges, theta_edges_deg):
@@ -1069,6 +1102,61 @@ class Engine:
     def observe_path(self):
         """how the last observation of this context was accumulated: OBSERVE_PATH_LDS, OBSERVE_PATH_GLOBAL, 0: none yet"""
         return int(self.lib.mcrat_hip_observe_path(self.ctx))
+
+    # ---- sky observers: mock observations from any direction, with images (include/mcrat_hip.h)
+    def _observe_sky(self, call, what, n, cos_acc, t_edges, e_edges, time_now, ex, ey, x_edges, y_edges):
+        def vec(a, name):
+            a = _f8(a)
+            if a.ndim == 1 and a.shape[0] == 3:
+                a = a.reshape(3, 1)
+            if a.ndim != 2 or a.shape[0] != 3:
+                raise ValueError("%s: %s must be three components per observer, shape (3, n_obs)" % (what, name))
+            return np.ascontiguousarray(a)
+        nv, ca, te, ee = vec(n, "n"), _f8(cos_acc).ravel(), _f8(t_edges).ravel(), _f8(e_edges).ravel()
+        n_obs, n_t, n_e = nv.shape[1], len(te) - 1, len(ee) - 1
+        if len(ca) != n_obs:
+            raise ValueError("%s: cos_acc must have one entry per observer" % what)
+        if (x_edges is None) != (y_edges is None):
+            raise ValueError("%s: x_edges and y_edges come together" % what)
+        image = x_edges is not None
+        xe, ye = (_f8(x_edges).ravel(), _f8(y_edges).ravel()) if image else (None, None)
+        n_x, n_y = (len(xe) - 1, len(ye) - 1) if image else (0, 0)
+        xv, yv = (vec(ex, "ex") if ex is not None else None), (vec(ey, "ey") if ey is not None else None)
+        for a, name in ((xv, "ex"), (yv, "ey")):
+            if a is not None and a.shape[1] != n_obs:
+                raise ValueError("%s: %s must have one vector per observer" % (what, name))
+        ptr = lambda a: a.ctypes.data_as(_dp) if a is not None else None
+        row = lambda a, k: ptr(a[k]) if a is not None else None
+        obs = SkyObserver(n_obs, row(nv, 0), row(nv, 1), row(nv, 2), ptr(ca), row(xv, 0), row(xv, 1), row(xv, 2), row(yv, 0), row(yv, 1), row(yv, 2),
+                          n_t, ptr(te), n_e, ptr(ee), n_x, ptr(xe), n_y, ptr(ye))
+        shape = tuple(max(m, 0) for m in ((n_obs, n_t, n_e, n_y, n_x) if image else (n_obs, n_t, n_e)))
+        res = {"count": np.zeros(shape, dtype=np.int64), "n_accepted": np.zeros(shape[0], dtype=np.int64), "n_outside": np.zeros(shape[0], dtype=np.int64)}
+        for k in ("w", "we", "i", "q", "u", "v"):
+            res[k] = np.zeros(shape)
+        ll = C.POINTER(C.c_longlong)
+        out = SkyObservation(res["count"].ctypes.data_as(ll), *[res[k].ctypes.data_as(_dp) for k in ("w", "we", "i", "q", "u", "v")],
+                             res["n_accepted"].ctypes.data_as(ll), res["n_outside"].ctypes.data_as(ll))
+        self._check(call(self.ctx, C.byref(obs), time_now, C.byref(out)), what)
+        return res
+
+    def observe_sky(self, n, cos_acc, t_edges, e_edges, time_now, ex=None, ey=None, x_edges=None, y_edges=None):
+        """this list's photons as observers anywhere on the sky see them at the list's clock time_now (mcrat_hip_observe_sky; sky_observers gives
+        n, cos_acc, ex, ey from angles).  n, ex, ey: (3, n_obs).  Without x_edges and y_edges -> dict of (n_obs, n_t, n_e) arrays count, w, we, i,
+        q, u, v and the per-observer n_accepted, n_outside; with them the arrays are images, (n_obs, n_t, n_e, n_y, n_x) over the sky-plane
+        coordinates X = r.ex, Y = r.ey [cm]."""
+        return self._observe_sky(self.lib.mcrat_hip_observe_sky, "observe_sky", n, cos_acc, t_edges, e_edges, float(time_now), ex, ey, x_edges, y_edges)
+
+    def pool_observe_sky(self, n, cos_acc, t_edges, e_edges, time_now, ex=None, ey=None, x_edges=None, y_edges=None):
+        """every list of the pool in one launch, list r at its own clock time_now[r] (mcrat_hip_pool_observe_sky)"""
+        tn = _f8(time_now).ravel()
+        if len(tn) != self.n_pool_ranks:
+            raise ValueError("pool_observe_sky: time_now needs one clock per rank of the pool")
+        return self._observe_sky(self.lib.mcrat_hip_pool_observe_sky, "pool_observe_sky", n, cos_acc, t_edges, e_edges, tn.ctypes.data_as(_dp), ex, ey,
+                                 x_edges, y_edges)
+
+    def observe_sky_path(self):
+        """how the last sky observation of this context was accumulated: SKY_PATH_LDS, SKY_PATH_GLOBAL, 0: none yet"""
+        return int(self.lib.mcrat_hip_observe_sky_path(self.ctx))
 
     # ---- line-of-sight optical depths and photospheres (include/mcrat_hip.h)
     def _sightlines(self, what, n, call, step_frac, h_min, max_steps, tau_stop, surface_level):
