@@ -73,7 +73,8 @@ def test_absorption_matches_the_oracle(hip, oracle, b_field_calc, dims):
         assert np.array_equal(got[f], want[f], equal_nan=got[f].dtype.kind == "f"), f
 
 
-def _oracle_pool(oracle, frame, cfg, aos, null_slots, dens, b_field_calc, seed, maximum_photons, frames=(200, 200), B=(None, None, None), ph_weight=1e40):
+def _oracle_pool(oracle, frame, cfg, aos, null_slots, dens, b_field_calc, seed, maximum_photons, frames=(200, 200), B=(None, None, None), ph_weight=1e40,
+                 r_inj=1e12, theta_min=0.0, theta_max=0.05):
     """-> (photons emitted, weight, fallback flag, the list before the emission, the list after it)"""
     L = oracle.lib()
     c = oracle.make_config(cfg["dimensions"], cfg["geometry"], cfg["stokes"])
@@ -91,7 +92,7 @@ def _oracle_pool(oracle, frame, cfg, aos, null_slots, dens, b_field_calc, seed, 
     rng = oracle.Rng()
     L.orc_rng_init(C.byref(rng), seed, 0)
     w, fb = C.c_double(), C.c_int()
-    n = L.orc_photonEmitCyclosynch(C.byref(c), C.byref(cs), C.byref(l), 1e12, ph_weight, maximum_photons, 0.0, 0.05, C.byref(H.c), C.byref(rng), 0, 0,
+    n = L.orc_photonEmitCyclosynch(C.byref(c), C.byref(cs), C.byref(l), r_inj, ph_weight, maximum_photons, theta_min, theta_max, C.byref(H.c), C.byref(rng), 0, 0,
                                    C.byref(w), C.byref(fb))
     buf = (C.c_char * (l.list_capacity * oracle.PHOTON_DTYPE.itemsize)).from_address(l.photons)
     out = np.frombuffer(buf, dtype=oracle.PHOTON_DTYPE).copy()

@@ -3,7 +3,8 @@
 The loop kernel is a template over DIMENSIONS x GEOMETRY x STOKES x TAU_CALCULATION (the reference's compile-time tuple, Src/mcrat.h:262-427) and over
 how a list is run: threads per list (128 / 256 / 512), the list's hot columns in LDS or in HBM/L2 (RESIDENT), the fused pass (FUSE: DIRECT optical
 depths, not in spherical geometry, 256 or 512 threads), and -- with the cyclo-synchrotron switch -- the hook of mcrat.c:786-808 inside the loop (CSH;
-64 / 128 / 256 threads, covered by tests/test_gpu_pool_cyclosynch.py's block sweep).  Several of these builds spill registers (up to 300 B of scratch per
+64 / 128 / 256 threads: all nine (DIMENSIONS, GEOMETRY) pairs x STOKES x the three thread counts in tests/test_gpu_birth_geometries.py,
+test_every_hook_build_of_the_loop_kernel_equals_the_oracle; rebinning lists in tests/test_gpu_pool_cyclosynch.py's block sweep).  Several of these builds spill registers (up to 300 B of scratch per
 lane, profiles/r04_kernel_resources.txt), and round 3 met one that wrote a wrong Stokes V after an edit elsewhere: a hand-picked sample of instantiations
 is not enough.  Here every (physics tuple) gets ONE oracle trajectory per list (three ragged lists, ~40 passes, < 0.2 s of oracle each) and every launch
 form the engine's switches can select (MCRAT_HIP_RANK_BLOCK, MCRAT_HIP_RANK_FUSE, MCRAT_HIP_NO_LDS_LISTS) must reproduce it: integers exact, doubles

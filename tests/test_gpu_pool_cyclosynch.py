@@ -23,9 +23,9 @@ def hip():
     return engine
 
 
-def _oracle_frame(oracle, cfg, frame, dens, B, before, seed, stream, remaining, max_photons, theta_max, emit_pool, b_field_calc, ang_phi):
+def _oracle_frame(oracle, cfg, frame, dens, B, before, seed, stream, remaining, max_photons, theta_max, emit_pool, b_field_calc, ang_phi, r_inj=1e12, stokes=1):
     L = oracle.lib()
-    c = oracle.make_config(cfg["dimensions"], cfg["geometry"], 1)
+    c = oracle.make_config(cfg["dimensions"], cfg["geometry"], stokes)
     H = oracle.OracleHydro(frame)
     ptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_double)) if a is not None else None
     cs = oracle.CS(b_field_calc, 0.5, 0.1, ptr(dens), ptr(B[0]), ptr(B[1]), ptr(B[2]), 200, 200, 0.5, ang_phi)
@@ -42,7 +42,7 @@ def _oracle_frame(oracle, cfg, frame, dens, B, before, seed, stream, remaining, 
     rng = oracle.Rng()
     L.orc_rng_init(C.byref(rng), seed, stream)
     st, cnt, t = oracle.Stats(), oracle.CSCounts(), C.c_double(0.0)
-    L.orc_scatter_frame_cs(C.byref(c), C.byref(cs), C.byref(l), C.byref(H.c), C.byref(rng), C.byref(t), remaining, 1e12, 1e40, max_photons, 0.0, theta_max,
+    L.orc_scatter_frame_cs(C.byref(c), C.byref(cs), C.byref(l), C.byref(H.c), C.byref(rng), C.byref(t), remaining, r_inj, 1e40, max_photons, 0.0, theta_max,
                            emit_pool, 0, C.byref(st), C.byref(cnt))
     assert cnt.error == 0
     buf = (C.c_char * (l.list_capacity * oracle.PHOTON_DTYPE.itemsize)).from_address(l.photons)
