@@ -996,7 +996,10 @@ int mcrat_hip_observe_sky_path(const mcrat_hip_ctx *ctx);
 
 /* introspection used by bench.py / tests -------------------------------------- */
 int mcrat_hip_synchronize(mcrat_hip_ctx *ctx);
-size_t mcrat_hip_device_bytes(const mcrat_hip_ctx *ctx);   /* HBM held by the context */
+/* HBM held by the context: photons, staged frame, cell-lookup grid, loop state and the device blocks of all four analysis products -- observe,
+ * observe_sky, sightline_* and radiation_field (the blocks of radiation_field and of observe_sky were left out before the four became one
+ * array).  A view holds no analysis block of its own: it uses its pool's, and they count there. */
+size_t mcrat_hip_device_bytes(const mcrat_hip_ctx *ctx);
 int mcrat_hip_lookup_cell(mcrat_hip_ctx *ctx, int n, const double *a0, const double *a1, const double *a2, int *cell_out); /* device cell search == findContainingBlock geometry.c:350 */
 /* The staged frame's covered-octant table (one int per lookup bucket and octant, bucket-major: the cell that covers the octant, or -1): returns its
  * number of entries -- 0: the frame's grid has none (a log-mapped axis, above the size cap, MCRAT_HIP_NO_COVERED), negative: an MCRAT_HIP_E* code --

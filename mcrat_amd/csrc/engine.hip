@@ -165,16 +165,13 @@ struct mcrat_hip_ctx {
     ReducePartial *d_red = nullptr;
     ReducePartial *h_red = nullptr;   // pinned
     static constexpr int RED_BLOCKS = 512;
-    void *obs_buf = nullptr;          // mcrat_hip_observe: the cube, the per-observer counters and the staged inputs (observe_plan.hpp); a view uses its pool's
-    size_t obs_bytes = 0;
+    // the device blocks of the analysis products, each laid out by its plan header: mcrat_hip_observe (the cube, the per-observer counters and the
+    // staged inputs), mcrat_hip_sightline_* (the output block and the caller's rays), mcrat_hip_radiation_field (head, accumulator and staged
+    // edges), mcrat_hip_observe_sky (as observe).  A view uses its pool's (analysis_block).
+    enum AnalysisBlock { BLOCK_OBSERVE = 0, BLOCK_SIGHTLINE, BLOCK_RADFIELD, BLOCK_SKY, N_ANALYSIS_BLOCKS };
+    struct DeviceBlock { void *buf = nullptr; size_t bytes = 0; } analysis[N_ANALYSIS_BLOCKS];
     int obs_path = 0;                 // the accumulation path of the last observation (ObservePath)
-    void *sl_buf = nullptr;           // mcrat_hip_sightline_*: the output block and the caller's rays (sightline_plan.hpp); a view uses its pool's
-    size_t sl_bytes = 0;
-    void *rf_buf = nullptr;           // mcrat_hip_radiation_field: head, accumulator and staged edges (radfield_plan.hpp); a view uses its pool's
-    size_t rf_bytes = 0;
     int rf_path = 0;                  // the accumulation path of the last radiation field (ObservePath)
-    void *sky_buf = nullptr;          // mcrat_hip_observe_sky: the cube, the per-observer counters and the staged inputs (sky_plan.hpp); a view uses its pool's
-    size_t sky_bytes = 0;
     int sky_path = 0;                 // the accumulation path of the last sky observation (ObservePath)
 
     // profiling
@@ -429,10 +426,8 @@ extern "C" void mcrat_hip_destroy(mcrat_hip_ctx *c)
     if (c->h_state) (void)hipHostFree(c->h_state);
     if (c->d_red) (void)hipFree(c->d_red);
     if (c->h_red) (void)hipHostFree(c->h_red);
-    if (c->obs_buf) (void)hipFree(c->obs_buf);
-    if (c->sl_buf) (void)hipFree(c->sl_buf);
-    if (c->rf_buf) (void)hipFree(c->rf_buf);
-    if (c->sky_buf) (void)hipFree(c->sky_buf);
+    for (const auto &b : c->analysis)
+        if (b.buf) (void)hipFree(b.buf);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -456,8 +451,10 @@ extern "C" int mcrat_hip_synchronize(mcrat_hip_ctx *c)
 extern "C" size_t mcrat_hip_device_bytes(const mcrat_hip_ctx *c)
 {
     if (!c) return 0;
+    size_t analysis = 0;
+    for (const auto &b : c->analysis) analysis += b.bytes;
     return c->ph_bytes + c->hy_bytes + c->grid_bytes + c->grid_count_cap * sizeof(unsigned) + sizeof(Shortlist) + sizeof(LoopState) + c->partials_bytes +
-           sizeof(ReducePartial) * mcrat_hip_ctx::RED_BLOCKS + c->obs_bytes + c->sl_bytes;
+           sizeof(ReducePartial) * mcrat_hip_ctx::RED_BLOCKS + analysis;
 }
 
 extern "C" int mcrat_hip_create_hot_cross_section(mcrat_hip_ctx *c, double *thermal_table, int n_ph_e, int n_t, double log_ph_e_min,
@@ -4067,9 +4064,54 @@ extern "C" int mcrat_hip_avg_energy(mcrat_hip_ctx *c, double *erg)
     return MCRAT_HIP_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- the analysis products' device blocks
+// Block `which` with room for `need` bytes: the pool's when c is a view.  The block may be replaced, so nothing may still read the old one: c's
+// stream is drained first, and that of h -- another context whose staged frame the product reads, or nullptr -- because the frame is staged there.
+static int analysis_block(mcrat_hip_ctx *c, const mcrat_hip_ctx *h, int which, size_t need, char **d)
+{
+    mcrat_hip_ctx *owner = c->parent ? c->parent : c;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (h && h != c) HIPCHK(c, hipStreamSynchronize(h->stream));
+    mcrat_hip_ctx::DeviceBlock &b = owner->analysis[which];
+    int rc = ensure_device_bytes(c, &b.buf, &b.bytes, need);
+    if (rc) return rc;
+    *d = static_cast<char *>(b.buf);
+    return MCRAT_HIP_OK;
+}
+
+// A cube job, what mcrat_hip_observe and mcrat_hip_observe_sky share (observe_plan.hpp, sky_plan.hpp): the block is the cube's seven planes, the
+// per-observer counters and, behind them, `in` -- the kernel's inputs in the order it stages them, then the lists' clocks when there are any.  One
+// memset, one copy of the inputs, one launch, the planes and counters read back to wherever *out wants them.  `a` comes with everything but its
+// device pointers; launch(a) returns an MCRAT_HIP_* code.
+template <class Plan, class Dev, class Launch, class Out>
+static int cube_run(mcrat_hip_ctx *c, int which, const Plan &plan, const std::vector<double> &in, bool clocks, Dev a, Launch launch, Out *out)
+{
+    char *d = nullptr;
+    int rc = analysis_block(c, nullptr, which, plan.out_bytes + sizeof(double) * in.size(), &d);
+    if (rc) return rc;
+    double *d_in = reinterpret_cast<double *>(d + plan.out_bytes);
+    a.staged = d_in;
+    a.clocks = clocks ? d_in + plan.staged_doubles : nullptr;
+    a.cube = reinterpret_cast<double *>(d);
+    a.n_accepted = reinterpret_cast<unsigned long long *>(d + plan.cube_bytes);
+    a.n_outside = a.n_accepted + plan.n_obs;
+    HIPCHK(c, hipMemsetAsync(d, 0, plan.out_bytes, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_in, in.data(), sizeof(double) * in.size(), hipMemcpyHostToDevice, c->stream));
+    if ((rc = launch(a))) return rc;
+    const size_t plane = sizeof(double) * (size_t)plan.n_bins, counters = sizeof(long long) * (size_t)plan.n_obs;
+    void *planes[OBSERVE_PLANES] = {out->count, out->w, out->we, out->i, out->q, out->u, out->v};
+    static_assert(sizeof(long long) == 8, "the count plane and the counters are read back as they are");
+    for (int k = 0; k < OBSERVE_PLANES; ++k)
+        if (planes[k]) HIPCHK(c, hipMemcpyAsync(planes[k], d + plane * (size_t)k, plane, hipMemcpyDeviceToHost, c->stream));
+    if (out->n_accepted) HIPCHK(c, hipMemcpyAsync(out->n_accepted, d + plan.cube_bytes, counters, hipMemcpyDeviceToHost, c->stream));
+    if (out->n_outside) HIPCHK(c, hipMemcpyAsync(out->n_outside, d + plan.cube_bytes + counters, counters, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MCRAT_HIP_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- mock observations
 // The photons of c->ph -- n_slots of them -- binned by observer, detection time and energy (observe_plan.hpp, observe.hip), and the cube read back.
-// clocks: one per slots_per_clock slots (a rank pool's lists), or nullptr and time_now for all.  The device block belongs to the pool when c is a view.
+// clocks: one per slots_per_clock slots (a rank pool's lists), or nullptr and time_now for all.
 static int observe_run(mcrat_hip_ctx *c, const mcrat_hip_observer *obs, int n_slots, const double *clocks, int n_clocks, int slots_per_clock, double time_now,
                        mcrat_hip_observation *out)
 {
@@ -4084,41 +4126,23 @@ static int observe_run(mcrat_hip_ctx *c, const mcrat_hip_observer *obs, int n_sl
     if (why == OBSERVE_OK) why = observe_plan(obs->n_obs, obs->cos_lo, obs->cos_hi, obs->n_t, obs->t_edges, obs->n_e, obs->e_edges, forced, &plan);
     if (why != OBSERVE_OK) { c->last_error = observe_refusal_text(why); return MCRAT_HIP_EINVAL; }
 
-    // the inputs in the order the kernel stages them, the clocks behind them: one copy
+    // the inputs in the order the kernel stages them, the clocks behind them
     const size_t n_obs = (size_t)plan.n_obs;
     std::vector<double> in;
     in.reserve(plan.staged_doubles + (size_t)n_clocks);
-    in.insert(in.end(), obs->cos_obs, obs->cos_obs + n_obs); in.insert(in.end(), obs->sin_obs, obs->sin_obs + n_obs);
-    in.insert(in.end(), obs->cos_lo, obs->cos_lo + n_obs); in.insert(in.end(), obs->cos_hi, obs->cos_hi + n_obs);
+    for (const double *v : {obs->cos_obs, obs->sin_obs, obs->cos_lo, obs->cos_hi}) in.insert(in.end(), v, v + n_obs);
     in.insert(in.end(), obs->t_edges, obs->t_edges + plan.n_t + 1); in.insert(in.end(), obs->e_edges, obs->e_edges + plan.n_e + 1);
     if (clocks) in.insert(in.end(), clocks, clocks + n_clocks);
 
-    mcrat_hip_ctx *owner = c->parent ? c->parent : c;
-    HIPCHK(c, hipStreamSynchronize(c->stream));                  // (the block may be replaced: nothing may still read the old one)
-    int rc = ensure_device_bytes(c, &owner->obs_buf, &owner->obs_bytes, plan.out_bytes + sizeof(double) * in.size());
-    if (rc) return rc;
-    char *d = static_cast<char *>(owner->obs_buf);
-    double *d_in = reinterpret_cast<double *>(d + plan.out_bytes);
     ObserveDev a{};
     a.n_slots = n_slots; a.n_obs = plan.n_obs; a.n_t = plan.n_t; a.n_e = plan.n_e; a.n_bins = plan.n_bins;
-    a.staged = d_in;
-    a.clocks = clocks ? d_in + plan.staged_doubles : nullptr;
     a.slots_per_clock = slots_per_clock;
     a.time_now = time_now;
-    a.cube = reinterpret_cast<double *>(d);
-    a.n_accepted = reinterpret_cast<unsigned long long *>(d + plan.cube_bytes);
-    a.n_outside = a.n_accepted + n_obs;
-    HIPCHK(c, hipMemsetAsync(d, 0, plan.out_bytes, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_in, in.data(), sizeof(double) * in.size(), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, launch_observe(c->ph, a, plan, c->kc.stokes != 0, device_cus(c), c->stream));
-    const size_t plane = sizeof(double) * (size_t)plan.n_bins;
-    void *planes[OBSERVE_PLANES] = {out->count, out->w, out->we, out->i, out->q, out->u, out->v};
-    static_assert(sizeof(long long) == 8, "the count plane is read back as it is");
-    for (int k = 0; k < OBSERVE_PLANES; ++k)
-        if (planes[k]) HIPCHK(c, hipMemcpyAsync(planes[k], d + plane * (size_t)k, plane, hipMemcpyDeviceToHost, c->stream));
-    if (out->n_accepted) HIPCHK(c, hipMemcpyAsync(out->n_accepted, a.n_accepted, sizeof(long long) * n_obs, hipMemcpyDeviceToHost, c->stream));
-    if (out->n_outside) HIPCHK(c, hipMemcpyAsync(out->n_outside, a.n_outside, sizeof(long long) * n_obs, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int rc = cube_run(c, mcrat_hip_ctx::BLOCK_OBSERVE, plan, in, clocks != nullptr, a, [&](const ObserveDev &dev) -> int {
+        HIPCHK(c, launch_observe(c->ph, dev, plan, c->kc.stokes != 0, device_cus(c), c->stream));
+        return MCRAT_HIP_OK;
+    }, out);
+    if (rc) return rc;
     c->obs_path = plan.path;
     return MCRAT_HIP_OK;
 }
@@ -4177,23 +4201,8 @@ static std::vector<double> sky_staged_inputs(const SkyArgs &s, const SkyPlan &pl
     return in;
 }
 
-// The cube's planes and the per-observer counters from the device block to wherever the caller wants them.
-static int sky_read_back(mcrat_hip_ctx *c, const SkyPlan &plan, const char *d, mcrat_hip_sky_observation *out)
-{
-    const size_t plane = sizeof(double) * (size_t)plan.n_bins, counters = sizeof(long long) * (size_t)plan.n_obs;
-    void *planes[OBSERVE_PLANES] = {out->count, out->w, out->we, out->i, out->q, out->u, out->v};
-    static_assert(sizeof(long long) == 8, "the count plane and the counters are read back as they are");
-    for (int k = 0; k < OBSERVE_PLANES; ++k)
-        if (planes[k]) HIPCHK(c, hipMemcpyAsync(planes[k], d + plane * (size_t)k, plane, hipMemcpyDeviceToHost, c->stream));
-    if (out->n_accepted) HIPCHK(c, hipMemcpyAsync(out->n_accepted, d + plan.cube_bytes, counters, hipMemcpyDeviceToHost, c->stream));
-    if (out->n_outside) HIPCHK(c, hipMemcpyAsync(out->n_outside, d + plan.cube_bytes + counters, counters, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return MCRAT_HIP_OK;
-}
-
-// The photons of c->ph -- n_slots of them -- binned by observer, detection time, energy and sky-plane position (sky_plan.hpp, sky.hip): one memset,
-// one copy of the inputs, one launch, the cube read back.  clocks: one per slots_per_clock slots (a rank pool's lists), or nullptr and time_now for
-// all.  The device block belongs to the pool when c is a view.
+// The photons of c->ph -- n_slots of them -- binned by observer, detection time, energy and sky-plane position (sky_plan.hpp, sky.hip), and the cube
+// read back.  clocks: one per slots_per_clock slots (a rank pool's lists), or nullptr and time_now for all.
 static int sky_run(mcrat_hip_ctx *c, const mcrat_hip_sky_observer *obs, int n_slots, const double *clocks, int n_clocks, int slots_per_clock, double time_now,
                    mcrat_hip_sky_observation *out)
 {
@@ -4204,26 +4213,16 @@ static int sky_run(mcrat_hip_ctx *c, const mcrat_hip_sky_observer *obs, int n_sl
     SkyPlan plan;
     const SkyRefusal why = sky_plan(args, getenv("MCRAT_HIP_SKY_PATH"), &plan);
     if (why != SKY_OK) { c->last_error = sky_refusal_text(why); return MCRAT_HIP_EINVAL; }
-    const std::vector<double> in = sky_staged_inputs(args, plan, clocks, n_clocks);
 
-    mcrat_hip_ctx *owner = c->parent ? c->parent : c;
-    HIPCHK(c, hipStreamSynchronize(c->stream));                  // (the block may be replaced: nothing may still read the old one)
-    if ((rc = ensure_device_bytes(c, &owner->sky_buf, &owner->sky_bytes, plan.out_bytes + sizeof(double) * in.size()))) return rc;
-    char *d = static_cast<char *>(owner->sky_buf);
-    double *d_in = reinterpret_cast<double *>(d + plan.out_bytes);
     SkyDev a{};
     a.n_slots = n_slots; a.n_obs = plan.n_obs; a.n_t = plan.n_t; a.n_e = plan.n_e; a.n_x = plan.n_x; a.n_y = plan.n_y; a.n_bins = plan.n_bins;
-    a.staged = d_in;
-    a.clocks = clocks ? d_in + plan.staged_doubles : nullptr;
     a.slots_per_clock = slots_per_clock;
     a.time_now = time_now;
-    a.cube = reinterpret_cast<double *>(d);
-    a.n_accepted = reinterpret_cast<unsigned long long *>(d + plan.cube_bytes);
-    a.n_outside = a.n_accepted + plan.n_obs;
-    HIPCHK(c, hipMemsetAsync(d, 0, plan.out_bytes, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_in, in.data(), sizeof(double) * in.size(), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, launch_sky(c->ph, a, plan, c->kc.stokes != 0, sky_grid(plan, n_slots, device_cus(c)), c->stream));
-    if ((rc = sky_read_back(c, plan, d, out))) return rc;
+    rc = cube_run(c, mcrat_hip_ctx::BLOCK_SKY, plan, sky_staged_inputs(args, plan, clocks, n_clocks), clocks != nullptr, a, [&](const SkyDev &dev) -> int {
+        HIPCHK(c, launch_sky(c->ph, dev, plan, c->kc.stokes != 0, sky_grid(plan, n_slots, device_cus(c)), c->stream));
+        return MCRAT_HIP_OK;
+    }, out);
+    if (rc) return rc;
     c->sky_path = plan.path;
     return MCRAT_HIP_OK;
 }
@@ -4251,7 +4250,7 @@ extern "C" int mcrat_hip_observe_sky_path(const mcrat_hip_ctx *c) { return c ? c
 // ---------------------------------------------------------------------------------------------- line-of-sight optical depths
 // n rays marched through a staged frame (sightline_plan.hpp, sightline.hip) and the per-ray results read back.  rays: the caller's seven host
 // arrays r0, r1, r2, p0 .. p3, or nullptr -- then the rays are the n slots of c->ph.  hydro: the context whose staged frame the rays cross, or
-// nullptr for c's own.  The device block belongs to the pool when c is a view.
+// nullptr for c's own.
 static int sightline_run(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_sightline_params *params, int n, const double *const *rays,
                          mcrat_hip_sightlines *out)
 {
@@ -4273,12 +4272,9 @@ static int sightline_run(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcr
     if (why == SIGHTLINE_OK) why = bad_switch;                   // (what the arguments are refused for comes first)
     if (why != SIGHTLINE_OK) { c->last_error = sightline_refusal_text(why); return MCRAT_HIP_EINVAL; }
 
-    mcrat_hip_ctx *owner = c->parent ? c->parent : c;
-    HIPCHK(c, hipStreamSynchronize(c->stream));                  // (the block may be replaced: nothing may still read the old one)
-    if (h != c) HIPCHK(c, hipStreamSynchronize(h->stream));      // ... and the other context's frame is staged on its stream
-    int rc = ensure_device_bytes(c, &owner->sl_buf, &owner->sl_bytes, plan.ray_offset + (rays ? plan.ray_bytes : 0));
+    char *d = nullptr;
+    int rc = analysis_block(c, h, mcrat_hip_ctx::BLOCK_SIGHTLINE, plan.ray_offset + (rays ? plan.ray_bytes : 0), &d);
     if (rc) return rc;
-    char *d = static_cast<char *>(owner->sl_buf);
     const int blocks = sightline_grid(plan, device_cus(c));
     SightlineDev a{};
     a.n = n;
@@ -4362,7 +4358,7 @@ static int radfield_prepare(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const 
 }
 
 // The n_slots slots of c->ph located in the frame of `hydro` and summed per bin (radfield_plan.hpp, radfield.hip): one memset, one copy of the
-// edges, one launch (a bin-major build: and the transposition), the planes read back.  The device block belongs to the pool when c is a view.
+// edges, one launch (a bin-major build: and the transposition), the planes read back.
 static int radfield_run(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_radfield_bins *bins, int n_slots, mcrat_hip_radfield *out)
 {
     c->rf_path = OBSERVE_PATH_NONE;
@@ -4372,11 +4368,8 @@ static int radfield_run(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcra
     if (rc) return rc;
     if (n_slots <= 0) { c->last_error = "radiation_field: no photons"; return MCRAT_HIP_ESTATE; }
 
-    mcrat_hip_ctx *owner = c->parent ? c->parent : c;
-    HIPCHK(c, hipStreamSynchronize(c->stream));                  // (the block may be replaced: nothing may still read the old one)
-    if (h != c) HIPCHK(c, hipStreamSynchronize(h->stream));      // ... and the other context's frame is staged on its stream
-    if ((rc = ensure_device_bytes(c, &owner->rf_buf, &owner->rf_bytes, plan.total_bytes))) return rc;
-    char *d = static_cast<char *>(owner->rf_buf);
+    char *d = nullptr;
+    if ((rc = analysis_block(c, h, mcrat_hip_ctx::BLOCK_RADFIELD, plan.total_bytes, &d))) return rc;
     RadfieldDev a{};
     a.n_slots = n_slots; a.n_r = plan.s.n_r; a.n_mu = plan.s.n_mu; a.n_bins = plan.n_bins;
     a.staged = reinterpret_cast<const double *>(d + plan.staged_offset);

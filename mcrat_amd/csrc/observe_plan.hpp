@@ -71,6 +71,12 @@ constexpr size_t OBSERVE_LDS_BUDGET = OBSERVE_LDS_PER_CU / 2;
 constexpr int OBSERVE_MAX_GROUPS_PER_CU = 8;
 constexpr int OBSERVE_LDS_GROUPS_PER_CU = 2;
 enum ObservePath { OBSERVE_PATH_NONE = 0, OBSERVE_PATH_LDS = 1, OBSERVE_PATH_GLOBAL = 2 };
+constexpr int OBSERVE_BLOCK = 256;               // threads per workgroup of every binned-sum kernel: one lane per slot and trip
+// global path of observe_sky and radiation_field: a wavefront's table of 2048 one-byte lane numbers that tells which of its lanes share a bin
+// (bin_accumulate.hpp, match_alone), one table per wavefront of the workgroup, and the entry a bin goes to
+constexpr int OBSERVE_MATCH_BITS = 11;
+constexpr size_t OBSERVE_MATCH_BYTES = (size_t)(OBSERVE_BLOCK / 64) << OBSERVE_MATCH_BITS;
+MCRAT_OBS_HD inline unsigned observe_match_hash(int bin) { return ((unsigned)bin * 2654435761u) >> (32 - OBSERVE_MATCH_BITS); }
 
 struct ObservePlan {
     int n_obs, n_t, n_e, n_bins;         // n_bins = n_obs * n_t * n_e
@@ -95,13 +101,55 @@ inline ObserveRefusal observe_path_switch(const char *env, ObservePath *forced)
     return OBSERVE_OK;
 }
 
-inline ObserveRefusal observe_edges_check(const double *edges, int n, ObserveRefusal not_finite, ObserveRefusal not_ascending)
+// An axis' edges[0 .. n]: all finite, then strictly ascending -- which of the two failed; every product maps that to its own refusal.
+enum EdgesFault { EDGES_OK = 0, EDGES_NOT_FINITE, EDGES_NOT_ASCENDING };
+inline EdgesFault edges_check(const double *edges, int n)
 {
     for (int k = 0; k <= n; ++k)
-        if (!isfinite(edges[k])) return not_finite;
+        if (!isfinite(edges[k])) return EDGES_NOT_FINITE;
     for (int k = 0; k < n; ++k)
-        if (!(edges[k] < edges[k + 1])) return not_ascending;
-    return OBSERVE_OK;
+        if (!(edges[k] < edges[k + 1])) return EDGES_NOT_ASCENDING;
+    return EDGES_OK;
+}
+template <class Refusal>
+inline Refusal edges_refusal(const double *edges, int n, Refusal ok, Refusal not_finite, Refusal not_ascending)
+{
+    const EdgesFault f = edges_check(edges, n);
+    return f == EDGES_OK ? ok : (f == EDGES_NOT_FINITE ? not_finite : not_ascending);
+}
+
+// Where a binned sum is accumulated (observe, observe_sky, radiation_field): in the workgroup's LDS when the staged inputs with the counters behind
+// them (staged_bytes) and the whole accumulator (acc_bytes) fit the budget, in global memory otherwise, unless `forced` says which -- forced LDS
+// without `fits` is the caller's to refuse.  lds_bytes: behind the staged part the accumulator (LDS) or the wavefronts' match tables (global;
+// match_bytes, 0 for a kernel without them).  groups_per_cu, LDS path: two, whatever would fit.  Every workgroup flushes its bins to the same
+// addresses and the memory side serves the atomics of one address one after the other, so more workgroups cost more at the flush than they win
+// streaming (1 x 1 x 64 on 10^6 photons: 88.6 us with eight per CU against 31.8 us with two).  Global path: as many as share a
+// CU's LDS, at most eight.
+struct AccumulateRule {
+    bool fits;
+    ObservePath path;
+    size_t lds_bytes;
+    int groups_per_cu;
+};
+inline AccumulateRule accumulate_rule(size_t staged_bytes, size_t acc_bytes, size_t match_bytes, ObservePath forced)
+{
+    AccumulateRule r{};
+    r.fits = staged_bytes + acc_bytes <= OBSERVE_LDS_BUDGET;
+    r.path = forced != OBSERVE_PATH_NONE ? forced : (r.fits ? OBSERVE_PATH_LDS : OBSERVE_PATH_GLOBAL);
+    r.lds_bytes = staged_bytes + (r.path == OBSERVE_PATH_LDS ? acc_bytes : match_bytes);
+    const size_t share = OBSERVE_LDS_PER_CU / r.lds_bytes;       // (0 < lds_bytes; within the budget: 2 or more)
+    r.groups_per_cu = r.path == OBSERVE_PATH_LDS ? OBSERVE_LDS_GROUPS_PER_CU
+                                                 : (share < (size_t)OBSERVE_MAX_GROUPS_PER_CU ? (int)share : OBSERVE_MAX_GROUPS_PER_CU);
+    return r;
+}
+
+// workgroups of `block` lanes for a grid-stride loop over n items: what covers them, at most groups_per_cu per CU and never more than hard_max (> 0)
+inline int accumulate_grid(long long n, int block, int cus, int groups_per_cu, int hard_max = 0)
+{
+    const long long want = (n + block - 1) / block;
+    long long cap = (long long)(cus > 0 ? cus : 256) * groups_per_cu;
+    if (hard_max > 0 && cap > hard_max) cap = hard_max;
+    return (int)(want < cap ? want : cap);
 }
 
 // The checks, in this order: the counts, their product, the cones, the time edges, the energy edges, what must fit LDS; then the path -- LDS when
@@ -114,8 +162,8 @@ inline ObserveRefusal observe_plan(int n_obs, const double *cos_lo, const double
     if (per_obs > INT_MAX || per_obs * (long long)n_obs > INT_MAX) return OBSERVE_TOO_MANY_BINS;
     for (int o = 0; o < n_obs; ++o)
         if (!(cos_lo[o] > cos_hi[o])) return OBSERVE_BAD_CONE;
-    ObserveRefusal why = observe_edges_check(t_edges, n_t, OBSERVE_T_EDGES_NOT_FINITE, OBSERVE_T_EDGES_NOT_ASCENDING);
-    if (why == OBSERVE_OK) why = observe_edges_check(e_edges, n_e, OBSERVE_E_EDGES_NOT_FINITE, OBSERVE_E_EDGES_NOT_ASCENDING);
+    ObserveRefusal why = edges_refusal(t_edges, n_t, OBSERVE_OK, OBSERVE_T_EDGES_NOT_FINITE, OBSERVE_T_EDGES_NOT_ASCENDING);
+    if (why == OBSERVE_OK) why = edges_refusal(e_edges, n_e, OBSERVE_OK, OBSERVE_E_EDGES_NOT_FINITE, OBSERVE_E_EDGES_NOT_ASCENDING);
     if (why != OBSERVE_OK) return why;
     ObservePlan p{};
     p.n_obs = n_obs; p.n_t = n_t; p.n_e = n_e; p.n_bins = (int)(per_obs * n_obs);
@@ -124,16 +172,9 @@ inline ObserveRefusal observe_plan(int n_obs, const double *cos_lo, const double
     p.staged_doubles = (size_t)4 * n_obs + (size_t)n_t + 1 + (size_t)n_e + 1;
     p.staged_bytes = 8 * p.staged_doubles + (size_t)2 * 8 * (size_t)n_obs;
     if (p.staged_bytes > OBSERVE_LDS_BUDGET) return OBSERVE_STAGING_TOO_LARGE;
-    const bool fits = p.staged_bytes + p.cube_bytes <= OBSERVE_LDS_BUDGET;
-    if (forced == OBSERVE_PATH_LDS && !fits) return OBSERVE_LDS_FORCED_TOO_LARGE;
-    p.path = forced != OBSERVE_PATH_NONE ? forced : (fits ? OBSERVE_PATH_LDS : OBSERVE_PATH_GLOBAL);
-    p.lds_bytes = p.staged_bytes + (p.path == OBSERVE_PATH_LDS ? p.cube_bytes : 0);
-    // LDS path: two per CU, whatever would fit.  Every workgroup flushes its bins to the same addresses and the memory side serves the atomics of
-    // one address one after the other, so more workgroups cost more at the flush than they win streaming (1 x 1 x 64 on 10^6 photons: 88.6 us
-    // with eight per CU against 31.8 us with two).  Global path: as many as its staged inputs let share a CU, at most eight.
-    const size_t share = OBSERVE_LDS_PER_CU / p.lds_bytes;       // (0 < lds_bytes <= the budget: 2 or more)
-    p.groups_per_cu = p.path == OBSERVE_PATH_LDS ? OBSERVE_LDS_GROUPS_PER_CU
-                                                 : (share < (size_t)OBSERVE_MAX_GROUPS_PER_CU ? (int)share : OBSERVE_MAX_GROUPS_PER_CU);
+    const AccumulateRule r = accumulate_rule(p.staged_bytes, p.cube_bytes, 0, forced);
+    if (forced == OBSERVE_PATH_LDS && !r.fits) return OBSERVE_LDS_FORCED_TOO_LARGE;
+    p.path = r.path; p.lds_bytes = r.lds_bytes; p.groups_per_cu = r.groups_per_cu;
     *plan = p;
     return OBSERVE_OK;
 }

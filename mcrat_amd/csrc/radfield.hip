@@ -5,16 +5,16 @@
 // record, or the bucket's record and one list entry) and one for the cell's temperature: the pass is bound by the latency of those gathers, as a
 // sightline step is.  The edges of SHELLS are staged into LDS once per workgroup.
 //
-// Two accumulation paths, picked by the plan:
+// Two accumulation paths, picked by the plan; the forms of both are bin_accumulate.hpp's:
 //   LDS      SHELLS whose six planes fit: the workgroup owns a private copy in LDS, adds into it with LDS atomics and flushes the bins it touched
-//            once, when it has run out of slots (observe.hip's form).
+//            once, when it has run out of slots (flush_lds_bins).
 //   global   CELLS, and SHELLS beyond LDS: hardware f64 atomic adds that return nothing, and an integer atomic for the count, straight into the
 //            accumulator in HBM.  A wavefront's 64 photons may sit in 64 different cells or all in one cell of the jet core.  So the wavefront first
 //            finds out which of its lanes share a bin: every lane writes its number into a one-byte table in LDS at a hash of its bin and reads back
 //            who won the entry; a lane that lost to a lane of the same bin marks the entry.  A lane that won an unmarked entry has a bin of its own
-//            and adds what it holds, all such lanes in the same six instructions.  Only the rest -- lanes of shared bins, and the few that lost an
-//            entry to another bin -- go through observe.hip's rounds: one per distinct bin, the group summed over the wavefront, its first lane
-//            adding for all.  Spread photons take no round at all, a wavefront inside one cell takes one.
+//            and adds what it holds, all such lanes in the same six instructions (match_alone).  Only the rest -- lanes of shared bins, and the few
+//            that lost an entry to another bin -- go through the rounds (add_shared_bins): one per distinct bin, the group summed over the wavefront,
+//            its first lane adding for all.  Spread photons take no round at all, a wavefront inside one cell takes one.
 // The accumulator in HBM is plane-major or bin-major (radfield_plan.hpp, MCRAT_RADFIELD_BIN_MAJOR); a bin-major one is transposed into the planes
 // the caller receives by radfield_transpose_kernel.
 // Counts are exact.  The five sums per bin depend on the order in which the atomics are served: they are NOT bit-reproducible from run to run.
@@ -24,32 +24,20 @@
 #include "observe_plan.hpp"
 #include "physics.hpp"
 #include "radfield_plan.hpp"
+#include "bin_accumulate.hpp"
 
 namespace mcrat {
 
 namespace {
 
-// no-return hardware adds: ds_add_f64 / global_atomic_add_f64 and their 64-bit integer kin
-__device__ __forceinline__ void add_f64(double *p, double v) { (void)unsafeAtomicAdd(p, v); }
-__device__ __forceinline__ void add_u64(unsigned long long *p, unsigned long long v) { (void)atomicAdd(p, v); }
+constexpr int RF_SUMS = RADFIELD_PLANES - 1;      // W, WE_lab, WE_comv, WNS, WT behind the count
 
-__device__ __forceinline__ double wave_sum(double v)
-{
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// one bin's six adds
-template <bool BIN_MAJOR>
-__device__ __forceinline__ void add_bin(double *acc, size_t nb, int bin, unsigned long long m, double w, double we_lab, double we_comv, double wns, double wt)
-{
-    add_u64(reinterpret_cast<unsigned long long *>(acc) + radfield_word(BIN_MAJOR, RF_COUNT, (size_t)bin, nb), m);
-    add_f64(acc + radfield_word(BIN_MAJOR, RF_W, (size_t)bin, nb), w);
-    add_f64(acc + radfield_word(BIN_MAJOR, RF_WE_LAB, (size_t)bin, nb), we_lab);
-    add_f64(acc + radfield_word(BIN_MAJOR, RF_WE_COMV, (size_t)bin, nb), we_comv);
-    add_f64(acc + radfield_word(BIN_MAJOR, RF_WNS, (size_t)bin, nb), wns);
-    add_f64(acc + radfield_word(BIN_MAJOR, RF_WT, (size_t)bin, nb), wt);
-}
+// the accumulator's address rule in HBM: plane- or bin-major (radfield_plan.hpp)
+struct RadfieldWord {
+    double *acc;
+    size_t nb;
+    __device__ __forceinline__ double *operator()(int plane, size_t bin) const { return acc + radfield_word(RADFIELD_BIN_MAJOR, plane, bin, nb); }
+};
 
 template <int DIMS, int GEOM, bool SHELLS, bool LDS_PLANES>
 __global__ __launch_bounds__(RADFIELD_BLOCK) void radfield_kernel(PhotonDev ph, HydroDev hy, RadfieldDev a)
@@ -64,10 +52,12 @@ __global__ __launch_bounds__(RADFIELD_BLOCK) void radfield_kernel(PhotonDev ph, 
     for (int k = tid; k < n_staged; k += RADFIELD_BLOCK) s_mem[k] = a.staged[k];
     if (tid < RADFIELD_N_SCALARS) s_scalar[tid] = 0ull;
     const size_t nb = (size_t)a.n_bins;
+    const PlaneMajor at_lds{s_planes, nb};
+    const RadfieldWord at{a.acc, nb};
     if constexpr (LDS_PLANES)
         for (size_t k = tid; k < (size_t)RADFIELD_PLANES * nb; k += RADFIELD_BLOCK) s_planes[k] = 0.0;      // (+0.0 and the integer 0 are the same bits)
     __syncthreads();
-    unsigned char *const s_match = reinterpret_cast<unsigned char *>(s_planes) + ((size_t)(tid >> 6) << RADFIELD_MATCH_BITS);      // (global path) this wavefront's table
+    unsigned char *const s_match = reinterpret_cast<unsigned char *>(s_planes) + ((size_t)(tid >> 6) << OBSERVE_MATCH_BITS);      // (global path) this wavefront's table
 
     const unsigned n = (unsigned)a.n_slots, stride = gridDim.x * RADFIELD_BLOCK;
     for (unsigned base = blockIdx.x * RADFIELD_BLOCK; base < n; base += stride) {          // (n < 2^31 and stride <= 2^19: no wrap; the same trips for every lane of the workgroup)
@@ -79,7 +69,7 @@ __global__ __launch_bounds__(RADFIELD_BLOCK) void radfield_kernel(PhotonDev ph, 
             live = observe_observable(ph.flags[i], ph.type[i], w);
         }
         int cell = -1, bin = -1;
-        double we_lab = 0, we_comv = 0, wns = 0, wt = 0;
+        double v[RF_SUMS] = {0, 0, 0, 0, 0};              // w, w * e_lab, w * e_comv, w * num_scatt, w * temp
         if (live) {
             const double r0 = ph.r0[i], r1 = ph.r1[i], r2 = ph.r2[i];
             const double p[4] = {ph.p0[i], ph.p1[i], ph.p2[i], ph.p3[i]};
@@ -97,10 +87,10 @@ __global__ __launch_bounds__(RADFIELD_BLOCK) void radfield_kernel(PhotonDev ph, 
                 phys::relocation_azimuth<DIMS, GEOM>(r0, r1, a0, cphi, sphi);
                 phys::beta_from_record<DIMS>(hit.a, hit.b, hit.c, cphi, sphi, beta);
                 phys::boost_with<false>(beta, hit.gam, phys::kf_of_gamma(hit.gam), p, comv);
-                we_lab = w * radfield_e_lab(p[0]);
-                we_comv = w * (comv[0] * C_LIGHT);
-                wns = w * ns;
-                wt = w * hy.temp[cell];
+                v[1] = w * radfield_e_lab(p[0]);
+                v[2] = w * (comv[0] * C_LIGHT);
+                v[3] = w * ns;
+                v[4] = w * hy.temp[cell];
                 if constexpr (SHELLS) {
                     double r, mu;
                     radfield_r_mu(r0, r1, r2, r, mu);
@@ -116,50 +106,19 @@ __global__ __launch_bounds__(RADFIELD_BLOCK) void radfield_kernel(PhotonDev ph, 
             if (m_unlocated) add_u64(&s_scalar[RF_N_UNLOCATED], (unsigned long long)__popcll(m_unlocated));
             if (m_outside) add_u64(&s_scalar[RF_N_OUTSIDE], (unsigned long long)__popcll(m_outside));
         }
+        v[0] = w;
         const bool has = bin >= 0;
         if constexpr (LDS_PLANES) {
-            if (has) add_bin<false>(s_planes, nb, bin, 1ull, w, we_lab, we_comv, wns, wt);
+            if (has) add_bin<RF_SUMS>(at_lds, bin, 1ull, v);
         } else {
-            // which lanes share a bin: the table entry at a hash of the bin goes to one of the lanes that want it
-            const unsigned h = ((unsigned)bin * 2654435761u) >> (32 - RADFIELD_MATCH_BITS);
-            if (has) s_match[h] = (unsigned char)lane;
-            __syncthreads();
-            const int owner = has ? (int)s_match[h] : lane;
-            const int owner_bin = __shfl(bin, owner, 64);
-            __syncthreads();
-            if (has && owner != lane && owner_bin == bin) s_match[h] = 64;      // the owner has company
-            __syncthreads();
-            const bool alone = has && owner == lane && s_match[h] == (unsigned char)lane;
-            if (alone) add_bin<RADFIELD_BIN_MAJOR>(a.acc, nb, bin, 1ull, w, we_lab, we_comv, wns, wt);
-            // the rest, group by group of the lanes that share a bin (the others contribute +0.0, which changes no sum)
-            unsigned long long todo = __ballot(has && !alone);
-            while (todo) {
-                const int leader = __ffsll((long long)todo) - 1;
-                const int lb = __shfl(bin, leader, 64);
-                const bool mine = !alone && bin == lb;
-                const unsigned long long group = __ballot(mine);
-                todo &= ~group;
-                const int m = __popcll(group);
-                double gw = w, gl = we_lab, gc = we_comv, gn = wns, gt = wt;
-                if (m > 1) {
-                    gw = wave_sum(mine ? w : 0.0); gl = wave_sum(mine ? we_lab : 0.0); gc = wave_sum(mine ? we_comv : 0.0);
-                    gn = wave_sum(mine ? wns : 0.0); gt = wave_sum(mine ? wt : 0.0);
-                }
-                if (lane == leader) add_bin<RADFIELD_BIN_MAJOR>(a.acc, nb, lb, (unsigned long long)m, gw, gl, gc, gn, gt);
-            }
+            const bool alone = match_alone(s_match, lane, bin, has);
+            if (alone) add_bin<RF_SUMS>(at, bin, 1ull, v);
+            add_shared_bins<RF_SUMS>(at, lane, alone ? -1 : bin, v);
         }
     }
     __syncthreads();
     if (tid < RADFIELD_N_SCALARS && s_scalar[tid]) add_u64(&a.head[tid], s_scalar[tid]);
-    if constexpr (LDS_PLANES) {
-        const unsigned long long *const s_count = reinterpret_cast<const unsigned long long *>(s_planes);
-        for (size_t b = tid; b < nb; b += RADFIELD_BLOCK) {
-            const unsigned long long m = s_count[b];
-            if (!m) continue;
-            add_bin<RADFIELD_BIN_MAJOR>(a.acc, nb, (int)b, m, s_planes[RF_W * nb + b], s_planes[RF_WE_LAB * nb + b], s_planes[RF_WE_COMV * nb + b],
-                                        s_planes[RF_WNS * nb + b], s_planes[RF_WT * nb + b]);
-        }
-    }
+    if constexpr (LDS_PLANES) flush_lds_bins<RF_SUMS, RADFIELD_BLOCK>(s_planes, nb, at, tid);
 }
 
 // a bin-major accumulator into the six planes the caller receives: one lane per bin, the stores coalesced per plane
@@ -174,13 +133,7 @@ __global__ __launch_bounds__(RADFIELD_BLOCK) void radfield_transpose_kernel(cons
 template <int DIMS, int GEOM, bool SHELLS, bool LDS_PLANES>
 hipError_t launch_one(const PhotonDev &ph, const HydroDev &hy, const RadfieldDev &a, int blocks, size_t lds_bytes, hipStream_t stream)
 {
-    if (lds_bytes > 64 * 1024) {               // more than the default 64 KB of dynamic LDS has to be asked for (per device: asked every time)
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&radfield_kernel<DIMS, GEOM, SHELLS, LDS_PLANES>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((radfield_kernel<DIMS, GEOM, SHELLS, LDS_PLANES>), dim3(blocks), dim3(RADFIELD_BLOCK), lds_bytes, stream, ph, hy, a);
-    return hipGetLastError();
+    return launch_with_lds(&radfield_kernel<DIMS, GEOM, SHELLS, LDS_PLANES>, blocks, RADFIELD_BLOCK, lds_bytes, lds_bytes, stream, ph, hy, a);
 }
 
 template <int DIMS, int GEOM>
@@ -218,8 +171,8 @@ hipError_t launch_radfield(const KernelConfig &kc, const PhotonDev &ph, const Hy
 hipError_t launch_radfield_transpose(const double *records, double *planes, int n_bins, int cus, hipStream_t stream)
 {
     if (n_bins <= 0) return hipErrorInvalidValue;
-    const long long want = ((long long)n_bins + RADFIELD_BLOCK - 1) / RADFIELD_BLOCK, cap = (long long)(cus > 0 ? cus : 256) * RADFIELD_MAX_GROUPS_PER_CU;
-    hipLaunchKernelGGL(radfield_transpose_kernel, dim3((unsigned)(want < cap ? want : cap)), dim3(RADFIELD_BLOCK), 0, stream, records, planes, n_bins);
+    const int blocks = accumulate_grid(n_bins, RADFIELD_BLOCK, cus, RADFIELD_MAX_GROUPS_PER_CU);
+    hipLaunchKernelGGL(radfield_transpose_kernel, dim3((unsigned)blocks), dim3(RADFIELD_BLOCK), 0, stream, records, planes, n_bins);
     return hipGetLastError();
 }
 

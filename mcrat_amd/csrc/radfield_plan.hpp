@@ -92,14 +92,13 @@ enum RadfieldHeadWord { RF_N_OBSERVABLE = 0, RF_N_UNLOCATED, RF_N_OUTSIDE };
 constexpr int RADFIELD_N_SCALARS = 3;
 constexpr size_t RADFIELD_ACC_OFFSET = 256;
 constexpr bool RADFIELD_BIN_MAJOR = MCRAT_RADFIELD_BIN_MAJOR != 0;
-constexpr int RADFIELD_BLOCK = 256;              // threads per workgroup: one lane per slot and trip
-// Workgroups per CU the grid is sized for: two on the LDS path, as for the observation cube (every workgroup flushes into the same bins); eight --
-// 32 wavefronts -- on the global path, which is bound by the latency of the cell look-up's gathers and wants them in flight.
-constexpr int RADFIELD_LDS_GROUPS_PER_CU = OBSERVE_LDS_GROUPS_PER_CU;
+constexpr int RADFIELD_BLOCK = OBSERVE_BLOCK;    // threads per workgroup: one lane per slot and trip
+// Workgroups per CU the grid is sized for (accumulate_rule, observe_plan.hpp): two on the LDS path, as for the observation cube (every workgroup
+// flushes into the same bins); eight -- 32 wavefronts -- on the global path, which is bound by the latency of the cell look-up's gathers and wants
+// them in flight.
 constexpr int RADFIELD_MAX_GROUPS_PER_CU = OBSERVE_MAX_GROUPS_PER_CU;
-// global path: a wavefront's table of 2048 one-byte lane numbers that tells which of its lanes share a bin (radfield.hip)
-constexpr int RADFIELD_MATCH_BITS = 11;
-constexpr size_t RADFIELD_MATCH_BYTES = (size_t)(RADFIELD_BLOCK / 64) << RADFIELD_MATCH_BITS;
+// global path: the wavefronts' match tables (observe_plan.hpp)
+constexpr size_t RADFIELD_MATCH_BYTES = OBSERVE_MATCH_BYTES;
 
 // word `plane` of bin `bin` in an accumulator of n_bins bins
 MCRAT_RF_HD inline size_t radfield_word(bool bin_major, int plane, size_t bin, size_t n_bins)
@@ -139,19 +138,6 @@ inline RadfieldRefusal radfield_path_switch(const char *env, ObservePath *forced
     return RADFIELD_OK;
 }
 
-inline bool radfield_all_finite(const double *edges, int n)
-{
-    for (int k = 0; k <= n; ++k)
-        if (!isfinite(edges[k])) return false;
-    return true;
-}
-inline bool radfield_ascending(const double *edges, int n)
-{
-    for (int k = 0; k < n; ++k)
-        if (!(edges[k] < edges[k + 1])) return false;
-    return true;
-}
-
 // The checks, in this order: the mode; SHELLS: the edge arrays, the counts, their product, r_edges finite, mu_edges finite, r_edges ascending,
 // mu_edges ascending, what must fit LDS; then the switch `env` (MCRAT_HIP_RADFIELD_PATH) -- its spelling, lds with CELLS, lds with planes beyond
 // the budget.  The path: LDS when the staged edges, the counters and the six planes fit OBSERVE_LDS_BUDGET, global otherwise, unless the switch says
@@ -161,28 +147,31 @@ inline RadfieldRefusal radfield_check(int mode, int n_r, const double *r_edges, 
     if (mode != RADFIELD_CELLS && mode != RADFIELD_SHELLS) return RADFIELD_BAD_MODE;
     RadfieldShape s{};
     s.mode = mode;
-    bool fits = false;
     if (mode == RADFIELD_SHELLS) {
         if (!r_edges || !mu_edges) return RADFIELD_NULL_EDGES;
         if (n_r < 1 || n_mu < 1) return RADFIELD_NO_BINS;
         const long long bins = (long long)n_r * (long long)n_mu;
         if (bins > INT_MAX) return RADFIELD_TOO_MANY_BINS;
-        if (!radfield_all_finite(r_edges, n_r)) return RADFIELD_R_EDGES_NOT_FINITE;
-        if (!radfield_all_finite(mu_edges, n_mu)) return RADFIELD_MU_EDGES_NOT_FINITE;
-        if (!radfield_ascending(r_edges, n_r)) return RADFIELD_R_EDGES_NOT_ASCENDING;
-        if (!radfield_ascending(mu_edges, n_mu)) return RADFIELD_MU_EDGES_NOT_ASCENDING;
+        const EdgesFault bad_r = edges_check(r_edges, n_r), bad_mu = edges_check(mu_edges, n_mu);      // (both finite before either ascending)
+        if (bad_r == EDGES_NOT_FINITE) return RADFIELD_R_EDGES_NOT_FINITE;
+        if (bad_mu == EDGES_NOT_FINITE) return RADFIELD_MU_EDGES_NOT_FINITE;
+        if (bad_r == EDGES_NOT_ASCENDING) return RADFIELD_R_EDGES_NOT_ASCENDING;
+        if (bad_mu == EDGES_NOT_ASCENDING) return RADFIELD_MU_EDGES_NOT_ASCENDING;
         s.n_r = n_r; s.n_mu = n_mu; s.n_shell_bins = (int)bins;
         s.staged_doubles = (size_t)n_r + 1 + (size_t)n_mu + 1;
     }
     s.staged_bytes = 8 * s.staged_doubles + 8 * (size_t)RADFIELD_N_SCALARS;
     if (s.staged_bytes > OBSERVE_LDS_BUDGET) return RADFIELD_STAGING_TOO_LARGE;
-    if (mode == RADFIELD_SHELLS) fits = s.staged_bytes + (size_t)RADFIELD_PLANES * 8 * (size_t)s.n_shell_bins <= OBSERVE_LDS_BUDGET;
     ObservePath forced;
     const RadfieldRefusal why = radfield_path_switch(env, &forced);
     if (why != RADFIELD_OK) return why;
     if (forced == OBSERVE_PATH_LDS && mode == RADFIELD_CELLS) return RADFIELD_LDS_FORCED_ON_CELLS;
-    if (forced == OBSERVE_PATH_LDS && !fits) return RADFIELD_LDS_FORCED_TOO_LARGE;
-    s.path = forced != OBSERVE_PATH_NONE ? forced : (fits ? OBSERVE_PATH_LDS : OBSERVE_PATH_GLOBAL);
+    s.path = OBSERVE_PATH_GLOBAL;
+    if (mode == RADFIELD_SHELLS) {
+        const AccumulateRule r = accumulate_rule(s.staged_bytes, (size_t)RADFIELD_PLANES * 8 * (size_t)s.n_shell_bins, RADFIELD_MATCH_BYTES, forced);
+        if (forced == OBSERVE_PATH_LDS && !r.fits) return RADFIELD_LDS_FORCED_TOO_LARGE;
+        s.path = r.path;
+    }
     *shape = s;
     return RADFIELD_OK;
 }
@@ -200,18 +189,15 @@ inline RadfieldPlan radfield_layout(const RadfieldShape &s, int n_cells, bool bi
     p.planes_offset = bin_major ? (p.zeroed_bytes + 255) / 256 * 256 : RADFIELD_ACC_OFFSET;
     p.staged_offset = ((bin_major ? p.planes_offset + planes : p.zeroed_bytes) + 255) / 256 * 256;
     p.total_bytes = p.staged_offset + 8 * s.staged_doubles;
-    const bool lds = s.path == OBSERVE_PATH_LDS;
-    p.lds_bytes = s.staged_bytes + (lds ? planes : RADFIELD_MATCH_BYTES);
-    const size_t share = OBSERVE_LDS_PER_CU / p.lds_bytes;
-    p.groups_per_cu = lds ? RADFIELD_LDS_GROUPS_PER_CU : (share < (size_t)RADFIELD_MAX_GROUPS_PER_CU ? (int)share : RADFIELD_MAX_GROUPS_PER_CU);
+    const AccumulateRule r = accumulate_rule(s.staged_bytes, planes, RADFIELD_MATCH_BYTES, s.path);       // (the path is decided: the LDS and the workgroups that go with it)
+    p.lds_bytes = r.lds_bytes; p.groups_per_cu = r.groups_per_cu;
     return p;
 }
 
 // workgroups of RADFIELD_BLOCK lanes: a grid-stride loop, at most what the plan wants resident per CU
 inline int radfield_grid(const RadfieldPlan &p, int n_slots, int cus)
 {
-    const long long want = ((long long)n_slots + RADFIELD_BLOCK - 1) / RADFIELD_BLOCK, cap = (long long)(cus > 0 ? cus : 256) * p.groups_per_cu;
-    return (int)(want < cap ? want : cap);
+    return accumulate_grid(n_slots, RADFIELD_BLOCK, cus, p.groups_per_cu);
 }
 
 // ------------------------------------------------------------------ one photon (host and device)

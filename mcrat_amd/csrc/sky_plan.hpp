@@ -36,7 +36,7 @@
 #endif
 
 // The global path's match table, a build-time switch: 0 (the default) the wavefront finds the lanes that share a bin through a one-byte table in LDS
-// before it adds (radfield.hip's form); 1 no table, every lane goes through the rounds of observe.hip's global path.  tools/sky_bench.py measures
+// before it adds (bin_accumulate.hpp, match_alone); 1 no table, every lane goes through the rounds (add_shared_bins).  tools/sky_bench.py measures
 // both on an image (profiles/sky_observe.txt).
 #ifndef MCRAT_SKY_NO_MATCH
 #define MCRAT_SKY_NO_MATCH 0
@@ -109,10 +109,11 @@ constexpr double SKY_UNIT_TOLERANCE = 1e-12;
 constexpr int SKY_BLOCK = 256;                   // threads per workgroup: one lane per slot and trip
 // The grid: a grid-stride loop over at most this many workgroups (eight per CU on the 256 CUs of an MI355X), whatever the device reports.
 constexpr int SKY_MAX_GRID = 2048;
-// global path: a wavefront's table of 2048 one-byte lane numbers that tells which of its lanes share a bin (sky.hip)
-constexpr int SKY_MATCH_BITS = 11;
-constexpr size_t SKY_MATCH_BYTES = MCRAT_SKY_NO_MATCH ? 0 : (size_t)(SKY_BLOCK / 64) << SKY_MATCH_BITS;
-MCRAT_SKY_HD inline unsigned sky_match_hash(int bin) { return ((unsigned)bin * 2654435761u) >> (32 - SKY_MATCH_BITS); }
+// global path: the wavefronts' match tables (observe_plan.hpp), unless the build does without them
+static_assert(SKY_BLOCK == OBSERVE_BLOCK, "the match tables are sized for the workgroup");
+constexpr int SKY_MATCH_BITS = OBSERVE_MATCH_BITS;
+constexpr size_t SKY_MATCH_BYTES = MCRAT_SKY_NO_MATCH ? 0 : OBSERVE_MATCH_BYTES;
+MCRAT_SKY_HD inline unsigned sky_match_hash(int bin) { return observe_match_hash(bin); }
 
 // the caller's arguments as the checks read them (host pointers)
 struct SkyArgs {
@@ -144,11 +145,7 @@ MCRAT_SKY_HD inline size_t sky_bin_index(int o, int it, int ie, int iy, int ix, 
 
 inline SkyRefusal sky_edges_check(const double *edges, int n, SkyRefusal not_finite, SkyRefusal not_ascending)
 {
-    for (int k = 0; k <= n; ++k)
-        if (!isfinite(edges[k])) return not_finite;
-    for (int k = 0; k < n; ++k)
-        if (!(edges[k] < edges[k + 1])) return not_ascending;
-    return SKY_OK;
+    return edges_refusal(edges, n, SKY_OK, not_finite, not_ascending);
 }
 inline bool sky_finite3(const double *a, const double *b, const double *c, int o) { return isfinite(a[o]) && isfinite(b[o]) && isfinite(c[o]); }
 inline double sky_dot(const double *a0, const double *a1, const double *a2, const double *b0, const double *b1, const double *b2, int o)
@@ -159,8 +156,8 @@ inline bool sky_unit(const double *a, const double *b, const double *c, int o) {
 
 // The checks, in this order: the counts; the image axes' counts; the product; the directions finite, then unit; the cones; with image axes the
 // sky-plane vectors -- there, finite, unit, orthogonal --; the edges of t, e, x, y -- each finite, then ascending --; what must fit LDS; then the
-// switch `env` (MCRAT_HIP_SKY_PATH) -- its spelling, lds with a cube beyond the budget.  The path: LDS when the staged inputs, the counters and the
-// whole cube fit OBSERVE_LDS_BUDGET, global otherwise, unless the switch says which.  *plan is filled when SKY_OK.
+// switch `env` (MCRAT_HIP_SKY_PATH) -- its spelling, lds with a cube beyond the budget.  The path, the LDS and the workgroups per CU are
+// accumulate_rule's (observe_plan.hpp).  *plan is filled when SKY_OK.
 inline SkyRefusal sky_plan(const SkyArgs &a, const char *env, SkyPlan *plan)
 {
     if (a.n_obs < 1 || a.n_t < 1 || a.n_e < 1) return SKY_NO_BINS;
@@ -203,14 +200,9 @@ inline SkyRefusal sky_plan(const SkyArgs &a, const char *env, SkyPlan *plan)
     if (p.staged_bytes + SKY_MATCH_BYTES > OBSERVE_LDS_BUDGET) return SKY_STAGING_TOO_LARGE;       // (so that the global path always has room for its tables)
     ObservePath forced;
     if (observe_path_switch(env, &forced) != OBSERVE_OK) return SKY_BAD_PATH_SWITCH;
-    const bool fits = p.staged_bytes + p.cube_bytes <= OBSERVE_LDS_BUDGET;
-    if (forced == OBSERVE_PATH_LDS && !fits) return SKY_LDS_FORCED_TOO_LARGE;
-    p.path = forced != OBSERVE_PATH_NONE ? forced : (fits ? OBSERVE_PATH_LDS : OBSERVE_PATH_GLOBAL);
-    p.lds_bytes = p.staged_bytes + (p.path == OBSERVE_PATH_LDS ? p.cube_bytes : SKY_MATCH_BYTES);
-    // LDS path: two per CU, as for observe's cube (every workgroup flushes into the same bins).  Global path: as many as share a CU's LDS, at most eight.
-    const size_t share = OBSERVE_LDS_PER_CU / p.lds_bytes;       // (0 < lds_bytes <= the budget: 2 or more)
-    p.groups_per_cu = p.path == OBSERVE_PATH_LDS ? OBSERVE_LDS_GROUPS_PER_CU
-                                                 : (share < (size_t)OBSERVE_MAX_GROUPS_PER_CU ? (int)share : OBSERVE_MAX_GROUPS_PER_CU);
+    const AccumulateRule r = accumulate_rule(p.staged_bytes, p.cube_bytes, SKY_MATCH_BYTES, forced);
+    if (forced == OBSERVE_PATH_LDS && !r.fits) return SKY_LDS_FORCED_TOO_LARGE;
+    p.path = r.path; p.lds_bytes = r.lds_bytes; p.groups_per_cu = r.groups_per_cu;
     *plan = p;
     return SKY_OK;
 }
@@ -218,10 +210,7 @@ inline SkyRefusal sky_plan(const SkyArgs &a, const char *env, SkyPlan *plan)
 // workgroups of SKY_BLOCK lanes: a grid-stride loop, at most what the plan wants resident per CU and never more than SKY_MAX_GRID
 inline int sky_grid(const SkyPlan &p, int n_slots, int cus)
 {
-    const long long want = ((long long)n_slots + SKY_BLOCK - 1) / SKY_BLOCK;
-    long long cap = (long long)(cus > 0 ? cus : 256) * p.groups_per_cu;
-    if (cap > SKY_MAX_GRID) cap = SKY_MAX_GRID;
-    return (int)(want < cap ? want : cap);
+    return accumulate_grid(n_slots, SKY_BLOCK, cus, p.groups_per_cu, SKY_MAX_GRID);
 }
 
 // ------------------------------------------------------------------ one photon (host and device)

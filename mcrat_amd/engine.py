@@ -1069,6 +1069,17 @@ class Engine:
         self._check(self.lib.mcrat_hip_avg_energy(self.ctx, C.byref(e)), "avg_energy")
         return e.value
 
+    @staticmethod
+    def _cube_result(shape, struct):
+        """the seven planes of an observation cube of `shape` (observer first) and the per-observer counters, zeroed, and the ABI's output
+        struct (Observation, SkyObservation) that points at them"""
+        res = {"count": np.zeros(shape, dtype=np.int64), "n_accepted": np.zeros(shape[0], dtype=np.int64), "n_outside": np.zeros(shape[0], dtype=np.int64)}
+        for k in ("w", "we", "i", "q", "u", "v"):
+            res[k] = np.zeros(shape)
+        ll = C.POINTER(C.c_longlong)
+        return res, struct(res["count"].ctypes.data_as(ll), *[res[k].ctypes.data_as(_dp) for k in ("w", "we", "i", "q", "u", "v")],
+                           res["n_accepted"].ctypes.data_as(ll), res["n_outside"].ctypes.data_as(ll))
+
     # ---- mock observations: the resident photons binned by observer, detection time and energy (include/mcrat_hip.h)
     def _observe(self, call, what, cos_obs, sin_obs, cos_lo, cos_hi, t_edges, e_edges, time_now):
         co, so, cl, ch, te, ee = (_f8(a).ravel() for a in (cos_obs, sin_obs, cos_lo, cos_hi, t_edges, e_edges))
@@ -1077,13 +1088,7 @@ class Engine:
             raise ValueError("%s: cos_obs, sin_obs, cos_lo and cos_hi must have one entry per observer" % what)
         obs = Observer(n_obs, co.ctypes.data_as(_dp), so.ctypes.data_as(_dp), cl.ctypes.data_as(_dp), ch.ctypes.data_as(_dp),
                        n_t, te.ctypes.data_as(_dp), n_e, ee.ctypes.data_as(_dp))
-        shape = (max(n_obs, 0), max(n_t, 0), max(n_e, 0))
-        res = {"count": np.zeros(shape, dtype=np.int64), "n_accepted": np.zeros(shape[0], dtype=np.int64), "n_outside": np.zeros(shape[0], dtype=np.int64)}
-        for k in ("w", "we", "i", "q", "u", "v"):
-            res[k] = np.zeros(shape)
-        ll = C.POINTER(C.c_longlong)
-        out = Observation(res["count"].ctypes.data_as(ll), *[res[k].ctypes.data_as(_dp) for k in ("w", "we", "i", "q", "u", "v")],
-                          res["n_accepted"].ctypes.data_as(ll), res["n_outside"].ctypes.data_as(ll))
+        res, out = self._cube_result((max(n_obs, 0), max(n_t, 0), max(n_e, 0)), Observation)
         self._check(call(self.ctx, C.byref(obs), time_now, C.byref(out)), what)
         return res
 
@@ -1129,13 +1134,7 @@ class Engine:
         row = lambda a, k: ptr(a[k]) if a is not None else None
         obs = SkyObserver(n_obs, row(nv, 0), row(nv, 1), row(nv, 2), ptr(ca), row(xv, 0), row(xv, 1), row(xv, 2), row(yv, 0), row(yv, 1), row(yv, 2),
                           n_t, ptr(te), n_e, ptr(ee), n_x, ptr(xe), n_y, ptr(ye))
-        shape = tuple(max(m, 0) for m in ((n_obs, n_t, n_e, n_y, n_x) if image else (n_obs, n_t, n_e)))
-        res = {"count": np.zeros(shape, dtype=np.int64), "n_accepted": np.zeros(shape[0], dtype=np.int64), "n_outside": np.zeros(shape[0], dtype=np.int64)}
-        for k in ("w", "we", "i", "q", "u", "v"):
-            res[k] = np.zeros(shape)
-        ll = C.POINTER(C.c_longlong)
-        out = SkyObservation(res["count"].ctypes.data_as(ll), *[res[k].ctypes.data_as(_dp) for k in ("w", "we", "i", "q", "u", "v")],
-                             res["n_accepted"].ctypes.data_as(ll), res["n_outside"].ctypes.data_as(ll))
+        res, out = self._cube_result(tuple(max(m, 0) for m in ((n_obs, n_t, n_e, n_y, n_x) if image else (n_obs, n_t, n_e))), SkyObservation)
         self._check(call(self.ctx, C.byref(obs), time_now, C.byref(out)), what)
         return res
 

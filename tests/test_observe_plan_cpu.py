@@ -63,6 +63,33 @@ PLANS = {
     "t_before_e": (1, [1.0], [0.9], 2, [0.0, 0.0, 1.0], 2, [NAN, 1.0, 2.0], PATH_NONE),           # the first check to fire decides
     "cone_before_edges": (1, [0.5], [0.5], 2, [0.0, 0.0, 1.0], 2, "ramp", PATH_NONE),
 }
+# The rule the three binned sums share (accumulate_rule): name: (staged bytes, accumulator bytes, match-table bytes, forced path), at the boundaries
+# the products pin -- observe 1 x 2 x 682 | 683 (5536 B staged, 112 B per energy bin), observe_sky the same cube behind 8 KiB of match tables,
+# radiation_field 1462 | 1463 x 1 shells (8 * (n_r + 3) + 24 B staged, 48 B per shell)
+MATCH_BYTES = 4 * 2048
+RULES = {
+    "observe_last": (5536, LDS_BUDGET - 5536, 0, PATH_NONE),                       # the cube is the budget minus the staged part: still LDS
+    "observe_first": (5544, 112 * 683, 0, PATH_NONE),                              # one bin more
+    "sky_last": (5536, LDS_BUDGET - 5536, MATCH_BYTES, PATH_NONE),
+    "sky_first": (5544, 112 * 683, MATCH_BYTES, PATH_NONE),
+    "radfield_last": (8 * 1465 + 24, 48 * 1462, MATCH_BYTES, PATH_NONE),
+    "radfield_first": (8 * 1466 + 24, 48 * 1463, MATCH_BYTES, PATH_NONE),
+    "one_byte_over": (5536, LDS_BUDGET - 5536 + 1, 0, PATH_NONE),
+    "forced_lds_fits": (208, 3584, MATCH_BYTES, PATH_LDS),
+    "forced_global_fits": (208, 3584, MATCH_BYTES, PATH_GLOBAL),
+    "forced_lds_beyond": (5544, 112 * 683, MATCH_BYTES, PATH_LDS),                 # does not fit: the caller refuses, told by `fits`
+    "forced_global_beyond": (5544, 112 * 683, MATCH_BYTES, PATH_GLOBAL),
+    "no_room_for_match": (LDS_BUDGET - MATCH_BYTES + 8, 56 * 10 ** 6, MATCH_BYTES, PATH_NONE),      # staged + tables beyond the budget: one workgroup per CU is all that is left (observe_sky refuses this)
+    "room_for_match_exactly": (LDS_BUDGET - MATCH_BYTES, 56 * 10 ** 6, MATCH_BYTES, PATH_NONE),
+    "tiny_global": (24, 56 * 10 ** 6, 0, PATH_NONE),                               # hundreds would share a CU's LDS: eight
+    "cells": (24, 48 * 2 ** 20, MATCH_BYTES, PATH_GLOBAL),                         # radiation_field CELLS
+}
+EDGES = {"ramp": [0.0, 1.0, 2.0], "one_bin": [1.0, 2.0], "nan": [0.0, NAN, 2.0], "inf": [0.0, 1.0, INF], "minus_inf": [-INF, 1.0, 2.0], "equal": [0.0, 1.0, 1.0],
+         "descending": [0.0, 2.0, 1.0], "nan_and_equal": [1.0, 1.0, NAN], "equal_first_pair": [0.0, 0.0, 1.0]}
+EDGES_OK, EDGES_NOT_FINITE, EDGES_NOT_ASCENDING = 0, 1, 2
+# (items, block, CUs, workgroups per CU, hard maximum or 0)
+GRIDS = {"one": (1, 256, 256, 8, 0), "ragged": (4099, 256, 256, 8, 0), "capped": (10 ** 6, 256, 256, 2, 0), "cus_unknown": (10 ** 6, 256, 0, 8, 0),
+         "hard_max": (10 ** 7, 256, 304, 8, 2048), "hard_max_unreached": (10 ** 6, 256, 256, 2, 2048), "few_cus": (10 ** 6, 256, 4, 8, 2048)}
 SWITCHES = {"unset": None, "empty": "", "lds": "lds", "global": "global", "upper": "LDS", "other": "hbm", "number": "1"}
 
 N_PHOTONS, N_OBS = 2000, 3
@@ -90,6 +117,15 @@ static void path_switch(const char *name, const char *env)
     const ObserveRefusal why = observe_path_switch(env, &forced);
     printf("switch_%s: %d %d\n", name, (int)why, (int)forced);
 }
+static void rule(const char *name, size_t staged, size_t acc, size_t match, int forced)
+{
+    const AccumulateRule r = accumulate_rule(staged, acc, match, (ObservePath)forced);
+    printf("rule_%s: %d %d %zu %d\n", name, (int)r.fits, (int)r.path, r.lds_bytes, r.groups_per_cu);
+}
+static void edges(const char *name, std::vector<double> e)
+{
+    printf("edges_%s: %d %d\n", name, (int)edges_check(e.data(), (int)e.size() - 1), (int)edges_refusal(e.data(), (int)e.size() - 1, 7, 8, 9));
+}
 static std::vector<double> read_doubles(FILE *f, size_t n)
 {
     std::vector<double> v(n);
@@ -102,6 +138,7 @@ int main(int argc, char **argv)
 @CASES@
     for (int k = 1; k <= (int)OBSERVE_LDS_FORCED_TOO_LARGE; ++k) printf("text_%d:%s\n", k, observe_refusal_text((ObserveRefusal)k));
     printf("constants: %d %zu\n", OBSERVE_PLANES, OBSERVE_LDS_BUDGET);
+    printf("match: %d %d %zu %u %u %u\n", OBSERVE_BLOCK, OBSERVE_MATCH_BITS, OBSERVE_MATCH_BYTES, observe_match_hash(0), observe_match_hash(1), observe_match_hash(2147483647));
     printf("bin_index: %zu %zu %zu\n", observe_bin(0, 0, 0, 4, 8), observe_bin(1, 2, 3, 4, 8), observe_bin(2, 3, 7, 4, 8));
     printf("observable: %d %d %d %d %d %d\n", (int)observe_observable(FLAG_VALID, 'i', 1.0), (int)observe_observable(FLAG_VALID | FLAG_MOVES, 'c', 2.5),
            (int)observe_observable(FLAG_MOVES, 'i', 1.0), (int)observe_observable(FLAG_VALID, 'i', 0.0), (int)observe_observable(FLAG_VALID, 'p', 1.0),
@@ -143,6 +180,12 @@ def _cases():
         lines.append('plan("%s", %d, %s, %s, %d, %s, %d, %s, %d);' % (name, n_obs, _vec(lo, 0), _vec(hi, 0), n_t, _vec(te, n_t), n_e, _vec(ee, n_e), forced))
     for name, env in SWITCHES.items():
         lines.append('path_switch("%s", %s);' % (name, "nullptr" if env is None else '"%s"' % env))
+    for name, (staged, acc, match, forced) in RULES.items():
+        lines.append('rule("%s", %d, %d, %d, %d);' % (name, staged, acc, match, forced))
+    for name, e in EDGES.items():
+        lines.append('edges("%s", %s);' % (name, _vec(e, 0)))
+    for name, g in GRIDS.items():
+        lines.append('printf("grid_%s: %%d\\n", accumulate_grid(%dLL, %d, %d, %d, %d));' % ((name,) + g))
     return "\n".join("    " + l for l in lines)
 
 
@@ -269,6 +312,55 @@ def test_plan_cases_are_what_they_are_meant_to_be(out):
     assert out["planv_one_bin"][0] == PATH_LDS
     assert out["planv_forced_global"][0] == PATH_GLOBAL and out["planv_forced_lds"][0] == PATH_LDS and out["planv_forced_global_beyond"][0] == PATH_GLOBAL
     assert out["planv_staging_last"][0] == PATH_GLOBAL and out["planv_staging_last"][5] == 81912
+
+
+def accumulate_rule(staged, acc, match, forced):
+    """the shared rule restated: fits, path, the kernel's dynamic LDS, workgroups per CU"""
+    fits = staged + acc <= LDS_BUDGET
+    path = forced if forced != PATH_NONE else (PATH_LDS if fits else PATH_GLOBAL)
+    lds = staged + (acc if path == PATH_LDS else match)
+    return [int(fits), path, lds, 2 if path == PATH_LDS else min(2 * LDS_BUDGET // lds, 8)]
+
+
+@pytest.mark.parametrize("name", sorted(RULES))
+def test_accumulate_rule(out, name):
+    assert out["rule_" + name] == accumulate_rule(*RULES[name])
+
+
+def test_accumulate_rule_cases_are_what_they_are_meant_to_be(out):
+    """the path changes exactly where the staged part and the accumulator reach the budget, for each product's own boundary"""
+    for product, match in (("observe", 0), ("sky", MATCH_BYTES), ("radfield", MATCH_BYTES)):
+        last, first = RULES[product + "_last"], RULES[product + "_first"]
+        assert last[0] + last[1] == LDS_BUDGET and LDS_BUDGET < first[0] + first[1] <= LDS_BUDGET + 120
+        assert out["rule_%s_last" % product] == [1, PATH_LDS, LDS_BUDGET, 2]
+        assert out["rule_%s_first" % product] == [0, PATH_GLOBAL, first[0] + match, 8]
+    assert out["rule_one_byte_over"][:2] == [0, PATH_GLOBAL]
+    assert out["rule_forced_lds_fits"] == [1, PATH_LDS, 208 + 3584, 2] and out["rule_forced_global_fits"] == [1, PATH_GLOBAL, 208 + MATCH_BYTES, 8]
+    assert out["rule_forced_lds_beyond"][:2] == [0, PATH_LDS] and out["rule_forced_lds_beyond"][2] > LDS_BUDGET       # fits says no: every caller refuses
+    assert out["rule_forced_global_beyond"] == [0, PATH_GLOBAL, 5544 + MATCH_BYTES, 8]
+    assert out["rule_no_room_for_match"] == [0, PATH_GLOBAL, LDS_BUDGET + 8, 1] and out["rule_room_for_match_exactly"] == [0, PATH_GLOBAL, LDS_BUDGET, 2]
+    assert out["rule_tiny_global"] == [0, PATH_GLOBAL, 24, 8] and out["rule_cells"] == [0, PATH_GLOBAL, 24 + MATCH_BYTES, 8]
+    assert out["match"] == [256, 11, MATCH_BYTES, 0, (2654435761 >> 21), ((2147483647 * 2654435761) % 2 ** 32) >> 21]
+
+
+def test_edges_check(out):
+    """all finite first, then strictly ascending: which of the two failed, and the caller's own codes for them"""
+    want = {"ramp": EDGES_OK, "one_bin": EDGES_OK, "nan": EDGES_NOT_FINITE, "inf": EDGES_NOT_FINITE, "minus_inf": EDGES_NOT_FINITE, "equal": EDGES_NOT_ASCENDING,
+            "descending": EDGES_NOT_ASCENDING, "nan_and_equal": EDGES_NOT_FINITE, "equal_first_pair": EDGES_NOT_ASCENDING}
+    assert set(want) == set(EDGES)
+    for name, e in EDGES.items():
+        rule = EDGES_NOT_FINITE if not all(np.isfinite(e)) else (EDGES_OK if all(a < b for a, b in zip(e[:-1], e[1:])) else EDGES_NOT_ASCENDING)
+        assert rule == want[name], name
+        assert out["edges_" + name] == [want[name], 7 + want[name]], name
+
+
+def test_accumulate_grid(out):
+    """what covers the items, at most the workgroups per CU on every CU (256 when the device does not say), never more than the hard maximum"""
+    for name, (n, block, cus, per_cu, hard) in GRIDS.items():
+        cap = (cus if cus > 0 else 256) * per_cu
+        cap = min(cap, hard) if hard > 0 else cap
+        assert out["grid_" + name] == [min(-(-n // block), cap)], name
+    assert [out["grid_" + k][0] for k in ("one", "ragged", "capped", "cus_unknown", "hard_max", "hard_max_unreached", "few_cus")] == [1, 17, 512, 2048, 2048, 512, 32]
 
 
 def test_path_switch(out):
