@@ -236,6 +236,15 @@ static CsEmitParams cs_emit_params(const mcrat_hip_ctx *c, const mcrat_hip_cyclo
     return CsEmitParams{c->kc.dimensions, c->kc.geometry, cs->b_field_calc, cs->epsilon_b, 0.0, 0.0, 0.0, 0.0};
 }
 static void emit_into(CsEmitParams &p, const Region &shell) { p.rmin = shell.rmin; p.rmax = shell.rmax; p.theta_min = shell.tmin; p.theta_max = shell.tmax; }
+// One region (p: a slab's InjectParams or a shell's CsEmitParams) for the lists of a pool that share it: its cells flagged in c->grid_count and counted,
+// *n_cells of them, room for their records in d_cells, and write() -- the region's launch_region_write -- scans the flags and writes the records
+template <class Params, class Cell, class Write>
+static int pool_region_cells(mcrat_hip_ctx *c, const Params &p, DeviceTemp<Cell> &d_cells, int *n_cells, Write write)
+{
+    if (launch_region_flag(p, c->hy, c->grid_count, c->d_grid_total, n_cells, c->stream) != hipSuccess) return MCRAT_HIP_EHIP;
+    if (d_cells.reserve((size_t)*n_cells) != hipSuccess) return MCRAT_HIP_ENOMEM;
+    return write() == hipSuccess ? MCRAT_HIP_OK : MCRAT_HIP_EHIP;
+}
 
 static void drop_graph(mcrat_hip_ctx *c)
 {
@@ -1382,7 +1391,7 @@ extern "C" int mcrat_hip_inject_photons(mcrat_hip_ctx *c, double r_inj, double p
     unsigned long long total = 0;
     bool ok = false;
     for (unsigned long long attempt = 0; attempt <= 200 && !ok; ++attempt) {
-        HIPCHK(c, launch_inject_count(p, c->hy, weight, attempt, key, c->grid_count, c->d_grid_total, c->stream));
+        HIPCHK(c, launch_birth_count(p, c->hy, weight, attempt, key, c->grid_count, c->d_grid_total, c->stream));
         HIPCHK(c, hipMemcpyAsync(&total, c->d_grid_total, sizeof total, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         ok = weight_search_step(total, min_photons, (double)max_photons, &weight);
@@ -1458,9 +1467,8 @@ extern "C" int mcrat_hip_pool_inject_photons(mcrat_hip_ctx *c, double fps, mcrat
         for (int g = 0; g < n_slabs; ++g) {
             const InjectParams p = inject_params(c, slabs[(size_t)g]);
             int n_slab = 0;
-            if (launch_inject_slab_flag(p, c->hy, c->grid_count, c->d_grid_total, &n_slab, c->stream) != hipSuccess) return MCRAT_HIP_EHIP;
-            if (d_slab.reserve((size_t)n_slab) != hipSuccess) return MCRAT_HIP_ENOMEM;
-            if (n_slab > 0 && launch_inject_slab_write(p, c->hy, c->grid_count, n_slab, d_start, d_start + M + 1, d_slab, c->stream) != hipSuccess) return MCRAT_HIP_EHIP;
+            if ((rc = pool_region_cells(c, p, d_slab, &n_slab, [&] { return launch_region_write(p, c->hy, c->grid_count, n_slab, d_start, d_start + M + 1, d_slab, c->stream); })))
+                return rc;
             if (launch_inject_pool(p, c->hy, c->ph, c->rank_stride, R, d_slab, n_slab, d_pi, g, c->stream) != hipSuccess ||
                 hipStreamSynchronize(c->stream) != hipSuccess) { c->last_error = "photon injection of the pool's lists failed"; return MCRAT_HIP_EHIP; }
         }
@@ -1585,7 +1593,7 @@ extern "C" int mcrat_hip_emit_cyclosynch_pool(mcrat_hip_ctx *c, const mcrat_hip_
     bool ok = false;
     for (unsigned long long attempt = 0; attempt <= 400 && !ok; ++attempt) {
         if (hipMemsetAsync(d_flags, 0, 4 * sizeof(unsigned), c->stream) != hipSuccess) return MCRAT_HIP_EHIP;
-        if (launch_cs_emit_count(p, c->hy, c->hcol, weight, attempt, key, c->grid_count, c->d_grid_total, d_flags, c->stream) != hipSuccess ||
+        if (launch_birth_count(p, c->hy, c->hcol, weight, attempt, key, c->grid_count, c->d_grid_total, d_flags, c->stream) != hipSuccess ||
             hipMemcpyAsync(&total, c->d_grid_total, sizeof total, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
             hipMemcpyAsync(flags, d_flags, sizeof flags, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
             hipStreamSynchronize(c->stream) != hipSuccess) { c->last_error = "cyclo-synchrotron emission: count pass failed"; return MCRAT_HIP_EHIP; }
@@ -3511,11 +3519,9 @@ static int pool_emit_cyclosynch(PoolCsFrames &F)
         for (int g = 0; g < n_shells; ++g) {
             emit_into(p, shells[(size_t)g]);
             int n_shell = 0;
-            if (launch_cs_shell_flag(p, c->hy, c->grid_count, c->d_grid_total, &n_shell, c->stream) != hipSuccess) return MCRAT_HIP_EHIP;
-            if (d_shell.reserve((size_t)n_shell) != hipSuccess) return MCRAT_HIP_ENOMEM;
-            if (n_shell > 0 && launch_cs_shell_write(p, c->hy, c->hcol, c->grid_count, n_shell, d_start, d_start + M + 1, d_shell, d_bad, c->stream) != hipSuccess)
-                return MCRAT_HIP_EHIP;
-            if (n_shell == 0 && hipMemsetAsync(d_bad, 0, sizeof(unsigned), c->stream) != hipSuccess) return MCRAT_HIP_EHIP;
+            if ((rc = pool_region_cells(c, p, d_shell, &n_shell,
+                                        [&] { return launch_region_write(p, c->hy, c->hcol, c->grid_count, n_shell, d_start, d_start + M + 1, d_shell, d_bad, c->stream); })))
+                return rc;
             if (launch_cs_emit_pool(p, c->hy, c->hcol, c->ph, c->rank_stride, R, c->d_desc, d_shell, n_shell, d_pe, g, c->stream) != hipSuccess ||
                 hipMemcpyAsync(&bad[g], d_bad, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
                 hipStreamSynchronize(c->stream) != hipSuccess) { c->last_error = "cyclo-synchrotron emission of the pool's lists failed"; return MCRAT_HIP_EHIP; }

@@ -58,8 +58,10 @@ __device__ __forceinline__ double element_volume(int dims, int geom, const CellR
     return V;
 }
 
-// mclib.c:40-57
-__device__ __forceinline__ bool in_injection_slab(const InjectParams &p, const CellRec &c)
+// Whether cell c touches the region rmin .. rmax, theta_min .. theta_max of p (InjectParams or CsEmitParams): the injection slab of mclib.c:40-57,
+// to which its upper bounds belong, or the emission shell of mc_cyclosynch.c:1215-1226, to which they do not (STRICT_UPPER)
+template <bool STRICT_UPPER, class Params>
+__device__ __forceinline__ bool in_region(const Params &p, const CellRec &c)
 {
     double r_in, th_in, r_out, th_out;
     if (p.dimensions == DIM_THREE) {
@@ -69,6 +71,7 @@ __device__ __forceinline__ bool in_injection_slab(const InjectParams &p, const C
         hydro_to_spherical(p.dimensions, p.geometry, c.c0 - 0.5 * c.s0, c.c1 - 0.5 * c.s1, 0, r_in, th_in);
         hydro_to_spherical(p.dimensions, p.geometry, c.c0 + 0.5 * c.s0, c.c1 + 0.5 * c.s1, 0, r_out, th_out);
     }
+    if (STRICT_UPPER) return (p.rmin <= r_out) && (r_in < p.rmax) && (th_out >= p.theta_min) && (th_in < p.theta_max);
     return (p.rmin <= r_out) && (r_in <= p.rmax) && (th_out >= p.theta_min) && (th_in <= p.theta_max);
 }
 
@@ -103,42 +106,34 @@ __device__ __forceinline__ long long poisson(EventStream &rng, double mean)
     return (long long)mean;
 }
 
-__global__ __launch_bounds__(256) void inject_count_kernel(InjectParams p, HydroDev hy, double weight, unsigned long long attempt, RngKey key,
-                                                           unsigned *__restrict__ count, unsigned long long *__restrict__ total)
+// a cell's photon count: the draw, kept within what the reference's int holds
+__device__ __forceinline__ unsigned poisson_count(EventStream &rng, double mean)
 {
-    __shared__ unsigned long long s_sum[4];
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    unsigned long long mine = 0;
-    if (i < hy.M) {
-        const CellRec c = load_cell(hy, p.dimensions, i);
-        unsigned n = 0;
-        if (in_injection_slab(p, c)) {
-            const double T = hy.temp[i];
-            const double gamma = hy.gamma[i];
-            const double ph_dens_calc = (4.0 / 3.0) * element_volume(p.dimensions, p.geometry, c) * ((gamma * p.num_dens_coeff * T * T * T) / weight);   // mclib.c:110
-            EventStream rng = keyed_stream(key, attempt, (uint32_t)i, RNG_INJECT_COUNT);
-            const long long k = poisson(rng, ph_dens_calc);
-            n = (unsigned)(k < 0 ? 0 : (k > 0x7fffffffll ? 0x7fffffffll : k));
-        }
-        count[i] = n;
-        mine = n;
-    }
-    for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 64);
-    if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = mine;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(total, s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3]);
+    const long long k = poisson(rng, mean);
+    return (unsigned)(k < 0 ? 0 : (k > 0x7fffffffll ? 0x7fffffffll : k));
 }
 
-// exclusive scan of one value per thread over the workgroup (256 threads); returns the thread's offset, *total the sum
-__device__ __forceinline__ int block_exclusive_scan_256(int v, int *s_w, int *total)
+// the sum of one value per thread over the workgroup (256 threads), in every thread; s_sum: four words of LDS
+__device__ __forceinline__ unsigned long long block_sum_256(unsigned long long v, unsigned long long *s_sum)
+{
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    __syncthreads();                                     // (s_sum may still be read from the previous call)
+    if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
+}
+
+// exclusive scan of one value per thread (int or unsigned) over the workgroup (256 threads); returns the thread's offset, *total the sum
+template <class T>
+__device__ __forceinline__ T block_exclusive_scan_256(T v, T *s_w, T *total)
 {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int x = v;
-    for (int off = 1; off < 64; off <<= 1) { const int y = __shfl_up(x, off); if (lane >= off) x += y; }
-    __syncthreads();
+    T x = v;
+    for (int off = 1; off < 64; off <<= 1) { const T y = __shfl_up(x, off); if (lane >= off) x += y; }
+    __syncthreads();                                     // (s_w may still be read from the previous call)
     if (lane == 63) s_w[w] = x;
     __syncthreads();
-    int before = 0;
+    T before = 0;
     for (int k = 0; k < w; ++k) before += s_w[k];
     *total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
     return before + x - v;
@@ -218,132 +213,7 @@ __device__ void inject_one(const InjectParams &p, const HydroDev &hy, double wei
     ph.type[k] = 'i';                                                        // INJECTED_PHOTON, mcrat.h
 }
 
-__global__ __launch_bounds__(256) void inject_generate_kernel(InjectParams p, HydroDev hy, double weight, RngKey key, const int *__restrict__ start,
-                                                              PhotonDev ph)
-{
-    const int k = blockIdx.x * 256 + threadIdx.x;
-    if (k >= ph.n) return;
-    // the cell of photon k: start[i] <= k < start[i+1]
-    int lo = 0, hi = hy.M;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (start[mid] <= k) lo = mid; else hi = mid;
-    }
-    inject_one(p, hy, weight, key, k, lo, ph);
-}
-
-// ---- photonInjection for many lists of a rank pool at once.  Whether a cell touches the injection slab, its volume and gamma T^3 do not depend
-// on the list: inject_slab_* find the slab's cells once per group of lists with the same slab (an angle bin's ranks), in cell order, with the
-// two factors of mclib.c:110; inject_pool_kernel, one workgroup per list, runs the list's weight loop on its own Poisson streams (the keys of
-// the one-list path: {seed, attempt, cell, INJECT_COUNT}), and writes its photons ({seed, 0, k, INJECT_PHOTON}) into the list's window.
-__global__ __launch_bounds__(256) void inject_slab_flag_kernel(InjectParams p, HydroDev hy, unsigned *__restrict__ flag, unsigned long long *__restrict__ total)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    unsigned in = 0;
-    if (i < hy.M) {
-        in = in_injection_slab(p, load_cell(hy, p.dimensions, i)) ? 1u : 0u;
-        flag[i] = in;
-    }
-    const unsigned long long m = __ballot(in != 0);
-    if ((threadIdx.x & 63) == 0 && m) atomicAdd(total, (unsigned long long)__popcll(m));
-}
-
-__global__ __launch_bounds__(256) void inject_slab_write_kernel(InjectParams p, HydroDev hy, const unsigned *__restrict__ flag, const int *__restrict__ start,
-                                                                InjectSlabCell *__restrict__ out)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= hy.M || !flag[i]) return;
-    const CellRec c = load_cell(hy, p.dimensions, i);
-    const double T = hy.temp[i];
-    InjectSlabCell s;
-    s.cell = i; s.pad = 0;
-    s.v43 = (4.0 / 3.0) * element_volume(p.dimensions, p.geometry, c);       // mclib.c:110: (4/3) V * ((gamma a_n T^3) / weight), in that order
-    s.g = hy.gamma[i] * p.num_dens_coeff * T * T * T;
-    out[start[i]] = s;
-}
-
-__global__ __launch_bounds__(256) void inject_pool_kernel(InjectParams p, HydroDev hy, PhotonDev pool, int stride, const InjectSlabCell *__restrict__ slab,
-                                                          int n_slab, PoolInject *lists, int group)
-{
-    __shared__ unsigned long long s_sum[4];
-    __shared__ int s_w[4];
-    __shared__ int s_cell[POOL_INJECT_CAP];
-    __shared__ double s_weight;
-    __shared__ int s_ok, s_attempt;
-    const int r = blockIdx.x, tid = threadIdx.x;
-    PoolInject &L = lists[r];
-    if (!L.inject || L.group != group) return;
-    PhotonDev ph = pool;
-    offset_photons(ph, (size_t)r * (size_t)stride);
-    const RngKey key = {L.seed, L.stream, 0u};
-    if (tid == 0) { s_weight = L.weight_in; s_ok = 0; s_attempt = 0; }
-    __syncthreads();
-    unsigned long long total = 0;
-    for (int attempt = 0; attempt <= 200; ++attempt) {                       // mclib.c:87-136
-        const double weight = s_weight;
-        unsigned long long mine = 0;
-        for (int s = tid; s < n_slab; s += 256) {
-            const double ph_dens_calc = slab[s].v43 * (slab[s].g / weight);
-            EventStream rng = keyed_stream(key, (unsigned long long)attempt, (uint32_t)slab[s].cell, RNG_INJECT_COUNT);
-            const long long k = poisson(rng, ph_dens_calc);
-            mine += (unsigned long long)(k < 0 ? 0 : (k > 0x7fffffffll ? 0x7fffffffll : k));
-        }
-        for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 64);
-        __syncthreads();
-        if ((tid & 63) == 0) s_sum[tid >> 6] = mine;
-        __syncthreads();
-        total = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
-        if (tid == 0) {
-            if (total > (unsigned long long)L.max_photons) s_weight = weight * 10;
-            else if (total < (unsigned long long)L.min_photons) s_weight = weight * 0.5;
-            else { s_ok = 1; s_attempt = attempt; }
-        }
-        __syncthreads();
-        if (s_ok) break;
-    }
-    if (!s_ok) { if (tid == 0) { L.error = 1; L.n = 0; } return; }
-    const double weight = s_weight;
-    const int attempt = s_attempt, n = (int)total;
-    if (tid == 0) { L.n = n; L.weight_out = weight; L.error = n == 0 ? 2 : (n > stride || n > POOL_INJECT_CAP ? 3 : 0); }
-    if (n == 0 || n > stride || n > POOL_INJECT_CAP) return;
-    // photon k -> its cell: the accepted attempt's counts again, in cell order
-    int base = 0;
-    for (int c0 = 0; c0 < n_slab; c0 += 256) {
-        const int s = c0 + tid;
-        int cnt = 0, cell = -1;
-        if (s < n_slab) {
-            const double ph_dens_calc = slab[s].v43 * (slab[s].g / weight);
-            EventStream rng = keyed_stream(key, (unsigned long long)attempt, (uint32_t)slab[s].cell, RNG_INJECT_COUNT);
-            const long long k = poisson(rng, ph_dens_calc);
-            cnt = (int)(k < 0 ? 0 : (k > 0x7fffffffll ? 0x7fffffffll : k));
-            cell = slab[s].cell;
-        }
-        int chunk_total;
-        const int off = block_exclusive_scan_256(cnt, s_w, &chunk_total);
-        for (int j = 0; j < cnt; ++j) s_cell[base + off + j] = cell;
-        base += chunk_total;
-        __syncthreads();
-    }
-    ph.n = n;
-    for (int k = tid; k < n; k += 256) inject_one(p, hy, weight, key, k, s_cell[k], ph);
-}
-
-// ---------------------------------------------------------------------------------------------- cyclo-synchrotron pool emission
-
-
-// mc_cyclosynch.c:1215-1226 (note the strict upper bounds, unlike the injection's slab)
-__device__ __forceinline__ bool in_emission_slab(const CsEmitParams &p, const CellRec &c)
-{
-    double r_in, th_in, r_out, th_out;
-    if (p.dimensions == DIM_THREE) {
-        hydro_to_spherical(p.dimensions, p.geometry, fabs(c.c0) - 0.5 * c.s0, fabs(c.c1) - 0.5 * c.s1, fabs(c.c2) - 0.5 * c.s2, r_in, th_in);
-        hydro_to_spherical(p.dimensions, p.geometry, fabs(c.c0) + 0.5 * c.s0, fabs(c.c1) + 0.5 * c.s1, fabs(c.c2) + 0.5 * c.s2, r_out, th_out);
-    } else {
-        hydro_to_spherical(p.dimensions, p.geometry, c.c0 - 0.5 * c.s0, c.c1 - 0.5 * c.s1, 0, r_in, th_in);
-        hydro_to_spherical(p.dimensions, p.geometry, c.c0 + 0.5 * c.s0, c.c1 + 0.5 * c.s1, 0, r_out, th_out);
-    }
-    return (p.rmin <= r_out) && (r_in < p.rmax) && (th_out >= p.theta_min) && (th_in < p.theta_max);
-}
+// ---------------------------------------------------------------------------------------------- the Planck integral of the pool emission
 
 // blackbody_ph_spect, mc_cyclosynch.c:185-196
 __device__ __forceinline__ double planck_tail(double nu, double temp)
@@ -436,39 +306,114 @@ __device__ double qags_planck(double a, double b, double temp, int &status, bool
     return result;
 }
 
-// mc_cyclosynch.c:1244-1296, one weight: the Poisson count of every cell of the shell; flags[0] counts cells whose integral ran out of
-// intervals (qags_planck), flags[1] the cells of the shell, flags[2] the cells whose integral needed more than QAGS' first rule
-__global__ __launch_bounds__(256) void cs_emit_count_kernel(CsEmitParams p, HydroDev hy, HydroCols h, double weight, unsigned long long attempt, RngKey key,
-                                                            unsigned *__restrict__ count, unsigned long long *__restrict__ total, unsigned *__restrict__ flags)
+// ---------------------------------------------------------------------------------------------- the two kinds of birth
+// photonInjection (mclib.c:9-300) and the pool emission of photonEmitCyclosynch (mc_cyclosynch.c:1200-1460) are the same procedure: the cells of a
+// region get a Poisson number of photons at a weight, the weight is searched until the total fits, the photons are generated cell by cell.  A rule
+// says what differs: whether the region's upper bounds belong to it, the stream the counts are drawn from, and the mean number of photons of a cell
+// -- from the cell itself (one list: cell_mean) or from the region's record of it (rank pool: fill, record_mean), every expression as the reference
+// has it at that place.
+struct InjectRule {
+    using Params = InjectParams;
+    using Record = InjectSlabCell;
+    static constexpr bool STRICT_UPPER = false;
+    static constexpr uint32_t COUNT_STREAM = RNG_INJECT_COUNT;
+    InjectParams p;
+    HydroDev hy;
+    __device__ double cell_mean(int i, const CellRec &c, double weight, unsigned long long) const
+    {
+        const double T = hy.temp[i];
+        const double gamma = hy.gamma[i];
+        return (4.0 / 3.0) * element_volume(p.dimensions, p.geometry, c) * ((gamma * p.num_dens_coeff * T * T * T) / weight);   // mclib.c:110
+    }
+    __device__ void fill(Record &s, int i, const CellRec &c) const
+    {
+        const double T = hy.temp[i];
+        s.v43 = (4.0 / 3.0) * element_volume(p.dimensions, p.geometry, c);       // mclib.c:110: (4/3) V * ((gamma a_n T^3) / weight), in that order
+        s.g = hy.gamma[i] * p.num_dens_coeff * T * T * T;
+    }
+    __device__ static double record_mean(const Record &s, double weight) { return s.v43 * (s.g / weight); }
+};
+// flags[0] counts the cells whose integral ran out of intervals (qags_planck: the host refuses); cell_mean, on its first attempt, also flags[1] the
+// cells of the shell and flags[2] the cells whose integral needed more than QAGS' first rule (statistics)
+struct EmitRule {
+    using Params = CsEmitParams;
+    using Record = CsShellCell;
+    static constexpr bool STRICT_UPPER = true;
+    static constexpr uint32_t COUNT_STREAM = RNG_CS_COUNT;
+    CsEmitParams p;
+    HydroDev hy;
+    HydroCols h;
+    unsigned *flags;
+    __device__ double cell_mean(int i, const CellRec &c, double weight, unsigned long long attempt) const
+    {
+        if (attempt == 0) atomicAdd(flags + 1, 1u);
+        const double nu_c = cs_nu_c(p, hy, h, i);
+        int status;
+        bool bisected;
+        double ph_dens_calc = qags_planck(10, nu_c, hy.temp[i], status, bisected);          // mc_cyclosynch.c:1276
+        if (status == 2) atomicAdd(flags, 1u);
+        if (bisected && attempt == 0) atomicAdd(flags + 2, 1u);
+        ph_dens_calc *= element_volume(p.dimensions, p.geometry, c) / weight;                // :1277
+        return ph_dens_calc;
+    }
+    __device__ void fill(Record &s, int i, const CellRec &c) const
+    {
+        int status;
+        bool bisected;
+        s.integral = qags_planck(10, cs_nu_c(p, hy, h, i), hy.temp[i], status, bisected);    // :1276
+        s.volume = element_volume(p.dimensions, p.geometry, c);
+        if (status == 2) atomicAdd(flags, 1u);
+    }
+    __device__ static double record_mean(const Record &s, double weight)
+    {
+        double ph_dens_calc = s.integral;
+        ph_dens_calc *= s.volume / weight;                                                   // :1277
+        return ph_dens_calc;
+    }
+};
+template <class Params> struct BirthOf;
+template <> struct BirthOf<InjectParams> { using Rule = InjectRule; };
+template <> struct BirthOf<CsEmitParams> { using Rule = EmitRule; };
+
+// ---- one list.  mclib.c:87-136 / mc_cyclosynch.c:1244-1296, one weight: the Poisson count of every cell of the region and their sum
+template <class Rule>
+__global__ __launch_bounds__(256) void birth_count_kernel(Rule rule, double weight, unsigned long long attempt, RngKey key, unsigned *__restrict__ count,
+                                                          unsigned long long *__restrict__ total)
 {
     __shared__ unsigned long long s_sum[4];
     const int i = blockIdx.x * 256 + threadIdx.x;
-    unsigned long long mine = 0;
-    if (i < hy.M) {
-        const CellRec c = load_cell(hy, p.dimensions, i);
-        unsigned n = 0;
-        if (in_emission_slab(p, c)) {
-            if (attempt == 0) atomicAdd(flags + 1, 1u);
-            const double nu_c = cs_nu_c(p, hy, h, i);
-            int status;
-            bool bisected;
-            double ph_dens_calc = qags_planck(10, nu_c, hy.temp[i], status, bisected);
-            if (status == 2) atomicAdd(flags, 1u);                                                   // out of intervals: the host refuses
-            if (bisected && attempt == 0) atomicAdd(flags + 2, 1u);                                  // (statistics: cells past QAGS' first rule)
-            ph_dens_calc *= element_volume(p.dimensions, p.geometry, c) / weight;                    // :1277
-            EventStream rng = keyed_stream(key, attempt, (uint32_t)i, RNG_CS_COUNT);
-            const long long k = poisson(rng, ph_dens_calc);
-            n = (unsigned)(k < 0 ? 0 : (k > 0x7fffffffll ? 0x7fffffffll : k));
+    unsigned n = 0;
+    if (i < rule.hy.M) {
+        const CellRec c = load_cell(rule.hy, rule.p.dimensions, i);
+        if (in_region<Rule::STRICT_UPPER>(rule.p, c)) {
+            const double ph_dens_calc = rule.cell_mean(i, c, weight, attempt);
+            EventStream rng = keyed_stream(key, attempt, (uint32_t)i, Rule::COUNT_STREAM);
+            n = poisson_count(rng, ph_dens_calc);
         }
         count[i] = n;
-        mine = n;
     }
-    for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 64);
-    if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = mine;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(total, s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3]);
+    const unsigned long long sum = block_sum_256(n, s_sum);
+    if (threadIdx.x == 0) atomicAdd(total, sum);
 }
 
+// the cell of photon k of a birth, from the exclusive scan of the cells' counts: start[i] <= k < start[i + 1]
+__device__ __forceinline__ int cell_of_photon(const int *__restrict__ start, int M, int k)
+{
+    int lo = 0, hi = M;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (start[mid] <= k) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(256) void inject_generate_kernel(InjectParams p, HydroDev hy, double weight, RngKey key, const int *__restrict__ start,
+                                                              PhotonDev ph)
+{
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= ph.n) return;
+    inject_one(p, hy, weight, key, k, cell_of_photon(start, hy.M, k), ph);
+}
 
 // mc_cyclosynch.c:1340-1455: pool photon k into null slot null_slots[k], nearest_block_index = 0 (:1436)
 __global__ __launch_bounds__(256) void cs_emit_generate_kernel(CsEmitParams p, HydroDev hy, HydroCols h, double weight, RngKey key,
@@ -476,64 +421,135 @@ __global__ __launch_bounds__(256) void cs_emit_generate_kernel(CsEmitParams p, H
 {
     const int k = blockIdx.x * 256 + threadIdx.x;
     if (k >= n_emit) return;
-    int lo = 0, hi = hy.M;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (start[mid] <= k) lo = mid; else hi = mid;
-    }
     EventStream rng = keyed_stream(key, 0ull, (uint32_t)k, RNG_CS_PHOTON);
-    (void)cs_emit_one(p, hy, h, lo, weight, 0, rng, ph, null_slots[k]);
+    (void)cs_emit_one(p, hy, h, cell_of_photon(start, hy.M, k), weight, 0, rng, ph, null_slots[k]);
 }
 
-// The hook of mcrat.c:786-808 after a pass.  If the pass called photonEvent and the photon it reports is a pool photon, that photon
-// becomes a comptonised one and is replaced by a fresh pool photon of its weight in its cell (photonEmitCyclosynch with
-// inject_single_switch = 1, mc_cyclosynch.c:1467-1558, into the list's first null slot, photons.c:139-160), and it is itself moved to
-// a random place in that cell (:1540-1556); then the rebinning trigger of :797-808.  One workgroup; the pending advance must have
-// been applied (flush_kernel) so that the positions are current.  See CsFrame (launch.hpp) for how it parks the loop.
-// ---- pool emission for many lists at once (rank pool).  What photonEmitCyclosynch computes per cell -- whether the cell lies in the
-// emission shell, the Planck integral below its cyclotron frequency, its volume -- does not depend on the list; lists that emit into the
-// same shell (same injection radius, frame numbers and angle range: the ranks of an angle bin) share it.  cs_shell_*: the shell's cells
-// in ascending order with those per-cell values; cs_emit_pool_kernel: one workgroup per list runs that list's weight loop on its own
-// Poisson streams (the streams of the one-list path: {seed, attempt, cell, RNG_CS_COUNT}), places the photons in its null slots in
-// slot order (the list doubling inside its window of the pool when it has none), and generates them ({seed, 0, k, RNG_CS_PHOTON}).
-__global__ __launch_bounds__(256) void cs_shell_flag_kernel(CsEmitParams p, HydroDev hy, unsigned *__restrict__ flag, unsigned long long *__restrict__ total)
+// ---- many lists of a rank pool at once.  What a birth computes per cell -- whether the cell lies in the region, its volume, gamma T^3 or the Planck
+// integral below its cyclotron frequency -- does not depend on the list; lists with the same region (same radii, angle range and spectrum: the ranks of
+// an angle bin) share it.  region_flag_kernel and region_write_kernel: the region's cells in ascending order with those per-cell values (the rule's
+// record), once per group of lists.  Then one workgroup per list (inject_pool_kernel, cs_emit_pool_kernel) runs the list's weight search on its own
+// Poisson streams -- the keys of the one-list path, {seed, attempt, cell, COUNT_STREAM} -- and writes its photons ({seed, 0, k, RNG_*_PHOTON}).
+template <class Rule>
+__global__ __launch_bounds__(256) void region_flag_kernel(typename Rule::Params p, HydroDev hy, unsigned *__restrict__ flag, unsigned long long *__restrict__ total)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     unsigned in = 0;
     if (i < hy.M) {
-        in = in_emission_slab(p, load_cell(hy, p.dimensions, i)) ? 1u : 0u;
+        in = in_region<Rule::STRICT_UPPER>(p, load_cell(hy, p.dimensions, i)) ? 1u : 0u;
         flag[i] = in;
     }
     const unsigned long long m = __ballot(in != 0);
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(total, (unsigned long long)__popcll(m));
 }
 
-__global__ __launch_bounds__(256) void cs_shell_write_kernel(CsEmitParams p, HydroDev hy, HydroCols h, const unsigned *__restrict__ flag,
-                                                             const int *__restrict__ start, CsShellCell *__restrict__ out, unsigned *__restrict__ not_converged)
+template <class Rule>
+__global__ __launch_bounds__(256) void region_write_kernel(Rule rule, const unsigned *__restrict__ flag, const int *__restrict__ start,
+                                                           typename Rule::Record *__restrict__ out)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= hy.M || !flag[i]) return;
-    const CellRec c = load_cell(hy, p.dimensions, i);
-    int status;
-    bool bisected;
-    CsShellCell s;
+    if (i >= rule.hy.M || !flag[i]) return;
+    typename Rule::Record s;
     s.cell = i; s.pad = 0;
-    s.integral = qags_planck(10, cs_nu_c(p, hy, h, i), hy.temp[i], status, bisected);                  // :1276
-    s.volume = element_volume(p.dimensions, p.geometry, c);
-    if (status == 2) atomicAdd(not_converged, 1u);                                                     // out of intervals: the host refuses
+    rule.fill(s, i, load_cell(rule.hy, rule.p.dimensions, i));
     out[start[i]] = s;
+}
+
+// The weight search of one list by its workgroup: the total of the region's counts at a weight, the weight x 10 or x 0.5 (list_plan.hpp,
+// weight_search_step) and again, `attempts` times after the first at most.  ok: the total of `attempt` at `weight` was accepted.
+struct PoolSearchLds { unsigned long long sum[4]; int w[4]; double weight; int ok, attempt; };
+struct PoolSearch { bool ok; double weight; int attempt; unsigned long long total; };
+template <class Rule>
+__device__ PoolSearch pool_weight_search(const typename Rule::Record *__restrict__ cells, int n_cells, const RngKey &key, double weight_in, int attempts,
+                                         int min_photons, double max_photons, PoolSearchLds &lds)
+{
+    const int tid = threadIdx.x;
+    if (tid == 0) { lds.weight = weight_in; lds.ok = 0; lds.attempt = 0; }
+    __syncthreads();
+    unsigned long long total = 0;
+    for (int attempt = 0; attempt <= attempts; ++attempt) {
+        const double weight = lds.weight;
+        unsigned long long mine = 0;
+        for (int s = tid; s < n_cells; s += 256) {
+            EventStream rng = keyed_stream(key, (unsigned long long)attempt, (uint32_t)cells[s].cell, Rule::COUNT_STREAM);
+            mine += poisson_count(rng, Rule::record_mean(cells[s], weight));
+        }
+        total = block_sum_256(mine, lds.sum);
+        if (tid == 0) {
+            double next = weight;
+            if (weight_search_step(total, min_photons, max_photons, &next)) { lds.ok = 1; lds.attempt = attempt; }
+            else lds.weight = next;
+        }
+        __syncthreads();
+        if (lds.ok) break;
+    }
+    return PoolSearch{lds.ok != 0, lds.weight, lds.attempt, total};
+}
+
+// photon k -> its cell, s_cell[k]: the accepted attempt's counts again, in cell order (s_w: four words of LDS)
+template <class Rule>
+__device__ void pool_cells_of_photons(const typename Rule::Record *__restrict__ cells, int n_cells, const RngKey &key, double weight, int attempt, int *s_cell,
+                                      int *s_w)
+{
+    int base = 0;
+    for (int c0 = 0; c0 < n_cells; c0 += 256) {
+        const int s = c0 + (int)threadIdx.x;
+        int cnt = 0, cell = -1;
+        if (s < n_cells) {
+            EventStream rng = keyed_stream(key, (unsigned long long)attempt, (uint32_t)cells[s].cell, Rule::COUNT_STREAM);
+            cnt = (int)poisson_count(rng, Rule::record_mean(cells[s], weight));
+            cell = cells[s].cell;
+        }
+        int chunk_total;
+        const int off = block_exclusive_scan_256(cnt, s_w, &chunk_total);
+        for (int j = 0; j < cnt; ++j) s_cell[base + off + j] = cell;
+        base += chunk_total;
+        __syncthreads();
+    }
+}
+
+// (weight_search_step compares (double)total > max_photons and total < (unsigned long long)min_photons where the reference compares ints: the same
+// outcome for every total below 2^53 and every min_photons >= 0, and a total is below 2^31 times the number of cells)
+__global__ __launch_bounds__(256) void inject_pool_kernel(InjectParams p, HydroDev hy, PhotonDev pool, int stride, const InjectSlabCell *__restrict__ slab,
+                                                          int n_slab, PoolInject *lists, int group)
+{
+    __shared__ PoolSearchLds lds;
+    __shared__ int s_cell[POOL_INJECT_CAP];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    PoolInject &L = lists[r];
+    if (!L.inject || L.group != group) return;
+    PhotonDev ph = pool;
+    offset_photons(ph, (size_t)r * (size_t)stride);
+    const RngKey key = {L.seed, L.stream, 0u};
+    const PoolSearch found = pool_weight_search<InjectRule>(slab, n_slab, key, L.weight_in, 200, L.min_photons, (double)L.max_photons, lds);   // mclib.c:87-136
+    if (!found.ok) { if (tid == 0) { L.error = 1; L.n = 0; } return; }
+    const double weight = found.weight;
+    const int n = (int)found.total;
+    if (tid == 0) { L.n = n; L.weight_out = weight; L.error = n == 0 ? 2 : (n > stride || n > POOL_INJECT_CAP ? 3 : 0); }
+    if (n == 0 || n > stride || n > POOL_INJECT_CAP) return;
+    pool_cells_of_photons<InjectRule>(slab, n_slab, key, weight, found.attempt, s_cell, lds.w);
+    ph.n = n;
+    for (int k = tid; k < n; k += 256) inject_one(p, hy, weight, key, k, s_cell[k], ph);
+}
+
+// setNullPhoton (photons.c:210-250) on a fresh slot: -1 / total_optical_depth with 0; every other column is zero already.  (cs_hook_body keeps its own
+// copy of these stores, and cs_emit_one its own copy of inject_one's photon store, on purpose: cs_device.hpp reaches rank_loop_kernel and stays as it is.)
+__device__ __forceinline__ void null_fill_one(const PhotonDev &ph, int i)
+{
+    ph.type[i] = 'N';
+    ph.idx[i] = -1;
+    ph.flags[i] = (unsigned char)FLAG_VALID;
+    ph.ntau[i] = -INFINITY;
 }
 
 constexpr int CS_POOL_EMIT_CAP = 4096;       // pool photons one list may receive in one emission (LDS tables of cells and slots)
 
+// ... and the list's photons go into its null slots in slot order, the list doubling inside its window of the pool when it has none
 __global__ __launch_bounds__(256) void cs_emit_pool_kernel(CsEmitParams p, HydroDev hy, HydroCols h, PhotonDev pool, int stride, RankDesc *desc,
                                                            const CsShellCell *__restrict__ shell, int n_shell, CsPoolEmit *lists, int group)
 {
-    __shared__ unsigned long long s_sum[4];
-    __shared__ int s_w[4];
+    __shared__ PoolSearchLds lds;
     __shared__ int s_cell[CS_POOL_EMIT_CAP], s_slot[CS_POOL_EMIT_CAP];
-    __shared__ double s_weight;
-    __shared__ int s_ok, s_attempt;
     const int r = blockIdx.x, tid = threadIdx.x;
     CsPoolEmit &L = lists[r];
     if (!L.open || L.group != group) return;
@@ -542,59 +558,15 @@ __global__ __launch_bounds__(256) void cs_emit_pool_kernel(CsEmitParams p, Hydro
     offset_photons(ph, (size_t)r * (size_t)stride);
     ph.n = d.len;
     const RngKey key = {L.seed, d.stream, 0u};
-    // ---- :1244-1296: the weight loop
-    if (tid == 0) { s_weight = L.weight_in; s_ok = 0; s_attempt = 0; }
-    __syncthreads();
-    const int min_photons = n_shell > 0 ? 1 : 0;                                          // no cell in the shell: nothing to emit (:1236-1239)
-    unsigned long long total = 0;
-    for (int attempt = 0; attempt <= 400; ++attempt) {
-        const double weight = s_weight;
-        unsigned long long mine = 0;
-        for (int s = tid; s < n_shell; s += 256) {
-            double ph_dens_calc = shell[s].integral;
-            ph_dens_calc *= shell[s].volume / weight;                                      // :1277
-            EventStream rng = keyed_stream(key, (unsigned long long)attempt, (uint32_t)shell[s].cell, RNG_CS_COUNT);
-            const long long k = poisson(rng, ph_dens_calc);
-            mine += (unsigned long long)(k < 0 ? 0 : (k > 0x7fffffffll ? 0x7fffffffll : k));
-        }
-        for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 64);
-        __syncthreads();
-        if ((tid & 63) == 0) s_sum[tid >> 6] = mine;
-        __syncthreads();
-        total = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
-        if (tid == 0) {
-            if ((double)total > L.max_photons) s_weight = weight * 10;
-            else if ((long long)total < min_photons) s_weight = weight * 0.5;
-            else { s_ok = 1; s_attempt = attempt; }
-        }
-        __syncthreads();
-        if (s_ok) break;
-    }
-    if (!s_ok) { if (tid == 0) { L.error = 1; L.n_emit = 0; } return; }
-    const double weight = s_weight;
-    const int attempt = s_attempt, n_emit = (int)total;
+    // ---- :1244-1296: the weight loop.  No cell in the shell: nothing to emit (:1236-1239)
+    const PoolSearch found = pool_weight_search<EmitRule>(shell, n_shell, key, L.weight_in, 400, n_shell > 0 ? 1 : 0, L.max_photons, lds);
+    if (!found.ok) { if (tid == 0) { L.error = 1; L.n_emit = 0; } return; }
+    const double weight = found.weight;
+    const int n_emit = (int)found.total;
     if (tid == 0) { L.n_emit = n_emit; L.weight_out = weight; L.error = 0; }
     if (n_emit == 0) return;
     if (n_emit > CS_POOL_EMIT_CAP) { if (tid == 0) L.error = 4; return; }
-    // ---- photon k -> its cell: the counts of the accepted attempt again, in cell order (:1340-1455)
-    int base = 0;
-    for (int c0 = 0; c0 < n_shell; c0 += 256) {
-        const int s = c0 + tid;
-        int cnt = 0, cell = -1;
-        if (s < n_shell) {
-            double ph_dens_calc = shell[s].integral;
-            ph_dens_calc *= shell[s].volume / weight;
-            EventStream rng = keyed_stream(key, (unsigned long long)attempt, (uint32_t)shell[s].cell, RNG_CS_COUNT);
-            const long long k = poisson(rng, ph_dens_calc);
-            cnt = (int)(k < 0 ? 0 : (k > 0x7fffffffll ? 0x7fffffffll : k));
-            cell = shell[s].cell;
-        }
-        int chunk_total;
-        const int off = block_exclusive_scan_256(cnt, s_w, &chunk_total);
-        for (int j = 0; j < cnt; ++j) s_cell[base + off + j] = cell;
-        base += chunk_total;
-        __syncthreads();
-    }
+    pool_cells_of_photons<EmitRule>(shell, n_shell, key, weight, found.attempt, s_cell, lds.w);                  // :1340-1455
     // ---- addToPhotonList (photons.c:108-208): the null slots in slot order, the list doubled first when it has none
     int n = ph.n, n_null = 0;
     for (int pass = 0; pass < 2; ++pass) {
@@ -603,16 +575,15 @@ __global__ __launch_bounds__(256) void cs_emit_pool_kernel(CsEmitParams p, Hydro
             const int i = c0 + tid;
             const int isn = (i < n && ph.type[i] == 'N') ? 1 : 0;
             int chunk_total;
-            const int off = block_exclusive_scan_256(isn, s_w, &chunk_total);
+            const int off = block_exclusive_scan_256(isn, lds.w, &chunk_total);
             if (isn && n_null + off < n_emit) s_slot[n_null + off] = i;
             n_null += chunk_total;
             __syncthreads();
         }
         if (n_null != 0 || pass == 1) break;
-        const long long cap = n;                                                           // photons.c:112-121
-        const long long new_cap = (cap * 2 > cap + n_emit) ? cap * 2 : cap * (n_emit / cap);
+        const long long new_cap = list_capacity_grown(n, n_emit);                          // photons.c:112-121
         if (new_cap > stride) { if (tid == 0) L.error = 3; return; }
-        for (int i = n + tid; i < (int)new_cap; i += 256) { ph.type[i] = 'N'; ph.idx[i] = -1; ph.flags[i] = (unsigned char)FLAG_VALID; ph.ntau[i] = -INFINITY; }
+        for (int i = n + tid; i < (int)new_cap; i += 256) null_fill_one(ph, i);
         n = (int)new_cap;
         ph.n = n;
         if (tid == 0) desc[r].len = n;
@@ -627,7 +598,11 @@ __global__ __launch_bounds__(256) void cs_emit_pool_kernel(CsEmitParams p, Hydro
     }
 }
 
-
+// The hook of mcrat.c:786-808 after a pass.  If the pass called photonEvent and the photon it reports is a pool photon, that photon
+// becomes a comptonised one and is replaced by a fresh pool photon of its weight in its cell (photonEmitCyclosynch with
+// inject_single_switch = 1, mc_cyclosynch.c:1467-1558, into the list's first null slot, photons.c:139-160), and it is itself moved to
+// a random place in that cell (:1540-1556); then the rebinning trigger of :797-808.  One workgroup; the pending advance must have
+// been applied (flush_kernel) so that the positions are current.  See CsFrame (launch.hpp) for how it parks the loop.
 __global__ __launch_bounds__(256) void cs_replace_kernel(CsEmitParams p, HydroDev hy, HydroCols h, RngKey key, LoopState *st, PhotonDev ph, CsFrame *cf,
                                                          int resume)
 {
@@ -691,16 +666,10 @@ __global__ __launch_bounds__(256) void null_write_kernel(PhotonDev ph, const int
     null_slots[block_start[blockIdx.x] + pos] = i;
 }
 
-// setNullPhoton (photons.c:210-250) on fresh slots
 __global__ __launch_bounds__(256) void null_fill_kernel(PhotonDev ph, int first, int count)
 {
     const int k = blockIdx.x * 256 + threadIdx.x;
-    if (k >= count) return;
-    const int i = first + k;
-    ph.type[i] = 'N';
-    ph.idx[i] = -1;
-    ph.flags[i] = (unsigned char)FLAG_VALID;
-    ph.ntau[i] = -INFINITY;            // -1 / total_optical_depth with 0; every other column is zero already
+    if (k < count) null_fill_one(ph, first + k);
 }
 
 // ---------------------------------------------------------------------------------------------- rebinCyclosynchCompPhotons
@@ -957,21 +926,6 @@ __global__ __launch_bounds__(256) void rebin_pool_range_kernel(PhotonDev pool, i
     if (threadIdx.x == 0) out[blockIdx.x] = q;
 }
 
-// exclusive prefix sums over the workgroup's 256 threads; returns the thread's offset, *total the sum
-__device__ __forceinline__ unsigned block_exclusive_scan_256(unsigned v, unsigned (&s_w)[4], unsigned *total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned inc = v;
-    for (int off = 1; off < 64; off <<= 1) { const unsigned o = __shfl_up(inc, off); if (lane >= off) inc += o; }
-    __syncthreads();                                     // (s_w may still be read from the previous call)
-    if (lane == 63) s_w[wave] = inc;
-    __syncthreads();
-    unsigned base = 0;
-    for (int w = 0; w < wave; ++w) base += s_w[w];
-    *total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-    return base + inc - v;
-}
-
 __global__ __launch_bounds__(256) void rebin_pool_kernel(PhotonDev pool, RebinPoolList *__restrict__ lists, char *__restrict__ scratch)
 {
     __shared__ unsigned s_w[4];
@@ -1117,53 +1071,67 @@ hipError_t launch_cs_replace(const CsEmitParams &p, const HydroDev &hy, const Hy
     return hipGetLastError();
 }
 
-hipError_t launch_inject_slab_flag(const InjectParams &p, const HydroDev &hy, unsigned *flag, unsigned long long *d_total, int *n_slab, hipStream_t stream)
+template <class Rule>
+static hipError_t birth_count(const Rule &rule, double weight, unsigned long long attempt, RngKey key, unsigned *count, unsigned long long *d_total,
+                              hipStream_t stream)
 {
     hipError_t e = hipMemsetAsync(d_total, 0, sizeof(unsigned long long), stream);
     if (e != hipSuccess) return e;
-    inject_slab_flag_kernel<<<dim3((hy.M + 255) / 256), dim3(256), 0, stream>>>(p, hy, flag, d_total);
+    birth_count_kernel<<<dim3((rule.hy.M + 255) / 256), dim3(256), 0, stream>>>(rule, weight, attempt, key, count, d_total);
+    return hipGetLastError();
+}
+hipError_t launch_birth_count(const InjectParams &p, const HydroDev &hy, double ph_weight_adjusted, unsigned long long attempt, RngKey key, unsigned *count,
+                              unsigned long long *d_total, hipStream_t stream)
+{
+    return birth_count(InjectRule{p, hy}, ph_weight_adjusted, attempt, key, count, d_total, stream);
+}
+hipError_t launch_birth_count(const CsEmitParams &p, const HydroDev &hy, const HydroCols &h, double ph_weight_adjusted, unsigned long long attempt, RngKey key,
+                              unsigned *count, unsigned long long *d_total, unsigned *d_flags, hipStream_t stream)
+{
+    return birth_count(EmitRule{p, hy, h, d_flags}, ph_weight_adjusted, attempt, key, count, d_total, stream);
+}
+
+template <class Params>
+hipError_t launch_region_flag(const Params &p, const HydroDev &hy, unsigned *flag, unsigned long long *d_total, int *n_cells, hipStream_t stream)
+{
+    hipError_t e = hipMemsetAsync(d_total, 0, sizeof(unsigned long long), stream);
+    if (e != hipSuccess) return e;
+    region_flag_kernel<typename BirthOf<Params>::Rule><<<dim3((hy.M + 255) / 256), dim3(256), 0, stream>>>(p, hy, flag, d_total);
     unsigned long long total = 0;
     if ((e = hipMemcpyAsync(&total, d_total, sizeof total, hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
     if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
-    *n_slab = (int)total;
+    *n_cells = (int)total;
     return hipGetLastError();
 }
+template hipError_t launch_region_flag<InjectParams>(const InjectParams &, const HydroDev &, unsigned *, unsigned long long *, int *, hipStream_t);
+template hipError_t launch_region_flag<CsEmitParams>(const CsEmitParams &, const HydroDev &, unsigned *, unsigned long long *, int *, hipStream_t);
 
-hipError_t launch_inject_slab_write(const InjectParams &p, const HydroDev &hy, const unsigned *flag, int n_slab, int *start, int *scratch, InjectSlabCell *out,
-                                    hipStream_t stream)
+template <class Rule>
+static hipError_t region_write(const Rule &rule, const unsigned *flag, int n_cells, int *start, int *scratch, typename Rule::Record *out, hipStream_t stream)
 {
-    hipError_t e = launch_exclusive_scan(flag, hy.M, start, scratch, (long long)n_slab, stream);
+    if (n_cells <= 0) return hipSuccess;
+    hipError_t e = launch_exclusive_scan(flag, rule.hy.M, start, scratch, (long long)n_cells, stream);
     if (e != hipSuccess) return e;
-    inject_slab_write_kernel<<<dim3((hy.M + 255) / 256), dim3(256), 0, stream>>>(p, hy, flag, start, out);
+    region_write_kernel<<<dim3((rule.hy.M + 255) / 256), dim3(256), 0, stream>>>(rule, flag, start, out);
     return hipGetLastError();
+}
+hipError_t launch_region_write(const InjectParams &p, const HydroDev &hy, const unsigned *flag, int n_cells, int *start, int *scratch, InjectSlabCell *out,
+                               hipStream_t stream)
+{
+    return region_write(InjectRule{p, hy}, flag, n_cells, start, scratch, out, stream);
+}
+hipError_t launch_region_write(const CsEmitParams &p, const HydroDev &hy, const HydroCols &h, const unsigned *flag, int n_cells, int *start, int *scratch,
+                               CsShellCell *out, unsigned *not_converged, hipStream_t stream)
+{
+    hipError_t e = hipMemsetAsync(not_converged, 0, sizeof(unsigned), stream);
+    if (e != hipSuccess) return e;
+    return region_write(EmitRule{p, hy, h, not_converged}, flag, n_cells, start, scratch, out, stream);
 }
 
 hipError_t launch_inject_pool(const InjectParams &p, const HydroDev &hy, const PhotonDev &pool, int stride, int n_ranks, const InjectSlabCell *slab, int n_slab,
                               PoolInject *lists, int group, hipStream_t stream)
 {
     inject_pool_kernel<<<dim3(n_ranks), dim3(256), 0, stream>>>(p, hy, pool, stride, slab, n_slab, lists, group);
-    return hipGetLastError();
-}
-
-hipError_t launch_cs_shell_flag(const CsEmitParams &p, const HydroDev &hy, unsigned *flag, unsigned long long *d_total, int *n_shell, hipStream_t stream)
-{
-    hipError_t e = hipMemsetAsync(d_total, 0, sizeof(unsigned long long), stream);
-    if (e != hipSuccess) return e;
-    cs_shell_flag_kernel<<<dim3((hy.M + 255) / 256), dim3(256), 0, stream>>>(p, hy, flag, d_total);
-    unsigned long long total = 0;
-    if ((e = hipMemcpyAsync(&total, d_total, sizeof total, hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
-    if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
-    *n_shell = (int)total;
-    return hipGetLastError();
-}
-
-hipError_t launch_cs_shell_write(const CsEmitParams &p, const HydroDev &hy, const HydroCols &h, const unsigned *flag, int n_shell, int *start, int *scratch,
-                                 CsShellCell *out, unsigned *not_converged, hipStream_t stream)
-{
-    hipError_t e = hipMemsetAsync(not_converged, 0, sizeof(unsigned), stream);
-    if (e != hipSuccess) return e;
-    if ((e = launch_exclusive_scan(flag, hy.M, start, scratch, (long long)n_shell, stream)) != hipSuccess) return e;
-    cs_shell_write_kernel<<<dim3((hy.M + 255) / 256), dim3(256), 0, stream>>>(p, hy, h, flag, start, out, not_converged);
     return hipGetLastError();
 }
 
@@ -1178,15 +1146,6 @@ hipError_t launch_cs_replace_pool(const CsEmitParams &p, const HydroDev &hy, con
                                   int n_ranks, RankDesc *desc, CsFrame *frames, hipStream_t stream)
 {
     cs_replace_pool_kernel<<<dim3(n_ranks), dim3(256), 0, stream>>>(p, hy, h, states, pool, stride, desc, frames);
-    return hipGetLastError();
-}
-
-hipError_t launch_cs_emit_count(const CsEmitParams &p, const HydroDev &hy, const HydroCols &h, double ph_weight_adjusted, unsigned long long attempt,
-                                RngKey key, unsigned *count, unsigned long long *d_total, unsigned *d_flags, hipStream_t stream)
-{
-    hipError_t e = hipMemsetAsync(d_total, 0, sizeof(unsigned long long), stream);
-    if (e != hipSuccess) return e;
-    cs_emit_count_kernel<<<dim3((hy.M + 255) / 256), dim3(256), 0, stream>>>(p, hy, h, ph_weight_adjusted, attempt, key, count, d_total, d_flags);
     return hipGetLastError();
 }
 
@@ -1217,15 +1176,6 @@ hipError_t launch_null_fill(const PhotonDev &ph, int first, int count, hipStream
 {
     if (count <= 0) return hipSuccess;
     null_fill_kernel<<<dim3((count + 255) / 256), dim3(256), 0, stream>>>(ph, first, count);
-    return hipGetLastError();
-}
-
-hipError_t launch_inject_count(const InjectParams &p, const HydroDev &hy, double ph_weight_adjusted, unsigned long long attempt, RngKey key,
-                               unsigned *count, unsigned long long *d_total, hipStream_t stream)
-{
-    hipError_t e = hipMemsetAsync(d_total, 0, sizeof(unsigned long long), stream);
-    if (e != hipSuccess) return e;
-    inject_count_kernel<<<dim3((hy.M + 255) / 256), dim3(256), 0, stream>>>(p, hy, ph_weight_adjusted, attempt, key, count, d_total);
     return hipGetLastError();
 }
 

@@ -201,9 +201,10 @@ struct InjectParams {
     double num_dens_coeff;                     // 8.44f / 20.29f widened (mclib.c:23-32)
     int wien;                                  // spect == 'w'
 };
-// Poisson photon count of every cell for one weight (mclib.c:87-136); *total receives the sum
-hipError_t launch_inject_count(const InjectParams &p, const HydroDev &hy, double ph_weight_adjusted, unsigned long long attempt, RngKey key,
-                               unsigned *count, unsigned long long *d_total, hipStream_t stream);
+// Poisson photon count of every cell for one weight (mclib.c:87-136); *total receives the sum.  (The same name takes the pool emission's
+// arguments below: the two births are one kernel over a rule, inject.hip.)
+hipError_t launch_birth_count(const InjectParams &p, const HydroDev &hy, double ph_weight_adjusted, unsigned long long attempt, RngKey key,
+                              unsigned *count, unsigned long long *d_total, hipStream_t stream);
 // the photons themselves (mclib.c:150-296), ordered by cell then draw, into the SoA columns
 hipError_t launch_inject_generate(const InjectParams &p, const HydroDev &hy, double ph_weight_adjusted, RngKey key, const int *start,
                                   const PhotonDev &ph, hipStream_t stream);
@@ -220,9 +221,12 @@ struct alignas(8) PoolInject {
     double weight_out;               // out
     int n, error;                    // out: photons; 0 ok, 1 no weight fits, 2 no photons, 3 more than the list's window (or the kernel's table) holds
 };
-hipError_t launch_inject_slab_flag(const InjectParams &p, const HydroDev &hy, unsigned *flag, unsigned long long *d_total, int *n_slab, hipStream_t stream);   // waits
-hipError_t launch_inject_slab_write(const InjectParams &p, const HydroDev &hy, const unsigned *flag, int n_slab, int *start, int *scratch, InjectSlabCell *out,
-                                    hipStream_t stream);
+// The cells of a region -- Params: InjectParams (the slab) or CsEmitParams (the emission shell, below) -- flagged, flag[i] = 1, and counted; waits.
+template <class Params>
+hipError_t launch_region_flag(const Params &p, const HydroDev &hy, unsigned *flag, unsigned long long *d_total, int *n_cells, hipStream_t stream);
+// ... and, the flags scanned into `start`, their records in cell order (n_cells == 0: nothing to write)
+hipError_t launch_region_write(const InjectParams &p, const HydroDev &hy, const unsigned *flag, int n_cells, int *start, int *scratch, InjectSlabCell *out,
+                               hipStream_t stream);
 hipError_t launch_inject_pool(const InjectParams &p, const HydroDev &hy, const PhotonDev &pool, int stride, int n_ranks, const InjectSlabCell *slab, int n_slab,
                               PoolInject *lists, int group, hipStream_t stream);
 // getHydroData on the device (ingest.hip; mcrat_io.c:1898-1990); SlabDev, ChomboBox and StagePartial: hydro_plan.hpp
@@ -300,8 +304,9 @@ struct CsEmitParams {
     double rmin, rmax, theta_min, theta_max;        // the shell of :1203-1204 and the thread's angle range
 };
 struct CsHookArgs { CsEmitParams p; HydroCols h; };      // (see launch_rank_loop)
-hipError_t launch_cs_emit_count(const CsEmitParams &p, const HydroDev &hy, const HydroCols &h, double ph_weight_adjusted, unsigned long long attempt,
-                                RngKey key, unsigned *count, unsigned long long *d_total, unsigned *d_flags, hipStream_t stream);
+// d_flags[0] counts cells whose integral ran out of intervals, and on attempt 0 [1] the cells of the shell, [2] the cells past QAGS' first rule
+hipError_t launch_birth_count(const CsEmitParams &p, const HydroDev &hy, const HydroCols &h, double ph_weight_adjusted, unsigned long long attempt,
+                              RngKey key, unsigned *count, unsigned long long *d_total, unsigned *d_flags, hipStream_t stream);
 hipError_t launch_cs_emit_generate(const CsEmitParams &p, const HydroDev &hy, const HydroCols &h, double ph_weight_adjusted, RngKey key, const int *start,
                                    int n_emit, const int *null_slots, const PhotonDev &ph, hipStream_t stream);
 // the hook of mcrat.c:786-808 after every pass of a cyclo-synchrotron frame (one workgroup on the context's stream) and the state it
@@ -335,9 +340,9 @@ struct alignas(8) CsPoolEmit {
     int n_emit, error;               // out: photons emitted; 0 ok, 1 no weight fits, 2 fewer null slots than photons, 3 the list would outgrow its
                                      //      window of the pool, 4 more photons than the kernel's tables hold
 };
-hipError_t launch_cs_shell_flag(const CsEmitParams &p, const HydroDev &hy, unsigned *flag, unsigned long long *d_total, int *n_shell, hipStream_t stream);   // waits
-hipError_t launch_cs_shell_write(const CsEmitParams &p, const HydroDev &hy, const HydroCols &h, const unsigned *flag, int n_shell, int *start, int *scratch,
-                                 CsShellCell *out, unsigned *not_converged, hipStream_t stream);
+// the shell's cells: launch_region_flag, then their records; *not_converged: the cells whose integral ran out of intervals (0 for an empty shell)
+hipError_t launch_region_write(const CsEmitParams &p, const HydroDev &hy, const HydroCols &h, const unsigned *flag, int n_cells, int *start, int *scratch,
+                               CsShellCell *out, unsigned *not_converged, hipStream_t stream);
 hipError_t launch_cs_emit_pool(const CsEmitParams &p, const HydroDev &hy, const HydroCols &h, const PhotonDev &pool, int stride, int n_ranks, RankDesc *desc,
                                const CsShellCell *shell, int n_shell, CsPoolEmit *lists, int group, hipStream_t stream);
 // phAbsCyclosynch for the open lists of a rank pool, one workgroup per list (staging.hip)

@@ -8,6 +8,13 @@
 #include <stdio.h>
 #include "device_types.hpp"
 
+// the rules the kernels of inject.hip apply too (weight search, list growth) are host and device functions under hipcc, plain inline ones elsewhere
+#if defined(__HIPCC__)
+#define MCRAT_LIST_HD __host__ __device__
+#else
+#define MCRAT_LIST_HD
+#endif
+
 namespace mcrat {
 
 // ------------------------------------------------------------------ what the kernels and the host share
@@ -141,7 +148,7 @@ inline RadialRange emit_shell_radii(double r_inj, int scatt_frame_number, int in
 
 // One step of the weight search of mclib.c:87-136 and mc_cyclosynch.c:1244-1296: `total` photons were drawn with *weight.  More than max_photons:
 // the weight x 10; fewer than min_photons (>= 0): x 0.5; otherwise the weight is accepted (true).  The caller draws again, up to its own limit.
-inline bool weight_search_step(unsigned long long total, int min_photons, double max_photons, double *weight)
+MCRAT_LIST_HD inline bool weight_search_step(unsigned long long total, int min_photons, double max_photons, double *weight)
 {
     if ((double)total > max_photons) *weight *= 10;
     else if (total < (unsigned long long)min_photons) *weight *= 0.5;
@@ -151,7 +158,7 @@ inline bool weight_search_step(unsigned long long total, int min_photons, double
 
 // addToPhotonList (photons.c:112-121) when the list of `cap` slots has no null slot for the n_add photons: twice the slots if that is room enough,
 // else cap * (n_add / cap) -- the reference's integer division, as it is.
-inline long long list_capacity_grown(long long cap, long long n_add)
+MCRAT_LIST_HD inline long long list_capacity_grown(long long cap, long long n_add)
 {
     return (cap * 2 > cap + n_add) ? cap * 2 : cap * (n_add / cap);
 }

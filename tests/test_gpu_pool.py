@@ -363,6 +363,88 @@ def test_pool_injection_gives_every_list_the_photons_of_its_own_injection(hip):
     pb.close()
 
 
+def _inject_both_ways(hip, specs, slots):
+    """the 384 x 96 2-D spherical grid of the test above in two pools of `slots` slots per list: specs through mcrat_hip_pool_inject_photons in
+    the first, list by list through mcrat_hip_inject_photons on the views of the second -> per pool (pool, views, what each list got: (photons,
+    weight), None for a list that sat out, or (error code, last_error text) where the call refused)"""
+    raw = synth.pluto_raw_grid(synth.TWO, synth.SPHERICAL, (1e11, 0.0), (4e12, 0.6), (384, 96), seed=31, log_axis0=True)
+    jet = hip.Engine.outflow(3, lumi=2e53, theta_j=0.1)
+    fps = 5.0
+    slab = dict(r_inj=1e12, ph_inj_switch=1, min_r=0, max_r=0, min_theta=0, max_theta=0, fps=fps, r0_domain=(1e11, 4e12), r1_domain=(0.0, 0.6),
+                r2_domain=(0.0, 0.0))
+    R = len(specs)
+    out = []
+    for batched in (True, False):
+        pool = hip.Engine(synth.TWO, synth.SPHERICAL, 1)
+        pool.ingest(raw, slab, jet)
+        pool.pool_create(R, slots)
+        views = [pool.pool_rank(r, 70 + r) for r in range(R)]
+        got = [None] * R
+        if batched:                                                         # through the C ABI: the per-list statuses are part of what is compared
+            arr = (hip.PoolInjectList * R)()
+            for r, q in enumerate(specs):
+                if q is not None:
+                    a = arr[r]
+                    a.inject, a.spect, a.min_photons, a.max_photons = 1, q["spect"].encode(), q["min_photons"], q["max_photons"]
+                    a.r_inj, a.ph_weight, a.theta_min, a.theta_max, a.seed = q["r_inj"], q["ph_weight"], q["theta_min"], q["theta_max"], q["seed"]
+            rc = pool.lib.mcrat_hip_pool_inject_photons(pool.ctx, fps, arr)
+            text = pool.lib.mcrat_hip_last_error(pool.ctx).decode()
+            for r, q in enumerate(specs):
+                if q is not None:
+                    got[r] = (arr[r].status, text) if arr[r].status else (arr[r].num_photons, arr[r].ph_weight_adjusted)
+                    views[r].n = arr[r].num_photons if not arr[r].status else 0
+            failed = [arr[r].status for r, q in enumerate(specs) if q is not None and arr[r].status]
+            assert rc == (failed[0] if failed else 0)                       # the call returns the first failing list's code
+        else:
+            for r, q in enumerate(specs):
+                if q is None:
+                    continue
+                n, w = hip.C.c_int(0), hip.C.c_double(0)
+                rc = pool.lib.mcrat_hip_inject_photons(views[r].ctx, q["r_inj"], q["ph_weight"], q["min_photons"], q["max_photons"], q["spect"].encode(),
+                                                       q["theta_min"], q["theta_max"], fps, q["seed"], hip.C.byref(n), hip.C.byref(w))
+                got[r] = (rc, pool.lib.mcrat_hip_last_error(views[r].ctx).decode()) if rc else (n.value, w.value)
+                views[r].n = 0 if rc else n.value
+        out.append((pool, views, got))
+    return out
+
+
+def _assert_lists_equal(specs, a, b, injected):
+    (pa, va, ga), (pb, vb, gb) = a, b
+    assert ga == gb                                                         # counts and adjusted weights, or status and text
+    for r in injected:
+        x, y = va[r].get_photons(), vb[r].get_photons()
+        assert len(x["p0"]) == ga[r][0] and specs[r]["min_photons"] <= ga[r][0] <= specs[r]["max_photons"]
+        for k in x:
+            assert np.array_equal(x[k], y[k], equal_nan=(np.asarray(x[k]).dtype.kind == "f")), (r, k)
+
+
+def test_pool_injection_of_more_photons_than_the_kernels_table_holds(hip):
+    """one list asks for more than POOL_INJECT_CAP = 8192 photons (inject_pool_kernel reports error 3 and the list takes the one-list path), a
+    second stays under the cap in the same call (the kernel path): both equal their one-list injections"""
+    common = dict(r_inj=1e12, ph_weight=1e50, spect="b", theta_min=0.0, theta_max=0.05)
+    specs = [dict(common, min_photons=8200, max_photons=16400, seed=11), dict(common, min_photons=300, max_photons=900, seed=12)]
+    a, b = _inject_both_ways(hip, specs, 20000)
+    assert a[2][0][0] > 8192 and a[2][1][0] <= 900
+    _assert_lists_equal(specs, a, b, [0, 1])
+    a[0].close()
+    b[0].close()
+
+
+def test_pool_injection_into_a_window_smaller_than_min_photons(hip):
+    """one list's window is smaller than its min_photons: status and text are those of the one-list call on the view, and the other lists of
+    the call are still injected.  (A pool of 256 slots per list has windows of 512, mcrat_hip_pool_create rounds up: min_photons is 600.)"""
+    common = dict(r_inj=1e12, spect="b", theta_min=0.0, theta_max=0.05)
+    specs = [dict(common, ph_weight=1e50, min_photons=600, max_photons=1200, seed=11),
+             dict(common, ph_weight=3e50, min_photons=60, max_photons=200, seed=12),
+             dict(common, ph_weight=3e50, min_photons=60, max_photons=200, seed=13)]
+    a, b = _inject_both_ways(hip, specs, 256)
+    assert a[2][0][0] != 0 and "slots per rank" in a[2][0][1]               # refused, and why
+    assert a[0].pool_summaries()[0].list_capacity == 0                      # its window stays empty
+    _assert_lists_equal(specs, a, b, [1, 2])
+    a[0].close()
+    b[0].close()
+
+
 @pytest.mark.parametrize("case", ["2000+5000-cylindrical", "2000+4000-cylindrical-stokes", "3000-spherical-stokes"])
 @pytest.mark.parametrize("threads", ["auto", "256"])
 def test_lists_of_thousands_of_photons_equal_the_oracle(hip, oracle, case, threads, monkeypatch):

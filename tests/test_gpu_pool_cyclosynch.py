@@ -143,6 +143,97 @@ def test_pool_lists_with_the_switch_on_match_the_oracle_list_by_list(hip, oracle
     pool.close()
 
 
+# The side exits of cs_emit_pool_kernel and of pool_emit_cyclosynch (engine.hip).  The batched emission is reached through the whole frame only, so the
+# frame gets a remaining time in which no photon moves by a bit (3e-20 cm) and nothing scatters; what the frame still does after the emission is the
+# absorption that closes it (every pool photon becomes a null slot again), which the one-list side repeats on its view.  Weights: found on the CPU with
+# orc_photonEmitCyclosynch on this mesh (seed 31, stream 0) -- the count's mean times the weight is 1.94e46, the first attempt is accepted in every case:
+# 3.88e42 gives 5099 photons (mean 5000: 10 sigma = 707 inside 4096 .. 6000), 2.58e43 gives 751 (inside 601 .. 899), 1.29e44 gives 150.
+SIDE_EXITS = {
+    # max_photons (rebin_e_perc = 0.1 of it bounds the emission), slots per list, per list: (photons, null slots, ph_weight_suggest, theta_min, theta_max)
+    "table-overflow": (60000, 6600, [(300, 6300, 3.88e42, 0.0, 0.05), (300, 300, 1.29e44, 0.0, 0.05)]),   # list 0: more than CS_POOL_EMIT_CAP = 4096 photons, error 4
+    "no-null-slot-doubles": (2000, 4800, [(300, 0, 1.29e44, 0.0, 0.05)]),                                # the list doubles inside its window, in the kernel
+    "no-null-slot-refused": (20000, 4800, [(300, 0, 2.58e43, 0.0, 0.05)]),                               # list_capacity_grown(300, 751) = 600: 300 null slots for 751 photons
+    "empty-shell": (2000, 4800, [(300, 300, 1e40, 3.0, 3.1)]),                                          # no cell in the angle range
+}
+STILL = 1e-30
+
+
+def _last_error(e):
+    return e.lib.mcrat_hip_last_error(e.ctx).decode()
+
+
+@pytest.mark.parametrize("case", sorted(SIDE_EXITS))
+def test_pool_emission_side_exits_equal_the_one_list_emission_on_a_view(hip, oracle, case):
+    max_photons, slots, lists = SIDE_EXITS[case]
+    frame, ph, cfg = synth.config2(n_photons=300, nzc=8, lumi=3e53)
+    dens = np.ascontiguousarray(frame["dens"])
+    R = len(lists)
+    starts = []
+    for r, (n_ph, n_null, w, tmin, tmax) in enumerate(lists):
+        aos = np.roll(synth.photons_to_aos(ph, oracle.PHOTON_DTYPE), 7 * r)[:n_ph]
+        L, l = oracle.lib(), oracle.PhotonList()                            # (as _start_list: the null slots as setNullPhoton leaves them)
+        L.orc_list_init(C.byref(l))
+        full = np.concatenate([aos, np.repeat(aos[:1], n_null)])
+        assert L.orc_list_set(C.byref(l), full.ctypes.data, len(full)) == 0
+        for i in range(n_ph, n_ph + n_null):
+            assert L.orc_list_set_null(C.byref(l), i) == 0
+        buf = (C.c_char * (l.list_capacity * oracle.PHOTON_DTYPE.itemsize)).from_address(l.photons)
+        starts.append(np.frombuffer(buf, dtype=oracle.PHOTON_DTYPE).copy().astype(hip.PHOTON_DTYPE))
+        L.orc_list_free(C.byref(l))
+    pools = []
+    for batched in (True, False):
+        pool = hip.Engine(cfg["dimensions"], cfg["geometry"], 1, cyclosynchrotron=1)
+        pool.set_hydro(frame)
+        pool.set_hydro_extras(dens, None, None, None)
+        pool.pool_create(R, slots)
+        for r in range(R):
+            pool.pool_rank(r, r).set_photons_aos(starts[r])
+        pools.append(pool)
+    pa, pb = pools
+    args = [dict(seed=31 + r, time_now=0.0, remaining_time=STILL, r_inj=1e12, ph_weight_suggest=w, theta_min=tmin, theta_max=tmax, emit_pool=1,
+                 scatt_frame_number=200, inj_frame_number=200) for r, (n_ph, n_null, w, tmin, tmax) in enumerate(lists)]
+    got_a, got_b, text_a, text_b = None, [], "", ""
+    try:
+        sts, cnts = pa.pool_scatter_frames_cyclosynch(args, max_photons, frame["fps"], b_field_calc=1)
+        got_a = [(cnts[r].num_cyclosynch_ph_emit, cnts[r].pool_weight, cnts[r].integrals_not_converged) for r in range(R)]
+    except hip.McratHipError:
+        text_a = _last_error(pa)
+    before_b = []
+    for r, a in enumerate(args):
+        v = pb.pool_rank(r, r)
+        before_b.append(v.get_photons_aos())
+        try:
+            got_b.append(v.emit_cyclosynch_pool(a["r_inj"], a["ph_weight_suggest"], max_photons, a["theta_min"], a["theta_max"], frame["fps"], a["seed"],
+                                                b_field_calc=1, scatt_frame_number=200, inj_frame_number=200))
+            if got_b[-1][0] > 0:
+                v.absorb_cyclosynch(b_field_calc=1)                        # what closes the frame of a list that emitted
+        except hip.McratHipError:
+            text_b = _last_error(v)
+    print(case, got_a, got_b, repr(text_a), repr(text_b))
+    assert text_a == text_b
+    if case == "no-null-slot-refused":
+        assert "fewer null slots than photons to add" in text_a and got_a is None and got_b == []
+    else:
+        assert text_a == "" and got_a == got_b
+        for r in range(R):
+            a, b = pa.pool_rank(r, r).get_photons_aos(), pb.pool_rank(r, r).get_photons_aos()
+            assert len(a) == len(b), r
+            # every column but the loop's own: the frame's one pass has located the photons, filled in their comoving four-momenta and drawn their
+            # free paths (nearest_block_index, recalc_properties, comv_p0-3, the optical-depth columns); the emission alone has not
+            for f in ("type", "weight", "num_scatt", "p0", "p1", "p2", "p3", "r0", "r1", "r2", "s0", "s1", "s2", "s3"):
+                assert np.array_equal(a[f], b[f], equal_nan=(a[f].dtype.kind == "f")), (r, f)
+    n0, w0 = (got_b[0][0], got_b[0][1]) if got_b else (None, None)
+    if case == "table-overflow":
+        assert 4096 < n0 <= 6000 and 1 <= got_b[1][0] <= 200 and (w0, got_b[1][1]) == (lists[0][2], lists[1][2])
+    elif case == "no-null-slot-doubles":
+        assert 1 <= n0 < 300 and len(pb.pool_rank(0, 0).get_photons_aos()) == 600
+    elif case == "empty-shell":
+        assert (n0, w0) == (0, lists[0][2])
+        assert pb.pool_rank(0, 0).get_photons_aos().tobytes() == before_b[0].tobytes()        # the list untouched
+    pa.close()
+    pb.close()
+
+
 def test_dozens_of_lists_rebinned_in_the_same_frame(hip, oracle, monkeypatch):
     """mc_cyclosynch.c:610-710 for all parked lists of a frame in two launches (engine.hip, pool_rebin_lists; inject.hip, rebin_pool_kernel):
     96 lists, of which more than 64 have their rebinning trigger (mcrat.c:797-808) fire in the same frame, come out bit for bit as when every list is rebinned on its own
