@@ -940,6 +940,71 @@ int mcrat_hip_radiation_field(mcrat_hip_ctx *ctx, const mcrat_hip_ctx *hydro, co
 int mcrat_hip_pool_radiation_field(mcrat_hip_ctx *pool, const mcrat_hip_ctx *hydro, const mcrat_hip_radfield_bins *bins, mcrat_hip_radfield *out);
 int mcrat_hip_radiation_field_path(const mcrat_hip_ctx *ctx);
 
+/* the comoving radiation field: spectra, beaming and Eddington moments in the fluid frame ---
+ * What mcrat_hip_radiation_field locates and boosts, kept: the resident photons located in ONE staged hydro frame, boosted into their cell's frame and
+ * binned by position, fluid-frame energy and fluid-frame direction cosine about the flow.  A slot counts as for mcrat_hip_radiation_field.  For a
+ * counted photon, in exactly this order, in IEEE double with correctly rounded division and square root and without contraction:
+ *     r, mu                 as mcrat_hip_radiation_field has them
+ *     cell                  as mcrat_hip_radiation_field locates it; cell < 0: n_unlocated += 1, the photon is in no bin
+ *     beta[3], g            the cell's velocity at the azimuth of (r0, r1) and its staged Lorentz factor, as mcrat_hip_radiation_field obtains them
+ *     bp    = (beta0*p1 + beta1*p2) + beta2*p3
+ *     e_lab = p0 * C_LIGHT   [erg]
+ *     e     = (g * (p0 - bp)) * C_LIGHT        the energy in the fluid frame [erg]: mcrat_hip_radiation_field's e_comv
+ *     m     = ((p1*r0 + p2*r1) + p3*r2) / (p0 * r)     the lab cosine between the photon's direction and the radial direction
+ *     b2    = (beta0*beta0 + beta1*beta1) + beta2*beta2
+ *     a     = b2 > 0 ? ((bp / b) - b * p0) / (p0 - bp), with b = sqrt(b2)
+ *                    : m
+ *             the cosine, in the fluid frame, between the photon's direction and the flow direction: (p' . beta_hat) / p'0 in closed form, no
+ *             Lorentz factor needed.  A cell at rest has no flow direction and its frame is the lab: the radial cosine.
+ *     a, m  clamped into [-1, 1]; a NaN stays a NaN
+ * Position bin s: mode MCRAT_HIP_COMOVING_CELLS: s = cell, n_s = the frame's num_elements; mode MCRAT_HIP_COMOVING_SHELLS: s = ir * n_mu + imu as
+ * MCRAT_HIP_RADFIELD_SHELLS has it, n_s = n_r * n_mu.  ie and ia: bin k of an axis holds  edges[k] <= x < edges[k + 1]  for x = e and x = a, decided by
+ * comparisons only.  bin = (s * n_e + ie) * n_a + ia.  A located photon outside any axis, or with a coordinate that is not a number, adds to
+ * n_outside and to no bin.  The last a edge must lie above 1 for the forward pole (a == 1) to be counted.
+ * Per bin eight planes of 8 bytes, each [n_s][n_e][n_a]: count (integer), w, we = w*e, wea = (w*e)*a, weaa = ((w*e)*a)*a, we_lab = w*e_lab,
+ * wem = (w*e_lab)*m, wemm = ((w*e_lab)*m)*m; beside them n_observable, n_unlocated, n_outside:
+ * sum(count) + n_unlocated + n_outside == n_observable.  The caller's quotients: J = sum we, H = sum wea, K = sum weaa over the a axis; K / J is the
+ * Eddington factor (1/3 where the field is isotropic in the fluid frame, 1 where it streams) and H / J the mean cosine; the lab analogues about the
+ * radial direction come from the last three planes summed over e and a.
+ * Counts that do not hang on e or a -- n_observable, n_unlocated, the count summed over the e and a axes when their edges cover everything -- are
+ * exact: the same as the same expressions in host code.  e and a are computed from the device's staged operands (the azimuth's reciprocal is the
+ * loop's Newton form, gam is staged), so a photon within rounding of an e or a edge may fall on either side.  The seven sums are added with
+ * floating-point atomics and are NOT bit-reproducible from run to run; each is within (m + 2) * 2^-53 * sum|term| of the exact sum of its bin's m
+ * terms as the device computed them.
+ *   mcrat_hip_comoving_field_bins   n_bins = n_s * n_e * n_a for these arguments -- what the caller's arrays must hold -- after the checks below (it
+ *                                   needs the frame, not photons).
+ *   mcrat_hip_comoving_field        one list: a stand-alone context, or a view of a pool (that list alone).  A pending advance is flushed first.
+ *   mcrat_hip_pool_comoving_field   every list of a pool in one launch; it reads what mcrat_hip_pool_radiation_field reads, a frame selected with
+ *                                   mcrat_hip_pool_select_frame included.
+ *   mcrat_hip_comoving_field_path   how the context's last call accumulated: 1 a copy of the planes per workgroup in LDS, flushed once (SHELLS whose
+ *                                   edges and planes fit); 2 atomics straight into HBM (CELLS always; larger SHELLS); 0 none yet.
+ *                                   MCRAT_HIP_COMOVING_PATH=lds|global in the environment forces one (lds is refused where it cannot be had).
+ * hydro: as for mcrat_hip_radiation_field -- NULL: ctx's own frame; a frame on another context must be on the same device with the same DIMENSIONS
+ * and GEOMETRY.  No photon column changes.
+ * MCRAT_HIP_EINVAL, with its own text in mcrat_hip_last_error, checked in this order: an unknown mode; e_edges or a_edges NULL, SHELLS without r_edges
+ * or mu_edges; a count < 1; n_s * n_e * n_a overflowing an int (CELLS: once the frame is known, behind the checks below); r_edges, mu_edges,
+ * e_edges, a_edges not finite, in that order; then the four not strictly ascending, in that order; more edges than the kernel can stage (about
+ * 10 000 values); MCRAT_HIP_COMOVING_PATH neither lds nor global, lds with CELLS, lds with planes beyond LDS; a hydro context that does not match.
+ * Then MCRAT_HIP_ESTATE: no staged frame; no photons; the pool call on a context that is no pool and the one-list call on a pool.
+ * Both calls synchronise before they return. */
+#define MCRAT_HIP_COMOVING_CELLS 0
+#define MCRAT_HIP_COMOVING_SHELLS 1
+typedef struct mcrat_hip_comoving_bins {      /* inputs, host pointers; CELLS reads neither n_r, r_edges nor n_mu, mu_edges */
+    int mode;
+    int n_r;  const double *r_edges;          /* [n_r + 1] cm */
+    int n_mu; const double *mu_edges;         /* [n_mu + 1] cosines of the polar angle, ascending */
+    int n_e;  const double *e_edges;          /* [n_e + 1] erg, in the fluid frame */
+    int n_a;  const double *a_edges;          /* [n_a + 1] cosines about the flow in the fluid frame, ascending */
+} mcrat_hip_comoving_bins;
+typedef struct mcrat_hip_comoving {           /* outputs: host pointers, each [n_bins] (position-major, then e, then a), any may be NULL; and three counters */
+    long long *count; double *w, *we, *wea, *weaa, *we_lab, *wem, *wemm;
+    long long n_observable, n_unlocated, n_outside;
+} mcrat_hip_comoving;
+int mcrat_hip_comoving_field_bins(mcrat_hip_ctx *ctx, const mcrat_hip_ctx *hydro /* or NULL */, const mcrat_hip_comoving_bins *bins, int *n_bins);
+int mcrat_hip_comoving_field(mcrat_hip_ctx *ctx, const mcrat_hip_ctx *hydro, const mcrat_hip_comoving_bins *bins, mcrat_hip_comoving *out);
+int mcrat_hip_pool_comoving_field(mcrat_hip_ctx *pool, const mcrat_hip_ctx *hydro, const mcrat_hip_comoving_bins *bins, mcrat_hip_comoving *out);
+int mcrat_hip_comoving_field_path(const mcrat_hip_ctx *ctx);
+
 /* sky observers: mock observations from any direction, with images --------------
  * mcrat_hip_observe assumes an axisymmetric outflow: its observers are polar rings.  Here an observer is a direction anywhere on the sky with an
  * acceptance cone about it, the detection time comes from r.n, and the photon's position on the observer's sky plane may be two more axes of the
@@ -996,9 +1061,9 @@ int mcrat_hip_observe_sky_path(const mcrat_hip_ctx *ctx);
 
 /* introspection used by bench.py / tests -------------------------------------- */
 int mcrat_hip_synchronize(mcrat_hip_ctx *ctx);
-/* HBM held by the context: photons, staged frame, cell-lookup grid, loop state and the device blocks of all four analysis products -- observe,
- * observe_sky, sightline_* and radiation_field (the blocks of radiation_field and of observe_sky were left out before the four became one
- * array).  A view holds no analysis block of its own: it uses its pool's, and they count there. */
+/* HBM held by the context: photons, staged frame, cell-lookup grid, loop state and the device blocks of all five analysis products -- observe,
+ * observe_sky, sightline_*, radiation_field and comoving_field (the blocks of radiation_field and of observe_sky were left out before they became
+ * one array).  A view holds no analysis block of its own: it uses its pool's, and they count there. */
 size_t mcrat_hip_device_bytes(const mcrat_hip_ctx *ctx);
 int mcrat_hip_lookup_cell(mcrat_hip_ctx *ctx, int n, const double *a0, const double *a1, const double *a2, int *cell_out); /* device cell search == findContainingBlock geometry.c:350 */
 /* The staged frame's covered-octant table (one int per lookup bucket and octant, bucket-major: the cell that covers the octant, or -1): returns its

@@ -1,7 +1,7 @@
-// bin_accumulate.hpp -- how the binned-sum kernels add: device code, included by observe.hip, sky.hip and radfield.hip and by nothing else.  A bin is
+// bin_accumulate.hpp -- how the binned-sum kernels add: device code, included by observe.hip, sky.hip, radfield.hip and comoving.hip and by nothing else.  A bin is
 // a 64-bit integer count (plane 0) and N double sums (planes 1 .. N); where word `plane` of bin `bin` lies is the caller's address rule `at(plane,
-// bin)`, bound to its accumulator -- plane-major for the observation cube and every LDS copy (PlaneMajor, PlaneBases), plane- or bin-major for the
-// radiation field (radfield_word).  A lane's N values travel as double[N], N a template parameter and every loop over it unrolled: they stay in
+// bin)`, bound to its accumulator -- plane-major for the observation cube, the comoving field and every LDS copy (PlaneMajor, PlaneBases), plane- or
+// bin-major for the radiation field (radfield_word).  A lane's N values travel as double[N], N a template parameter and every loop over it unrolled: they stay in
 // registers.
 //
 // The forms, once each:

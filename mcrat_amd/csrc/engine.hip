@@ -22,6 +22,7 @@
 #include "sky_plan.hpp"
 #include "sightline_plan.hpp"
 #include "radfield_plan.hpp"
+#include "comoving_plan.hpp"
 #include "photon_cols.hpp"
 #include "photon_plan.hpp"
 #include "rng.hpp"
@@ -167,12 +168,13 @@ struct mcrat_hip_ctx {
     static constexpr int RED_BLOCKS = 512;
     // the device blocks of the analysis products, each laid out by its plan header: mcrat_hip_observe (the cube, the per-observer counters and the
     // staged inputs), mcrat_hip_sightline_* (the output block and the caller's rays), mcrat_hip_radiation_field (head, accumulator and staged
-    // edges), mcrat_hip_observe_sky (as observe).  A view uses its pool's (analysis_block).
-    enum AnalysisBlock { BLOCK_OBSERVE = 0, BLOCK_SIGHTLINE, BLOCK_RADFIELD, BLOCK_SKY, N_ANALYSIS_BLOCKS };
+    // edges), mcrat_hip_observe_sky (as observe), mcrat_hip_comoving_field (as radiation_field).  A view uses its pool's (analysis_block).
+    enum AnalysisBlock { BLOCK_OBSERVE = 0, BLOCK_SIGHTLINE, BLOCK_RADFIELD, BLOCK_SKY, BLOCK_COMOVING, N_ANALYSIS_BLOCKS };
     struct DeviceBlock { void *buf = nullptr; size_t bytes = 0; } analysis[N_ANALYSIS_BLOCKS];
     int obs_path = 0;                 // the accumulation path of the last observation (ObservePath)
     int rf_path = 0;                  // the accumulation path of the last radiation field (ObservePath)
     int sky_path = 0;                 // the accumulation path of the last sky observation (ObservePath)
+    int cf_path = 0;                  // the accumulation path of the last comoving field (ObservePath)
 
     // profiling
     std::vector<hipEvent_t> ev;
@@ -4443,6 +4445,107 @@ extern "C" int mcrat_hip_pool_radiation_field(mcrat_hip_ctx *c, const mcrat_hip_
 }
 
 extern "C" int mcrat_hip_radiation_field_path(const mcrat_hip_ctx *c) { return c ? c->rf_path : 0; }
+
+// ---------------------------------------------------------------------------------------------- the comoving radiation field
+// The checks of comoving_plan.hpp on the caller's bins, then the frame, as radfield_prepare: *h is the context whose staged frame the photons are
+// located in, *plan the block for its cells (CELLS: the product of the three axes is checked here, once the cells are known).
+static int comoving_prepare(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_comoving_bins *bins, const mcrat_hip_ctx **h_out, ComovingPlan *plan)
+{
+    ComovingShape shape;
+    ComovingRefusal why = comoving_check(bins->mode, bins->n_r, bins->r_edges, bins->n_mu, bins->mu_edges, bins->n_e, bins->e_edges, bins->n_a, bins->a_edges,
+                                         getenv("MCRAT_HIP_COMOVING_PATH"), &shape);
+    if (why != COMOVING_OK) { c->last_error = comoving_refusal_text(why); return MCRAT_HIP_EINVAL; }
+    const mcrat_hip_ctx *h = hydro ? hydro : c;
+    if (h != c && (h->kc.dimensions != c->kc.dimensions || h->kc.geometry != c->kc.geometry || h->cfg.device != c->cfg.device)) {
+        c->last_error = comoving_refusal_text(COMOVING_HYDRO_MISMATCH);
+        return MCRAT_HIP_EINVAL;
+    }
+    if (!h->have_hydro || h->hy.M <= 0) { c->last_error = "comoving_field: no staged hydro frame"; return MCRAT_HIP_ESTATE; }
+    if ((why = comoving_layout(shape, h->hy.M, plan)) != COMOVING_OK) { c->last_error = comoving_refusal_text(why); return MCRAT_HIP_EINVAL; }
+    *h_out = h;
+    return MCRAT_HIP_OK;
+}
+
+// The n_slots slots of c->ph located in the frame of `hydro`, boosted and summed per bin (comoving_plan.hpp, comoving.hip): one memset, one copy of
+// the edges, one launch, the planes read back.
+static int comoving_run(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_comoving_bins *bins, int n_slots, mcrat_hip_comoving *out)
+{
+    c->cf_path = OBSERVE_PATH_NONE;
+    const mcrat_hip_ctx *h = nullptr;
+    ComovingPlan plan;
+    int rc = comoving_prepare(c, hydro, bins, &h, &plan);
+    if (rc) return rc;
+    if (n_slots <= 0) { c->last_error = "comoving_field: no photons"; return MCRAT_HIP_ESTATE; }
+
+    char *d = nullptr;
+    if ((rc = analysis_block(c, h, mcrat_hip_ctx::BLOCK_COMOVING, plan.total_bytes, &d))) return rc;
+    ComovingDev a{};
+    a.n_slots = n_slots; a.n_r = plan.s.n_r; a.n_mu = plan.s.n_mu; a.n_e = plan.s.n_e; a.n_a = plan.s.n_a; a.n_bins = plan.n_bins;
+    a.staged = reinterpret_cast<const double *>(d + plan.staged_offset);
+    a.head = reinterpret_cast<unsigned long long *>(d);
+    a.acc = reinterpret_cast<double *>(d + COMOVING_ACC_OFFSET);
+    HIPCHK(c, hipMemsetAsync(d, 0, plan.zeroed_bytes, c->stream));
+    std::vector<double> in;
+    if (plan.s.mode == COMOVING_SHELLS) {
+        in.insert(in.end(), bins->r_edges, bins->r_edges + plan.s.n_r + 1);
+        in.insert(in.end(), bins->mu_edges, bins->mu_edges + plan.s.n_mu + 1);
+    }
+    in.insert(in.end(), bins->e_edges, bins->e_edges + plan.s.n_e + 1);
+    in.insert(in.end(), bins->a_edges, bins->a_edges + plan.s.n_a + 1);
+    HIPCHK(c, hipMemcpyAsync(d + plan.staged_offset, in.data(), sizeof(double) * in.size(), hipMemcpyHostToDevice, c->stream));
+    const int cus = device_cus(c);
+    c->prof_step_ms = 0; c->prof_launches = 0;                   // (cfg.profile: the kernel's own duration, mcrat_hip_profile_totals)
+    rc = profiled(c, 1, [&]() -> int {
+        HIPCHK(c, launch_comoving(c->kc, c->ph, h->hy, a, plan, comoving_grid(plan, n_slots, cus), c->stream));
+        return MCRAT_HIP_OK;
+    });
+    if (rc) return rc;
+    const size_t plane = sizeof(double) * (size_t)plan.n_bins;
+    void *planes[COMOVING_PLANES] = {out->count, out->w, out->we, out->wea, out->weaa, out->we_lab, out->wem, out->wemm};
+    static_assert(sizeof(long long) == 8, "the count plane and the counters are read back as they are");
+    for (int k = 0; k < COMOVING_PLANES; ++k)
+        if (planes[k]) HIPCHK(c, hipMemcpyAsync(planes[k], d + plan.planes_offset + plane * (size_t)k, plane, hipMemcpyDeviceToHost, c->stream));
+    long long head[COMOVING_N_SCALARS];
+    HIPCHK(c, hipMemcpyAsync(head, d, sizeof(head), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    out->n_observable = head[RF_N_OBSERVABLE]; out->n_unlocated = head[RF_N_UNLOCATED]; out->n_outside = head[RF_N_OUTSIDE];
+    c->cf_path = plan.s.path;
+    return MCRAT_HIP_OK;
+}
+
+extern "C" int mcrat_hip_comoving_field_bins(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_comoving_bins *bins, int *n_bins)
+{
+    if (!c || !bins || !n_bins) return MCRAT_HIP_EINVAL;
+    const mcrat_hip_ctx *h = nullptr;
+    ComovingPlan plan;
+    int rc = comoving_prepare(c, hydro, bins, &h, &plan);
+    if (rc) return rc;
+    *n_bins = plan.n_bins;
+    return MCRAT_HIP_OK;
+}
+
+extern "C" int mcrat_hip_comoving_field(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_comoving_bins *bins, mcrat_hip_comoving *out)
+{
+    if (!c || !bins || !out) return MCRAT_HIP_EINVAL;
+    if (c->is_pool) { c->last_error = "comoving_field: one list is a stand-alone context or a view of a pool (mcrat_hip_pool_comoving_field takes the pool)"; return MCRAT_HIP_ESTATE; }
+    if (c->have_photons) {
+        int rc = flush_pending(c);
+        if (rc) return rc;
+    }
+    return comoving_run(c, hydro, bins, c->have_photons ? c->ph.n : 0, out);
+}
+
+extern "C" int mcrat_hip_pool_comoving_field(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_comoving_bins *bins, mcrat_hip_comoving *out)
+{
+    if (!c || !bins || !out) return MCRAT_HIP_EINVAL;
+    if (!c->is_pool) { c->last_error = "pool_comoving_field: the context is no rank pool"; return MCRAT_HIP_ESTATE; }
+    // every slot of the pool, as mcrat_hip_pool_radiation_field reads them (a selected capture included)
+    int rc = flush_pending(c);
+    if (rc) return rc;
+    return comoving_run(c, hydro, bins, c->ph.n, out);
+}
+
+extern "C" int mcrat_hip_comoving_field_path(const mcrat_hip_ctx *c) { return c ? c->cf_path : 0; }
 
 extern "C" int mcrat_hip_eval_function(mcrat_hip_ctx *c, int fn, int n, const double *in, double *out, uint64_t seed)
 {

@@ -161,6 +161,18 @@ struct RadfieldDev {
 hipError_t launch_radfield(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, const RadfieldDev &a, const RadfieldPlan &plan, int blocks,
                            hipStream_t stream);
 hipError_t launch_radfield_transpose(const double *records, double *planes, int n_bins, int cus, hipStream_t stream);
+// the comoving radiation field (comoving.hip): the n_slots slots of ph located in the frame hy, boosted into their cell's frame and added per
+// (position, fluid-frame energy, fluid-frame cosine) bin.  Head, accumulator and staged edges are laid out as comoving_plan.hpp says; the caller
+// zeroes head and accumulator and sizes the grid (comoving_grid).
+struct ComovingPlan;
+struct ComovingDev {
+    int n_slots, n_r, n_mu, n_e, n_a, n_bins;
+    const double *staged;                // r_edges [n_r + 1], mu_edges [n_mu + 1] (SHELLS), e_edges [n_e + 1], a_edges [n_a + 1]
+    unsigned long long *head;            // n_observable, n_unlocated, n_outside
+    double *acc;                         // COMOVING_PLANES planes of n_bins words; plane 0 holds 64-bit integer counts
+};
+hipError_t launch_comoving(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, const ComovingDev &a, const ComovingPlan &plan, int blocks,
+                           hipStream_t stream);
 // mock observations from any direction on the sky, with images (sky.hip): the photons binned by observer, detection time, energy and, with image
 // axes (n_x, n_y >= 1; else both 0), sky-plane position in one pass over n_slots slots.  The cube and the staged inputs are laid out as sky_plan.hpp
 // says; clocks as in ObserveDev.  The caller zeroes the cube and the counters and sizes the grid (sky_grid).

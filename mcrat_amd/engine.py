@@ -244,6 +244,23 @@ RADFIELD_CELLS, RADFIELD_SHELLS = 0, 1            # mcrat_hip_radfield_bins.mode
 RADFIELD_PATH_LDS, RADFIELD_PATH_GLOBAL = 1, 2    # mcrat_hip_radiation_field_path
 RADFIELD_PLANES = ("w", "we_lab", "we_comv", "w_nscatt", "w_temp")
 
+
+class ComovingBins(C.Structure):
+    """mcrat_hip_comoving_bins: the binning of a comoving field -- the hydro cells or (r, mu) shells, fluid-frame energy and fluid-frame cosine"""
+    _fields_ = [("mode", C.c_int), ("n_r", C.c_int), ("r_edges", _dp), ("n_mu", C.c_int), ("mu_edges", _dp), ("n_e", C.c_int), ("e_edges", _dp),
+                ("n_a", C.c_int), ("a_edges", _dp)]
+
+
+class Comoving(C.Structure):
+    """mcrat_hip_comoving: the eight planes, each [n_bins], and the three counters"""
+    _fields_ = [("count", C.POINTER(C.c_longlong)), ("w", _dp), ("we", _dp), ("wea", _dp), ("weaa", _dp), ("we_lab", _dp), ("wem", _dp), ("wemm", _dp),
+                ("n_observable", C.c_longlong), ("n_unlocated", C.c_longlong), ("n_outside", C.c_longlong)]
+
+
+COMOVING_CELLS, COMOVING_SHELLS = 0, 1            # mcrat_hip_comoving_bins.mode
+COMOVING_PATH_LDS, COMOVING_PATH_GLOBAL = 1, 2    # mcrat_hip_comoving_field_path
+COMOVING_PLANES = ("w", "we", "wea", "weaa", "we_lab", "wem", "wemm")
+
 SCIENCE, CYLINDRICAL_OUTFLOW, SPHERICAL_OUTFLOW, STRUCTURED_SPHERICAL_OUTFLOW = 0, 1, 2, 3    # SIMULATION_TYPE, mcrat.h:30-33
 
 # every symbol include/mcrat_hip.h declares: (restype, argtypes)
@@ -350,6 +367,10 @@ SYMBOLS = {
     "mcrat_hip_radiation_field": (C.c_int, [_ctx, _ctx, C.POINTER(RadfieldBins), C.POINTER(Radfield)]),
     "mcrat_hip_pool_radiation_field": (C.c_int, [_ctx, _ctx, C.POINTER(RadfieldBins), C.POINTER(Radfield)]),
     "mcrat_hip_radiation_field_path": (C.c_int, [_ctx]),
+    "mcrat_hip_comoving_field_bins": (C.c_int, [_ctx, _ctx, C.POINTER(ComovingBins), _ip]),
+    "mcrat_hip_comoving_field": (C.c_int, [_ctx, _ctx, C.POINTER(ComovingBins), C.POINTER(Comoving)]),
+    "mcrat_hip_pool_comoving_field": (C.c_int, [_ctx, _ctx, C.POINTER(ComovingBins), C.POINTER(Comoving)]),
+    "mcrat_hip_comoving_field_path": (C.c_int, [_ctx]),
     "mcrat_hip_observe_sky": (C.c_int, [_ctx, C.POINTER(SkyObserver), C.c_double, C.POINTER(SkyObservation)]),
     "mcrat_hip_pool_observe_sky": (C.c_int, [_ctx, C.POINTER(SkyObserver), _dp, C.POINTER(SkyObservation)]),
     "mcrat_hip_observe_sky_path": (C.c_int, [_ctx]),
@@ -428,6 +449,29 @@ def shell_edges(r_edges, theta_edges_deg):
     if len(mu) and mu[-1] >= 1.0:
         mu[-1] = np.nextafter(1.0, 2.0)
     return _f8(r_edges).ravel().copy(), mu
+
+
+def cosine_edges(n):
+    """n equal bins over [-1, 1] for the a axis of Engine.comoving_field, the top edge just above 1, as shell_edges closes its axis: a photon
+    along the flow (a == 1) is counted"""
+    a = np.linspace(-1.0, 1.0, int(n) + 1)
+    a[-1] = np.nextafter(1.0, 2.0)
+    return a
+
+
+def eddington_moments(res):
+    """the moment hierarchy per position bin of a comoving field (Engine.comoving_field's dict): J, H, K = we, wea, weaa summed over the energy and
+    cosine axes, the Eddington factor K / J and the mean cosine H / J in the fluid frame about the flow, and the lab analogues about the radial
+    direction J_lab, H_lab, K_lab, K_lab / J_lab, H_lab / J_lab from we_lab, wem, wemm.  NaN where a bin holds no energy."""
+    out = {}
+    for tag, planes in (("", ("we", "wea", "weaa")), ("_lab", ("we_lab", "wem", "wemm"))):
+        j, h, k = (_f8(res[p]).sum(axis=(-2, -1)) for p in planes)
+        out["J" + tag], out["H" + tag], out["K" + tag] = j, h, k
+        for name, num in (("K_over_J", k), ("H_over_J", h)):
+            q = np.full(j.shape, np.nan)
+            np.divide(num, j, out=q, where=j != 0)
+            out[name + tag] = q
+    return out
 
 
 K_B = 1.380658e-16        # erg / K, the reference's value (mclib.c)
@@ -1228,6 +1272,40 @@ class Engine:
     def radiation_field_path(self):
         """how the last radiation field of this context was accumulated: RADFIELD_PATH_LDS, RADFIELD_PATH_GLOBAL, 0: none yet"""
         return int(self.lib.mcrat_hip_radiation_field_path(self.ctx))
+
+    # ---- the comoving radiation field: fluid-frame spectra, beaming and Eddington moments (include/mcrat_hip.h)
+    def _comoving_field(self, call, what, mode, e_edges, a_edges, r_edges, mu_edges, hydro):
+        h = hydro.ctx if hydro is not None else None
+        axes = [_f8(x).ravel() if x is not None else None for x in (r_edges, mu_edges, e_edges, a_edges)]
+        n_ax = [len(x) - 1 if x is not None else 0 for x in axes]
+        ptr = [x.ctypes.data_as(_dp) if x is not None else None for x in axes]
+        bins = ComovingBins(int(mode), n_ax[0], ptr[0], n_ax[1], ptr[1], n_ax[2], ptr[2], n_ax[3], ptr[3])
+        n_bins = C.c_int(0)
+        self._check(self.lib.mcrat_hip_comoving_field_bins(self.ctx, h, C.byref(bins), C.byref(n_bins)), what)
+        per_s = n_ax[2] * n_ax[3]
+        shape = (n_ax[0], n_ax[1], n_ax[2], n_ax[3]) if int(mode) == COMOVING_SHELLS else (n_bins.value // per_s, n_ax[2], n_ax[3])
+        res = {"count": np.zeros(shape, dtype=np.int64)}
+        for k in COMOVING_PLANES:
+            res[k] = np.zeros(shape)
+        out = Comoving(res["count"].ctypes.data_as(C.POINTER(C.c_longlong)), *[res[k].ctypes.data_as(_dp) for k in COMOVING_PLANES])
+        self._check(call(self.ctx, h, C.byref(bins), C.byref(out)), what)
+        res.update(n_observable=int(out.n_observable), n_unlocated=int(out.n_unlocated), n_outside=int(out.n_outside))
+        return res
+
+    def comoving_field(self, mode, e_edges, a_edges, r_edges=None, mu_edges=None, hydro=None):
+        """this list's photons located in the staged frame (hydro: another Engine's), boosted into their cell's frame and binned by position --
+        hydro cell (COMOVING_CELLS) or (r, mu) shell (COMOVING_SHELLS) --, fluid-frame energy [erg] and fluid-frame cosine about the flow
+        (cosine_edges gives a_edges) -> dict of arrays count, w, we, wea, weaa, we_lab, wem, wemm -- (M, n_e, n_a) for CELLS, (n_r, n_mu, n_e, n_a)
+        for SHELLS -- and the counters n_observable, n_unlocated, n_outside (mcrat_hip_comoving_field); eddington_moments takes the dict"""
+        return self._comoving_field(self.lib.mcrat_hip_comoving_field, "comoving_field", mode, e_edges, a_edges, r_edges, mu_edges, hydro)
+
+    def pool_comoving_field(self, mode, e_edges, a_edges, r_edges=None, mu_edges=None, hydro=None):
+        """every list of the pool in one launch (mcrat_hip_pool_comoving_field)"""
+        return self._comoving_field(self.lib.mcrat_hip_pool_comoving_field, "pool_comoving_field", mode, e_edges, a_edges, r_edges, mu_edges, hydro)
+
+    def comoving_field_path(self):
+        """how the last comoving field of this context was accumulated: COMOVING_PATH_LDS, COMOVING_PATH_GLOBAL, 0: none yet"""
+        return int(self.lib.mcrat_hip_comoving_field_path(self.ctx))
 
     def synchronize(self):
         self._check(self.lib.mcrat_hip_synchronize(self.ctx), "synchronize")
