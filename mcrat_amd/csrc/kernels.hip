@@ -23,6 +23,7 @@
 #include "sc_exchange.hpp"
 #include "physics.hpp"
 #include "photon_cols.hpp"
+#include "photon_plan.hpp"
 #include "rng.hpp"
 #include "cs_device.hpp"
 
@@ -1186,11 +1187,11 @@ __device__ __attribute__((noinline)) void copy_list_columns(double *r0, unsigned
 // the LDS copy, every other column (and the type) to the live lists.  The live copy of the LDS columns is not written: nobody reads it during the
 // frame (the accessors go to LDS) and the loop's epilogue stores all of them when the launch leaves the list, finished or not.  As copy_list_columns:
 // all of a slot's loads in flight before its first store, and a function of its own for the same reason.
-template <unsigned MASK>
+template <unsigned MASK, int PITCH>
 __device__ __attribute__((noinline)) void restore_list_columns_lds(double *r0, unsigned col_stride, int *idx, unsigned char *flags, char *type, int base,
-                                                                   int n, long long from, unsigned char *lds, int lds_slots, int tid, int block)
+                                                                   int n, long long from, unsigned char *lds, int tid, int block)
 {
-    using Cols = ListCols<MASK>;
+    using Cols = ListCols<MASK, PITCH>;
     static_assert((MASK & COLBIT_IDX) && (MASK & COLBIT_FLAGS), "idx and flags are among the LDS columns");
     typedef __attribute__((address_space(3))) unsigned char *LdsBytes;
     typedef __attribute__((address_space(3))) double *LdsDoubles;
@@ -1207,11 +1208,11 @@ __device__ __attribute__((noinline)) void restore_list_columns_lds(double *r0, u
         const char ct = *(reinterpret_cast<const char *>(type + i) + from);
 #pragma unroll
         for (int k = 0; k < N_DOUBLE_COLS; ++k) {
-            if (Cols::in_lds(k)) ((LdsDoubles)l)[Cols::lds_pos(k) * lds_slots + il] = v[k];
+            if (Cols::in_lds(k)) ((LdsDoubles)l)[Cols::lds_pos(k) * PITCH + il] = v[k];
             else r0[(size_t)k * col_stride + i] = v[k];
         }
-        ((LdsInts)(l + Cols::lds_idx_bytes(lds_slots)))[il] = ci;
-        (l + Cols::lds_flags_bytes(lds_slots))[il] = cf;
+        ((LdsInts)(l + Cols::lds_idx_bytes))[il] = ci;
+        (l + Cols::lds_flags_bytes)[il] = cf;
         type[i] = ct;
     }
 }
@@ -1269,8 +1270,7 @@ template <int DIMS, int GEOM, bool STOKES, bool RESIDENT, int RANK_BLOCK, bool F
 // (one wavefront per SIMD for the small-list builds -- up to 512 registers, spills to AGPRs, no scratch -- measured slower: cfg5's 64-thread lists
 // frac 0.394 -> 0.365, cfg3's 128-thread lists 0.32 -> 0.21: the second wavefront hides more latency than the scratch traffic costs)
 __global__ __launch_bounds__(RANK_BLOCK, RANK_WAVES_PER_SIMD) void rank_loop_kernel(PhotonDev gph, HydroDev hy_arg, LoopState *states, RngKey key,
-                                                                std::conditional_t<TAPE, TapeLayout, RankLayout> lay, long long max_passes,
-                                                                int lds_slots)
+                                                                std::conditional_t<TAPE, TapeLayout, RankLayout> lay, long long max_passes)
 {
     constexpr int EVENT_BLOCK = RANK_BLOCK;                    // (shadows the event kernel's block size inside this kernel)
 #ifndef RANK_NS_SPHERICAL
@@ -1278,7 +1278,7 @@ __global__ __launch_bounds__(RANK_BLOCK, RANK_WAVES_PER_SIMD) void rank_loop_ker
 #endif
     constexpr int RANK_NS_QUEUE = (GEOM == GEOM_SPHERICAL) ? RANK_NS_SPHERICAL : 4;   // slots a thread takes through phase 1 together (queue form)
     constexpr int RANK_QCAP = 4 * RANK_BLOCK;                  // slots per chunk = capacity of the slow-path queue
-    extern __shared__ __align__(16) unsigned char s_dyn[];     // the list's r and -1/tau columns when it fits (lds_slots >= n)
+    extern __shared__ __align__(16) unsigned char s_dyn[];     // the list's per-pass columns when it fits (RESIDENT), rank_lds_limit slots apart
     __shared__ LoopState st;
     __shared__ EventSharedT<RANK_BLOCK> sh;
     __shared__ int s_qn, s_sln, s_nrel, s_hook, s_len, s_item, s_ndefer;
@@ -1366,7 +1366,7 @@ __global__ __launch_bounds__(RANK_BLOCK, RANK_WAVES_PER_SIMD) void rank_loop_ker
         if constexpr (QUEUE && RESIDENT && RANK_BLOCK == 256) lean_restored = lay.cs == nullptr;
 #endif
         if (lean_restored) {
-            restore_list_columns_lds<LIST_MASK_FULL>(gph.r0, gph.col_stride, gph.idx, gph.flags, gph.type, base, n, lay.fq.snap_delta, s_dyn, lds_slots, tid, RANK_BLOCK);
+            restore_list_columns_lds<LIST_MASK_FULL, rank_lds_limit(RANK_BLOCK)>(gph.r0, gph.col_stride, gph.idx, gph.flags, gph.type, base, n, lay.fq.snap_delta, s_dyn, tid, RANK_BLOCK);
         } else {
             copy_list_columns(gph.r0, gph.col_stride, gph.idx, gph.flags, gph.type, base, n, lay.fq.snap_delta, 0, tid, RANK_BLOCK);
             __syncthreads();
@@ -1413,9 +1413,9 @@ __global__ __launch_bounds__(RANK_BLOCK, RANK_WAVES_PER_SIMD) void rank_loop_ker
     // address LDS and the accesses compile to ds_read / ds_write instead of flat loads.)
     constexpr bool FULL_HOT = RANK_BLOCK == 256;            // (512 threads: long lists, one per CU -- r and -1/tau at 32 B per slot reach 4096 slots)
     constexpr unsigned LDS_MASK = RESIDENT ? (FULL_HOT ? LIST_MASK_FULL : LIST_MASK_SMALL) : 0u;
-    using Cols = ListCols<LDS_MASK>;
-    static_assert(Cols::lds_bytes_per_slot == (RESIDENT ? (size_t)rank_lds_bytes_per_slot(RANK_BLOCK) : 0), "launch_rank_loop sizes the dynamic LDS with this");
-    const Cols ph(gph, RESIDENT ? s_dyn : nullptr, lds_slots, base);
+    using Cols = ListCols<LDS_MASK, RESIDENT ? rank_lds_limit(RANK_BLOCK) : 0>;      // (the columns' pitch in LDS: the form's slot limit, a constant)
+    static_assert(Cols::lds_bytes_per_slot == (RESIDENT ? (size_t)rank_lds_bytes_per_slot(RANK_BLOCK) : 0), "rank_form_resolve sizes the dynamic LDS (lds_bytes) with this");
+    const Cols ph(gph, RESIDENT ? s_dyn : nullptr, base);
     if constexpr (RESIDENT) {
         if (!lean_restored) {                                // (a lean restore has filled the LDS copy; the barrier behind the first draws covers it)
             for (int il = tid; il < n; il += EVENT_BLOCK) {
@@ -2577,6 +2577,7 @@ static bool with_rank_kernel(const RankForm &w, F &&f)
 static hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, const RankLaunch &rl,
                                    hipStream_t stream)
 {
+    if (photon_addressing(ph.col_stride) != PHOTON_ADDR_BYTE_OFFSET) return hipErrorInvalidValue;   // (no block that photon_layout lays out: photon_plan.hpp)
     RankLayout lay = {rl.n_ranks, rl.rank_stride, ph.n, rl.desc, rl.cs, rl.hook, FrameQueueDev{}};
     const bool queued = rank_launch_queued(rl);
     if (queued) {
@@ -2591,13 +2592,13 @@ static hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, 
         launched = with_rank_kernel<DV, GV>(plan.form, [&](auto kernel) {
             const int grid = rank_launch_grid(reinterpret_cast<const void *>(kernel), rl, plan);
             if (grid < 0) { lds_refused = true; return; }
-            kernel<<<dim3(grid), dim3(plan.form.threads), plan.dyn_bytes, stream>>>(ph, hy, states, key, lay, rl.max_passes, plan.lds_slots);
+            kernel<<<dim3(grid), dim3(plan.form.threads), plan.lds_bytes, stream>>>(ph, hy, states, key, lay, rl.max_passes);
         });
         if (lds_refused) {             // the runtime refuses the LDS: the lists simply stay in global memory (a queue launch has no such build)
             RankForm global = plan.form;
             global.resident = false;
             launched = with_rank_kernel<DV, GV>(global, [&](auto kernel) {
-                kernel<<<dim3(rl.n_ranks), dim3(global.threads), 0, stream>>>(ph, hy, states, key, lay, rl.max_passes, 0);
+                kernel<<<dim3(rl.n_ranks), dim3(global.threads), 0, stream>>>(ph, hy, states, key, lay, rl.max_passes);
             });
         }
     });
@@ -2609,7 +2610,7 @@ static hipError_t launch_rank_loop(const KernelConfig &kc, const PhotonDev &ph, 
 static hipError_t launch_rank_loop_tape(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, LoopState *states, RngKey key, int n_ranks, int rank_stride,
                                  const RankDesc *desc, const double *u, TapeList *tapes, long long max_passes, hipStream_t stream)
 {
-    if (!desc || !u || !tapes) return hipErrorInvalidValue;
+    if (!desc || !u || !tapes || photon_addressing(ph.col_stride) != PHOTON_ADDR_BYTE_OFFSET) return hipErrorInvalidValue;
     TapeLayout lay;
     static_cast<RankLayout &>(lay) = RankLayout{n_ranks, rank_stride, ph.n, desc, nullptr, nullptr, FrameQueueDev{}};
     lay.tape_u = u;
@@ -2617,8 +2618,8 @@ static hipError_t launch_rank_loop_tape(const KernelConfig &kc, const PhotonDev 
     return dispatch(kc, [&](auto D, auto G) {
         constexpr int DV = decltype(D)::value, GV = decltype(G)::value;
         static_assert(rank_build_exists(GV, TABLE_MODE, false, 256, false, false, false, true), "the tape build");
-        if (kc.stokes) rank_loop_kernel<DV, GV, true, false, 256, false, false, false, true><<<dim3(n_ranks), dim3(256), 0, stream>>>(ph, hy, states, key, lay, max_passes, 0);
-        else rank_loop_kernel<DV, GV, false, false, 256, false, false, false, true><<<dim3(n_ranks), dim3(256), 0, stream>>>(ph, hy, states, key, lay, max_passes, 0);
+        if (kc.stokes) rank_loop_kernel<DV, GV, true, false, 256, false, false, false, true><<<dim3(n_ranks), dim3(256), 0, stream>>>(ph, hy, states, key, lay, max_passes);
+        else rank_loop_kernel<DV, GV, false, false, 256, false, false, false, true><<<dim3(n_ranks), dim3(256), 0, stream>>>(ph, hy, states, key, lay, max_passes);
     });
 }
 

@@ -10,6 +10,12 @@
 //               Round 2 passed 27 pointers, aimed a second set of 27 at LDS, and the compiler kept 250-850 of those scalars spilled in
 //               vector-register lanes -- one v_readlane per use, 11 % of the kernel's instructions; a base, a stride and an LDS
 //               offset stay in a handful of scalar registers.
+//               A global column is addressed as a wave-uniform 64-bit base, base + k * stride (scalar arithmetic; the compiler keeps the bases it
+//               hoists spilled in lanes, two v_readlane per use -- forming them at each use measured slower), plus
+//               the slot's zero-extended 32-bit BYTE offset, i * 8: the offset is one shift per slot whatever the number of columns touched, and the
+//               pair is the scalar-base form of global_load / global_store.  (Before: k * stride + i per column in 32 bits, then a 64-bit shift and
+//               add per lane -- three vector instructions of address arithmetic per access.)  The offset needs n_pad * 8 < 2^32
+//               (photon_plan.hpp, photon_addressing), which every block that photon_layout lays out meets; a launch checks it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "device_types.hpp"
@@ -42,68 +48,79 @@ struct PtrCols {
     __device__ __forceinline__ char &type(int i) const { return d.type[i]; }
 };
 
-// MASK: the columns kept in LDS for the list [first, first + lds_slots): bit k = double column k, COLBIT_IDX, COLBIT_FLAGS.
-// LDS layout: the masked double columns in column order, lds_slots doubles each, then idx (ints), then flags (bytes).
-template <unsigned MASK>
+// MASK: the columns kept in LDS for the list [first, first + PITCH): bit k = double column k, COLBIT_IDX, COLBIT_FLAGS.
+// LDS layout: the masked double columns in column order, PITCH doubles each, then idx (PITCH ints), then flags (bytes).  PITCH is the slot limit of
+// the launch form (rank_form_plan.hpp, rank_lds_limit), a compile-time constant: a slot's r, u, -1/tau, idx and flags are one LDS address per element
+// width plus immediate offsets (seven double columns of 1088 slots end below the 64 KB a DS immediate reaches).
+template <unsigned MASK, int PITCH>
 struct ListCols {
+    static_assert((MASK == 0) == (PITCH == 0), "a pitch for the LDS columns, none without them");
     double *base;                // column 0 (r0) of the context; column k is base + k * stride
     unsigned stride;             // in doubles
     int *g_idx;
     unsigned char *g_flags;
     char *g_type;
     unsigned char *lds;          // the list's LDS copy (nullptr when MASK == 0)
-    int lds_slots;
     int first;                   // the list's first slot
     int n, n_pad;
 
     static constexpr int n_lds_doubles = __builtin_popcount(MASK & 0xffffffu);
     static constexpr size_t lds_bytes_per_slot = (size_t)n_lds_doubles * sizeof(double) + ((MASK & COLBIT_IDX) ? sizeof(int) : 0) + ((MASK & COLBIT_FLAGS) ? 1 : 0);
 
-    __device__ __forceinline__ ListCols(const PhotonDev &p, unsigned char *lds_, int lds_slots_, int first_)
-        : base(p.r0), stride(p.col_stride), g_idx(p.idx), g_flags(p.flags), g_type(p.type), lds(lds_), lds_slots(lds_slots_), first(first_), n(p.n), n_pad(p.n_pad) {}
+    __device__ __forceinline__ ListCols(const PhotonDev &p, unsigned char *lds_, int first_)
+        : base(p.r0), stride(p.col_stride), g_idx(p.idx), g_flags(p.flags), g_type(p.type), lds(lds_), first(first_), n(p.n), n_pad(p.n_pad) {}
 
+    // Element i of a global column of T that starts at `col` (wave-uniform): col + zext32(i * sizeof(T)).  The offset passes through an empty asm
+    // (no instruction; TAG keeps those of different columns apart; not volatile, so identical copies of one column's may be merged, which changes
+    // no result) so that the 64-bit sum is formed in the block of the access, where instruction selection can take the pair as scalar base +
+    // vector offset; summed once in a dominating block it is a 64-bit vector address again.  That selection is this compiler's behaviour, not a
+    // guarantee of the language: the results do not depend on it, and whether the accesses carry a scalar base is checked by reading the assembly
+    // (tools/isa_loops.py's dump; profiles/column_addressing_before_after.txt), by no test.
+    template <int TAG, class T>
+    static __device__ __forceinline__ T &at(T *col, int i)
+    {
+        unsigned off = (unsigned)i * (unsigned)sizeof(T);
+        asm("" : "+v"(off) : "n"(TAG));
+        return *reinterpret_cast<T *>(reinterpret_cast<unsigned char *>(col) + (size_t)off);
+    }
+    enum { TAG_IDX = 100, TAG_FLAGS, TAG_TYPE };
+    // the global copy of a column, whatever the mask (load into / write back from LDS)
+    template <int K>
+    __device__ __forceinline__ double &gcol(int i) const { return at<K>(base + (size_t)K * stride, i); }
     template <int K>
     __device__ __forceinline__ double &dcol(int i) const
     {
-        if constexpr ((MASK >> K) & 1u) {
-            constexpr int pos = __builtin_popcount(MASK & ((1u << K) - 1u));
-            return reinterpret_cast<double *>(lds)[pos * lds_slots + (i - first)];
-        } else {
-            return base[(unsigned)K * stride + (unsigned)i];     // (32-bit index arithmetic: 24 * stride < 2^32, alloc_photons)
-        }
+        if constexpr ((MASK >> K) & 1u) return reinterpret_cast<double *>(lds)[lds_pos(K) * PITCH + (i - first)];
+        else return gcol<K>(i);
     }
-    // the global copy of a column, whatever the mask (load into / write back from LDS)
-    template <int K>
-    __device__ __forceinline__ double &gcol(int i) const { return base[(unsigned)K * stride + (unsigned)i]; }
     template <int K>
     static constexpr bool in_lds() { return ((MASK >> K) & 1u) != 0; }
     // the LDS layout by itself, for code that fills the copy without an accessor (restore_list_columns_lds, kernels.hip): double column k sits
-    // lds_pos(k) * lds_slots doubles in, the idx column lds_idx_bytes(lds_slots) bytes, the flags lds_flags_bytes(lds_slots) bytes
+    // lds_pos(k) * PITCH doubles in, the idx column lds_idx_bytes bytes, the flags lds_flags_bytes bytes
     static constexpr bool in_lds(int k) { return ((MASK >> k) & 1u) != 0; }
     static constexpr int lds_pos(int k) { return __builtin_popcount(MASK & ((1u << k) - 1u)); }
-    static constexpr size_t lds_idx_bytes(int slots) { return (size_t)n_lds_doubles * slots * sizeof(double); }
-    static constexpr size_t lds_flags_bytes(int slots) { return lds_idx_bytes(slots) + ((MASK & COLBIT_IDX) ? (size_t)slots * sizeof(int) : 0); }
+    static constexpr size_t lds_idx_bytes = (size_t)n_lds_doubles * PITCH * sizeof(double);
+    static constexpr size_t lds_flags_bytes = lds_idx_bytes + ((MASK & COLBIT_IDX) ? (size_t)PITCH * sizeof(int) : 0);
 
 #define MCRAT_X(name, K) __device__ __forceinline__ double &name(int i) const { return dcol<K>(i); }
     MCRAT_DOUBLE_COLS(MCRAT_X)
 #undef MCRAT_X
     __device__ __forceinline__ int &idx(int i) const
     {
-        if constexpr ((MASK & COLBIT_IDX) != 0) return reinterpret_cast<int *>(reinterpret_cast<double *>(lds) + n_lds_doubles * lds_slots)[i - first];
-        else return g_idx[i];
+        if constexpr ((MASK & COLBIT_IDX) != 0) return reinterpret_cast<int *>(lds + lds_idx_bytes)[i - first];
+        else return at<TAG_IDX>(g_idx, i);
     }
     __device__ __forceinline__ unsigned char &flags(int i) const
     {
-        if constexpr ((MASK & COLBIT_FLAGS) != 0)
-            return (lds + (size_t)n_lds_doubles * lds_slots * sizeof(double) + ((MASK & COLBIT_IDX) ? (size_t)lds_slots * sizeof(int) : 0))[i - first];
-        else return g_flags[i];
+        if constexpr ((MASK & COLBIT_FLAGS) != 0) return (lds + lds_flags_bytes)[i - first];
+        else return at<TAG_FLAGS>(g_flags, i);
     }
-    __device__ __forceinline__ int &g_idx_at(int i) const { return g_idx[i]; }
-    __device__ __forceinline__ unsigned char &g_flags_at(int i) const { return g_flags[i]; }
-    __device__ __forceinline__ char &type(int i) const { return g_type[i]; }
+    __device__ __forceinline__ int &g_idx_at(int i) const { return at<TAG_IDX>(g_idx, i); }
+    __device__ __forceinline__ unsigned char &g_flags_at(int i) const { return at<TAG_FLAGS>(g_flags, i); }
+    __device__ __forceinline__ char &type(int i) const { return at<TAG_TYPE>(g_type, i); }
     // scratch column behind the 24 (engine.hip, alloc_photons): log(u+) of the slot's free-path draw of the NEXT pass, written by the
     // wavefronts that sit out the event walk (rank_loop_kernel)
-    __device__ __forceinline__ double &draw_log(int i) const { return base[(unsigned)N_DOUBLE_COLS * stride + (unsigned)i]; }
+    __device__ __forceinline__ double &draw_log(int i) const { return gcol<N_DOUBLE_COLS>(i); }
 };
 
 // the per-pass columns a list keeps in LDS: 256-thread lists all of them (61 B per slot), 128- and 64-thread lists r and -1/tau (32 B)

@@ -73,6 +73,15 @@ inline PhotonLayoutStatus photon_layout(int n, PhotonLayout *l)
     return PHOTON_LAYOUT_OK;
 }
 
+// How the loop kernel reaches slot i of a global column (photon_cols.hpp, ListCols): as the column's wave-uniform base plus the slot's zero-extended
+// 32-bit BYTE offset, i * 8, where every slot's offset fits -- n_pad * 8 < 2^32, n_pad the capacity of the block the columns lie in -- and as the
+// 32-bit index k * col_stride + i otherwise.  photon_layout's own bound is the tighter one (25 columns against 8 bytes), so every block it lays out has
+// byte offsets, and the loop kernels are built with them only: PHOTON_ADDR_INDEX names the accessor they had before, of which no build exists, so a
+// launch asks (kernels.hip, launch_rank_loop: the accessor's precondition, checked where the kernel is started) and refuses a block that has none.
+enum PhotonAddressing { PHOTON_ADDR_INDEX = 0, PHOTON_ADDR_BYTE_OFFSET = 1 };
+constexpr PhotonAddressing photon_addressing(size_t n_pad) { return n_pad * sizeof(double) <= 0xffffffffull ? PHOTON_ADDR_BYTE_OFFSET : PHOTON_ADDR_INDEX; }
+static_assert(photon_addressing(0xffffffffull / N_BLOCK_COLS) == PHOTON_ADDR_BYTE_OFFSET, "a block photon_layout accepts has 32-bit byte offsets");
+
 // the block at `base` as the kernels' PhotonDev, for a list of n slots
 inline PhotonDev bind_photons(const PhotonLayout &l, void *base, int n)
 {

@@ -15,6 +15,17 @@ constexpr int RANK_COLUMNS_GLOBAL = 1 << 30;      // longest_list of lists that 
 // Bytes of LDS per slot of a list whose per-pass columns are resident: with 256 threads r, u, -1/tau, idx and the flag byte; otherwise only r and
 // -1/tau (idx, flags and u stay in HBM/L2).  rank_loop_kernel asserts that its column layout (Cols::lds_bytes_per_slot) says the same.
 constexpr int rank_lds_bytes_per_slot(int block) { return block == 256 ? 7 * (int)sizeof(double) + (int)sizeof(int) + 1 : 4 * (int)sizeof(double); }
+// The longest list whose per-pass columns go to LDS, which is also the PITCH of the LDS copy's columns -- a constant of the build, so that the kernel
+// reaches a slot's columns through immediate offsets (photon_cols.hpp, ListCols) -- and therefore what every resident launch asks for:
+//   256 threads   two lists per CU: 13 KB of static LDS and 61 B per slot each within 160 KB -> 1088 slots (2 x (13 024 + 66 368) = 158 784 B)
+//   128 threads   four per CU: 7 KB of static LDS and 32 B per slot each: 1024 slots
+//   512 threads   lists of thousands of photons, one list per CU: 27 KB of static LDS and 32 B per slot within 160 KB -> 4096 slots
+constexpr int rank_lds_limit(int block) { return block == 128 ? 1024 : (block == 512 ? 4096 : 1088); }
+// (static LDS of the resident builds: 13 024 / 6 736 / 25 616 B at 256 / 128 / 512 threads, the same in every such instantiation, DIRECT and TABLE --
+// profiles/column_addressing_kernel_resources.txt; the compiler's occupancy figure knows nothing of the dynamic part, this does)
+static_assert(2 * (13024 + rank_lds_limit(256) * rank_lds_bytes_per_slot(256)) <= 160 * 1024 &&
+              4 * (6736 + rank_lds_limit(128) * rank_lds_bytes_per_slot(128)) <= 160 * 1024 &&
+              25616 + rank_lds_limit(512) * rank_lds_bytes_per_slot(512) <= 160 * 1024, "the lists per CU of each form fit the CU's LDS at the full pitch");
 
 // Which builds of rank_loop_kernel exist -- per (DIMS, GEOM, STOKES) and TAU_CALCULATION -- and why not the others (456 instantiations, 53 MB of
 // device code, minutes per translation unit; every form costs 36 of them):
@@ -53,25 +64,25 @@ struct RankFormRequest {
 // ... and what it gets
 struct RankFormPlan {
     RankForm form;
-    int lds_slots;        // slots of the per-pass columns in LDS (0: in HBM/L2)
-    size_t dyn_bytes;     // the launch's dynamic LDS
+    int lds_slots;        // slots the lists occupy of the per-pass columns in LDS (0: in HBM/L2)
+    size_t dyn_bytes;     // ... and the bytes of LDS those slots hold: what a resident list copies in and out
     bool no_queue_build;  // a queued request whose form has no queue build: the plan runs frame by frame
+    size_t lds_bytes;     // the launch's dynamic LDS: the columns lie rank_lds_limit slots apart whatever the lists' length, so the limit's bytes
 };
 inline RankFormPlan rank_form_resolve(const RankFormRequest &q)
 {
-    RankFormPlan p{RankForm{q.stokes, false, 256, false, q.hook, q.queued}, 0, 0, false};
+    RankFormPlan p{RankForm{q.stokes, false, 256, false, q.hook, q.queued}, 0, 0, false, 0};
     // threads per list: an unknown count runs 256 (64 is known with the hook only, 512 without it only)
     const int block = (q.threads == 128 || (q.threads == 64 && q.hook) || (q.threads == 512 && !q.hook)) ? q.threads : 256;
     p.form.threads = block == 128 ? RANK_SMALL : block;
     if (!q.hook) {
-        // per-pass columns in LDS (32 B per slot with 128 threads, 61 B with 256: rank_loop_kernel) for lists of up to 1024 photons
-        // (two 256-thread lists per CU: 13 KB of static LDS and 61 B per slot each within 160 KB -> 1088 slots; four 128-thread ones at 32 B: 1024)
-        // (512 threads -- lists of thousands of photons, one list per CU: 27 KB of static LDS and 32 B per slot within 160 KB -> 4096 slots)
-        const int lds_limit = (block == 128) ? 1024 : (block == 512 ? 4096 : 1088);
-        if (!q.no_lds_lists && q.longest_list <= lds_limit) p.lds_slots = (q.longest_list + 15) & ~15;
+        // per-pass columns in LDS for lists of up to rank_lds_limit photons
+        if (!q.no_lds_lists && q.longest_list <= rank_lds_limit(block)) p.lds_slots = (q.longest_list + 15) & ~15;
         p.form.resident = p.lds_slots > 0;
     }
     p.dyn_bytes = (size_t)p.lds_slots * rank_lds_bytes_per_slot(block);
+    // (by the BUILD's thread count, as the kernel takes its pitch: with -DRANK_SMALL=64 a request for 128 runs the 64-thread build)
+    p.lds_bytes = p.form.resident ? (size_t)rank_lds_limit(p.form.threads) * rank_lds_bytes_per_slot(p.form.threads) : 0;
     // a fused request where no fused build exists runs unfused
     p.form.fuse = q.fuse && rank_build_exists(q.geometry, q.table, p.form.resident, p.form.threads, true, q.hook, q.queued, false);
     p.no_queue_build = q.queued && !rank_build_exists(q.geometry, q.table, p.form.resident, p.form.threads, p.form.fuse, q.hook, true, false);

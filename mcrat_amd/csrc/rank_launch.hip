@@ -54,10 +54,10 @@ int rank_launch_grid(const void *kernel, const RankLaunch &rl, const RankFormPla
 {
     const int device = plan.form.resident ? launch_device(rl.dev) : 0;
     // static + dynamic LDS may exceed the 64 KiB default: the kernel must be told
-    if (plan.form.resident && allow_dynamic_lds(kernel, device, (int)plan.dyn_bytes) != hipSuccess) { (void)hipGetLastError(); return -1; }
+    if (plan.form.resident && allow_dynamic_lds(kernel, device, (int)plan.lds_bytes) != hipSuccess) { (void)hipGetLastError(); return -1; }
     if (!plan.form.queue) return rl.n_ranks;
     int cus = rl.dev ? rl.dev->cus : 0;
-    const int per_cu = resident_per_cu(kernel, device, plan.form.threads, plan.dyn_bytes);
+    const int per_cu = resident_per_cu(kernel, device, plan.form.threads, plan.lds_bytes);
     if (cus <= 0 && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) { (void)hipGetLastError(); cus = 0; }
     return rank_queue_grid(rl.n_open, per_cu, cus);
 }
