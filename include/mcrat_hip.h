@@ -1059,11 +1059,65 @@ int mcrat_hip_observe_sky(mcrat_hip_ctx *ctx, const mcrat_hip_sky_observer *obs,
 int mcrat_hip_pool_observe_sky(mcrat_hip_ctx *pool, const mcrat_hip_sky_observer *obs, const double *time_now /* [n_ranks] */, mcrat_hip_sky_observation *out);
 int mcrat_hip_observe_sky_path(const mcrat_hip_ctx *ctx);
 
+/* escape-weighted sky observations: optical depth as an axis of the cube ---------
+ * mcrat_hip_observe_sky counts a photon at tau = 30 to the edge of the outflow exactly like one that is already free.  Here every photon that an
+ * observer accepts is first marched to the edge of a staged frame, and its optical depth becomes one more axis of the cube; beside the raw sums the
+ * cube holds the sums weighted with exp(-tau).
+ * What exp(-tau) means: for a photon at x moving along p_hat through ONE frozen frame it is the probability that its current flight leaves the frame
+ * without another scattering; tau is the straight-line optical depth to the edge, exactly as mcrat_hip_sightline_* define it.  The accepted
+ * photons move within the cone about n, so sum w * exp(-tau) per (observer, time, energy[, pixel]) is the expected signal already streaming towards
+ * that observer, and the tau axis shows from which depth that signal comes.  This is NOT a peel-off estimator towards n: the direction is the
+ * photon's own.
+ * Counted slots: as for mcrat_hip_observe.  Acceptance and axes: observer o accepts a photon by the rule of mcrat_hip_observe_sky, and its e, t_det
+ * and (X, Y) are that call's, the same expressions in the same order; `sky` is read exactly as mcrat_hip_observe_sky reads its struct.
+ * The march: a slot accepted by at least one observer is marched once, from (r0, r1, r2) along (p0 .. p3) through the staged frame of `hydro` (NULL:
+ * the context's own), by the sightline definition above with march.step_frac, h_min, max_steps and tau_stop (march.surface_level is not read); it
+ * ends in tau and a status.  A slot nobody accepts is not marched.
+ * For every observer o that accepts the photon: status OPAQUE adds to n_opaque[o]; STEP_CAP or OFF_TABLE adds to n_unresolved[o]; LEFT_MESH -- tau
+ * is the optical depth to the edge -- goes to bin (o, itau, it, ie[, iy, ix]), every axis decided by  edges[k] <= x < edges[k + 1]  through
+ * comparisons only; a LEFT_MESH photon outside any axis, or with a coordinate (tau included) that is not a number, adds to n_outside[o].  A photon
+ * that starts outside the frame has tau = 0 exactly and is a legitimate member of a bin that holds 0.
+ * The cube: nine planes of 8 bytes per bin -- count (integer), W = sum w, WE = sum w*e, I, Q, U, V = sum w*s0 .. s3 (zero with stokes_switch off) as
+ * mcrat_hip_observe_sky has them, WX = sum w*x and WEX = sum (w*e)*x with x = exp(-tau) -- each [n_obs][n_tau][n_t][n_e][n_y][n_x] with x fastest
+ * ([n_obs][n_tau][n_t][n_e] without image axes).  Per observer:  sum of count over o's bins + n_outside[o] + n_opaque[o] + n_unresolved[o] ==
+ * n_accepted[o].  Per call:  n_status[1] + .. + n_status[4] == n_selected <= n_observable; n_selected is the number of counted slots that at least
+ * one observer accepts, which is the number of rays marched, n_status[s] the marched rays that ended with sightline status s (n_status[0] is 0).
+ * Exactness: counts that do not hang on tau are exact, as in mcrat_hip_observe_sky.  tau is the sightline kernel's tau bit for bit -- both kernels
+ * call one march step --, so the cube's counts equal those of mcrat_hip_sightline_photons' tau binned by the same rules.  The sums are added with
+ * floating-point atomics and are NOT bit-reproducible; each is within (m + 2) * 2^-53 * sum|term| of the exact sum of its terms as the device
+ * computed them.
+ * MCRAT_HIP_EINVAL, each with its own text in mcrat_hip_last_error, prefixed "observe_escaping:", checked in this order: the checks of
+ * mcrat_hip_observe_sky on `sky`, in that call's order up to the edges; n_tau < 1; the product of the six counts overflowing an int; tau_edges not
+ * finite, then not strictly ascending; the sightline checks of step_frac, h_min, max_steps, tau_stop in the sightline order; more edges and
+ * observers than the kernel can stage; MCRAT_HIP_ESCAPE_PATH neither lds nor global; lds forced for a cube that does not fit; a `hydro` context on
+ * another device or with other DIMENSIONS, GEOMETRY or TAU_CALCULATION.  Then MCRAT_HIP_ESTATE: no staged frame; TABLE without a table.
+ *   mcrat_hip_observe_escaping        one list: a stand-alone context, or a view of a pool (that list alone); time_now is the list's clock.  A
+ *                                     pending advance is flushed first.  MCRAT_HIP_ESTATE without photons, and on a pool, before any other check.
+ *   mcrat_hip_pool_observe_escaping   every list of a pool, each with its own clock time_now[r]; it reads exactly what mcrat_hip_pool_observe_sky
+ *                                     reads, and like it flushes nothing a view holds pending.  MCRAT_HIP_ESTATE on a context that is no pool.
+ *   mcrat_hip_observe_escaping_path   how the context's last escape-weighted observation was accumulated: 1 a copy of the cube per workgroup in
+ *                                     LDS, flushed once; 2 atomics straight into the cube in HBM; 0 none yet.  MCRAT_HIP_ESCAPE_PATH=lds|global in
+ *                                     the environment forces one.
+ * Both calls synchronise once, before they return.  No photon column changes. */
+typedef struct mcrat_hip_escape_observer {      /* inputs, host pointers */
+    mcrat_hip_sky_observer sky;                 /* observers, cones, t/e edges, optional image axes: read exactly as mcrat_hip_observe_sky reads them */
+    int n_tau; const double *tau_edges;         /* [n_tau + 1], finite, strictly ascending */
+    mcrat_hip_sightline_params march;           /* step_frac, h_min, max_steps, tau_stop as the sightline calls read them; surface_level is not read */
+} mcrat_hip_escape_observer;
+typedef struct mcrat_hip_escape_observation {   /* outputs, host pointers; any may be NULL */
+    long long *count; double *w, *we, *i, *q, *u, *v, *wx, *wex;   /* each [n_obs][n_tau][n_t][n_e][n_y][n_x], x fastest; without image axes [n_obs][n_tau][n_t][n_e] */
+    long long *n_accepted, *n_outside, *n_opaque, *n_unresolved;   /* [n_obs] */
+    long long n_observable, n_selected, n_status[5];               /* counted slots; slots at least one observer accepts (= rays marched); the marched rays per sightline status */
+} mcrat_hip_escape_observation;
+int mcrat_hip_observe_escaping(mcrat_hip_ctx *ctx, const mcrat_hip_ctx *hydro /* or NULL */, const mcrat_hip_escape_observer *obs, double time_now, mcrat_hip_escape_observation *out);
+int mcrat_hip_pool_observe_escaping(mcrat_hip_ctx *pool, const mcrat_hip_ctx *hydro, const mcrat_hip_escape_observer *obs, const double *time_now /* [n_ranks] */, mcrat_hip_escape_observation *out);
+int mcrat_hip_observe_escaping_path(const mcrat_hip_ctx *ctx);
+
 /* introspection used by bench.py / tests -------------------------------------- */
 int mcrat_hip_synchronize(mcrat_hip_ctx *ctx);
-/* HBM held by the context: photons, staged frame, cell-lookup grid, loop state and the device blocks of all five analysis products -- observe,
- * observe_sky, sightline_*, radiation_field and comoving_field (the blocks of radiation_field and of observe_sky were left out before they became
- * one array).  A view holds no analysis block of its own: it uses its pool's, and they count there. */
+/* HBM held by the context: photons, staged frame, cell-lookup grid, loop state and the device blocks of all six analysis products -- observe,
+ * observe_sky, sightline_*, radiation_field, comoving_field and observe_escaping (the blocks of radiation_field and of observe_sky were left out
+ * before they became one array).  A view holds no analysis block of its own: it uses its pool's, and they count there. */
 size_t mcrat_hip_device_bytes(const mcrat_hip_ctx *ctx);
 int mcrat_hip_lookup_cell(mcrat_hip_ctx *ctx, int n, const double *a0, const double *a1, const double *a2, int *cell_out); /* device cell search == findContainingBlock geometry.c:350 */
 /* The staged frame's covered-octant table (one int per lookup bucket and octant, bucket-major: the cell that covers the octant, or -1): returns its

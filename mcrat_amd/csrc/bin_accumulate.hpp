@@ -1,4 +1,4 @@
-// bin_accumulate.hpp -- how the binned-sum kernels add: device code, included by observe.hip, sky.hip, radfield.hip and comoving.hip and by nothing else.  A bin is
+// bin_accumulate.hpp -- how the binned-sum kernels add: device code, included by observe.hip, sky.hip, radfield.hip, comoving.hip and escape.hip and by nothing else.  A bin is
 // a 64-bit integer count (plane 0) and N double sums (planes 1 .. N); where word `plane` of bin `bin` lies is the caller's address rule `at(plane,
 // bin)`, bound to its accumulator -- plane-major for the observation cube, the comoving field and every LDS copy (PlaneMajor, PlaneBases), plane- or
 // bin-major for the radiation field (radfield_word).  A lane's N values travel as double[N], N a template parameter and every loop over it unrolled: they stay in
@@ -11,6 +11,7 @@
 //   flush_lds_bins     LDS path: the bins the workgroup touched, from its private copy to HBM
 //   launch_with_lds    a launch that asks for more than the default 64 KB of dynamic LDS when it needs them
 //   cube_pass          the whole pass of observe_kernel and sky_kernel over the slots and the observers, the per-photon rules supplied by a rule type
+//                      (escape_bin_kernel's pass runs over a compacted list with tau and status per entry and nine planes: its own loop, these forms)
 // Barriers: match_alone holds three __syncthreads().  It must be called by every lane of the workgroup the same number of times -- from loops whose
 // trip counts are uniform per workgroup, with `has` false for a lane that has nothing to add.
 // Counts are exact.  The sums depend on the order in which the atomics are served: they are NOT bit-reproducible from run to run; each stays within

@@ -21,6 +21,7 @@
 #include "observe_plan.hpp"
 #include "sky_plan.hpp"
 #include "sightline_plan.hpp"
+#include "escape_plan.hpp"
 #include "radfield_plan.hpp"
 #include "comoving_plan.hpp"
 #include "photon_cols.hpp"
@@ -168,13 +169,15 @@ struct mcrat_hip_ctx {
     static constexpr int RED_BLOCKS = 512;
     // the device blocks of the analysis products, each laid out by its plan header: mcrat_hip_observe (the cube, the per-observer counters and the
     // staged inputs), mcrat_hip_sightline_* (the output block and the caller's rays), mcrat_hip_radiation_field (head, accumulator and staged
-    // edges), mcrat_hip_observe_sky (as observe), mcrat_hip_comoving_field (as radiation_field).  A view uses its pool's (analysis_block).
-    enum AnalysisBlock { BLOCK_OBSERVE = 0, BLOCK_SIGHTLINE, BLOCK_RADFIELD, BLOCK_SKY, BLOCK_COMOVING, N_ANALYSIS_BLOCKS };
+    // edges), mcrat_hip_observe_sky (as observe), mcrat_hip_comoving_field (as radiation_field), mcrat_hip_observe_escaping (planes, counters, head, staged
+    // inputs and the compacted list).  A view uses its pool's (analysis_block).
+    enum AnalysisBlock { BLOCK_OBSERVE = 0, BLOCK_SIGHTLINE, BLOCK_RADFIELD, BLOCK_SKY, BLOCK_COMOVING, BLOCK_ESCAPE, N_ANALYSIS_BLOCKS };
     struct DeviceBlock { void *buf = nullptr; size_t bytes = 0; } analysis[N_ANALYSIS_BLOCKS];
     int obs_path = 0;                 // the accumulation path of the last observation (ObservePath)
     int rf_path = 0;                  // the accumulation path of the last radiation field (ObservePath)
     int sky_path = 0;                 // the accumulation path of the last sky observation (ObservePath)
     int cf_path = 0;                  // the accumulation path of the last comoving field (ObservePath)
+    int esc_path = 0;                 // the accumulation path of the last escape-weighted observation (ObservePath)
 
     // profiling
     std::vector<hipEvent_t> ev;
@@ -4345,6 +4348,159 @@ extern "C" int mcrat_hip_pool_sightline_photons(mcrat_hip_ctx *c, const mcrat_hi
     if (rc) return rc;
     return sightline_run(c, hydro, params, c->ph.n, nullptr, out);
 }
+
+// ---------------------------------------------------------------------------------------------- escape-weighted sky observations
+// The checks of escape_plan.hpp on the caller's struct, then the frame: *h is the context whose staged frame the accepted photons are marched
+// through.  EINVAL comes before ESTATE, in the order the header gives.
+static int escape_check(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_escape_observer *obs, EscapeArgs *args, EscapePlan *plan,
+                        const mcrat_hip_ctx **h_out)
+{
+    char text[ESCAPE_TEXT_BYTES];
+    if (sky_args(c, &obs->sky, &args->sky) || !obs->tau_edges) {
+        c->last_error = "observe_escaping: a null array in mcrat_hip_escape_observer";
+        return MCRAT_HIP_EINVAL;
+    }
+    args->n_tau = obs->n_tau; args->tau_edges = obs->tau_edges;
+    args->march = SightlineParams{obs->march.step_frac, obs->march.h_min, obs->march.max_steps, obs->march.tau_stop, -1.0};
+    const EscapeRefusal why = escape_plan(*args, getenv("MCRAT_HIP_ESCAPE_PATH"), plan);
+    if (why != ESCAPE_OK) { c->last_error = escape_refusal_text(why, text); return MCRAT_HIP_EINVAL; }
+    const mcrat_hip_ctx *h = hydro ? hydro : c;
+    if (h != c && (h->kc.dimensions != c->kc.dimensions || h->kc.geometry != c->kc.geometry || h->kc.table != c->kc.table || h->cfg.device != c->cfg.device)) {
+        c->last_error = escape_refusal_text(ESCAPE_HYDRO_MISMATCH, text);
+        return MCRAT_HIP_EINVAL;
+    }
+    if (!h->have_hydro) { c->last_error = "observe_escaping: no staged hydro frame"; return MCRAT_HIP_ESTATE; }
+    if (c->kc.table && !h->hy.hot_table) {
+        c->last_error = "TAU_CALCULATION == TABLE needs mcrat_hip_set_hot_cross_section first";
+        return MCRAT_HIP_ESTATE;
+    }
+    *h_out = h;
+    return MCRAT_HIP_OK;
+}
+
+// The kernels' inputs in the order the binning kernel stages them (escape_plan.hpp): the sky observation's, then tau_edges; the clocks behind them.
+static std::vector<double> escape_staged_inputs(const EscapeArgs &args, const EscapePlan &plan, const double *clocks, int n_clocks)
+{
+    SkyPlan sky{};                               // (what sky_staged_inputs reads of a plan)
+    sky.n_obs = plan.n_obs; sky.n_t = plan.n_t; sky.n_e = plan.n_e; sky.n_x = plan.n_x; sky.n_y = plan.n_y; sky.image = plan.image;
+    sky.staged_doubles = plan.staged_doubles;
+    std::vector<double> in = sky_staged_inputs(args.sky, sky, nullptr, 0);
+    in.insert(in.end(), args.tau_edges, args.tau_edges + plan.n_tau + 1);
+    if (clocks) in.insert(in.end(), clocks, clocks + n_clocks);
+    return in;
+}
+
+// How the block's results come back.  A small block -- light curves, spectra -- is read back whole by one copy and handed out on the host: fourteen
+// copies of a few hundred bytes each cost the light-curve call 0.12 ms of its 0.50.  A larger one -- images, megabytes per
+// plane -- is read plane by plane, as cube_run does: a plane the caller does not ask for is not copied.
+constexpr size_t ESCAPE_ONE_COPY_BYTES = 256 * 1024;
+
+// -> planes, per-observer counters and the call's counters from `block`, host memory that holds the first out_bytes of the device block from
+// `first` on (first == 0: all of it; first == plan.head_offset: the head alone), to wherever *out wants them
+static void escape_fill_outputs(const EscapePlan &plan, const char *block, size_t first, mcrat_hip_escape_observation *out)
+{
+    static_assert(sizeof(long long) == 8, "the count plane, the counters and the head are handed over as they are");
+    if (first == 0) {
+        const size_t plane = sizeof(double) * (size_t)plan.n_bins, counters = sizeof(long long) * (size_t)plan.n_obs;
+        void *planes[ESCAPE_PLANES] = {out->count, out->w, out->we, out->i, out->q, out->u, out->v, out->wx, out->wex};
+        for (int k = 0; k < ESCAPE_PLANES; ++k)
+            if (planes[k]) memcpy(planes[k], block + plane * (size_t)k, plane);
+        long long *per_observer[ESCAPE_COUNTERS] = {out->n_accepted, out->n_outside, out->n_opaque, out->n_unresolved};
+        for (int k = 0; k < ESCAPE_COUNTERS; ++k)
+            if (per_observer[k]) memcpy(per_observer[k], block + plan.counters_offset + counters * (size_t)k, counters);
+    }
+    long long head[ESCAPE_HEAD_WORDS];
+    memcpy(head, block + (plan.head_offset - first), sizeof head);
+    for (int k = 0; k < SIGHTLINE_N_STATUS; ++k) out->n_status[k] = head[k];
+    out->n_selected = head[ESCAPE_SELECTED_WORD];
+    out->n_observable = head[ESCAPE_OBSERVABLE_WORD];
+}
+
+// The read-back of a block beyond ESCAPE_ONE_COPY_BYTES: the planes and per-observer counters that *out asks for, each straight to where it wants
+// them, and the head into `head`; copies on c's stream, not waited for.
+static int escape_read_planes(mcrat_hip_ctx *c, const EscapePlan &plan, const char *d, mcrat_hip_escape_observation *out, char *head)
+{
+    const size_t plane = sizeof(double) * (size_t)plan.n_bins, counters = sizeof(long long) * (size_t)plan.n_obs;
+    void *planes[ESCAPE_PLANES] = {out->count, out->w, out->we, out->i, out->q, out->u, out->v, out->wx, out->wex};
+    for (int k = 0; k < ESCAPE_PLANES; ++k)
+        if (planes[k]) HIPCHK(c, hipMemcpyAsync(planes[k], d + plane * (size_t)k, plane, hipMemcpyDeviceToHost, c->stream));
+    long long *per_observer[ESCAPE_COUNTERS] = {out->n_accepted, out->n_outside, out->n_opaque, out->n_unresolved};
+    for (int k = 0; k < ESCAPE_COUNTERS; ++k)
+        if (per_observer[k]) HIPCHK(c, hipMemcpyAsync(per_observer[k], d + plan.counters_offset + counters * (size_t)k, counters, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(head, d + plan.head_offset, sizeof(long long) * ESCAPE_HEAD_WORDS, hipMemcpyDeviceToHost, c->stream));
+    return MCRAT_HIP_OK;
+}
+
+// The photons of c->ph -- n_slots of them -- that an observer accepts, marched through h's staged frame and binned (escape_plan.hpp, escape.hip):
+// check, block, stage, three launches, the read-back (escape_fill_outputs), one synchronise, the outputs filled in.  clocks: one per slots_per_clock slots (a rank pool's lists), or nullptr and
+// time_now for all.
+static int escape_run(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_escape_observer *obs, int n_slots, const double *clocks, int n_clocks,
+                      int slots_per_clock, double time_now, mcrat_hip_escape_observation *out)
+{
+    c->esc_path = OBSERVE_PATH_NONE;
+    EscapeArgs args{};
+    EscapePlan plan;
+    const mcrat_hip_ctx *h = nullptr;
+    int rc = escape_check(c, hydro, obs, &args, &plan, &h);
+    if (rc) return rc;
+
+    const EscapeLayout lay = escape_layout(plan, n_slots, clocks ? n_clocks : 0);
+    char *d = nullptr;
+    if ((rc = analysis_block(c, h, mcrat_hip_ctx::BLOCK_ESCAPE, lay.total_bytes, &d))) return rc;
+
+    const std::vector<double> in = escape_staged_inputs(args, plan, clocks, n_clocks);
+    HIPCHK(c, hipMemsetAsync(d, 0, plan.out_bytes, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + lay.staged_offset, in.data(), sizeof(double) * in.size(), hipMemcpyHostToDevice, c->stream));
+
+    EscapeDev a{};
+    a.n_slots = n_slots; a.n_obs = plan.n_obs; a.n_tau = plan.n_tau; a.n_t = plan.n_t; a.n_e = plan.n_e; a.n_x = plan.n_x; a.n_y = plan.n_y; a.n_bins = plan.n_bins;
+    a.step_frac = plan.march.step_frac; a.h_min = plan.march.h_min; a.max_steps = plan.march.max_steps; a.tau_stop = plan.march.tau_stop;
+    a.staged = reinterpret_cast<const double *>(d + lay.staged_offset);
+    a.clocks = clocks ? reinterpret_cast<const double *>(d + lay.clocks_offset) : nullptr;
+    a.slots_per_clock = slots_per_clock;
+    a.time_now = time_now;
+    a.cube = reinterpret_cast<double *>(d);
+    a.counters = reinterpret_cast<unsigned long long *>(d + plan.counters_offset);
+    a.head = reinterpret_cast<unsigned long long *>(d + plan.head_offset);
+    a.tau = reinterpret_cast<double *>(d + lay.tau_offset);
+    a.index = reinterpret_cast<int *>(d + lay.index_offset);
+    a.status = reinterpret_cast<int *>(d + lay.status_offset);
+    const int cus = device_cus(c);
+    HIPCHK(c, launch_escape(c->kc, c->ph, h->hy, a, plan, c->kc.stokes != 0, escape_select_grid(n_slots, cus), escape_march_grid(n_slots),
+                            escape_bin_grid(plan, n_slots, cus), c->stream));
+
+    const bool whole = plan.out_bytes <= ESCAPE_ONE_COPY_BYTES;
+    const size_t first = whole ? 0 : plan.head_offset;
+    std::vector<char> host(plan.out_bytes - first);
+    if (whole) HIPCHK(c, hipMemcpyAsync(host.data(), d, plan.out_bytes, hipMemcpyDeviceToHost, c->stream));
+    else if ((rc = escape_read_planes(c, plan, d, out, host.data()))) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    escape_fill_outputs(plan, host.data(), first, out);
+    c->esc_path = plan.path;
+    return MCRAT_HIP_OK;
+}
+
+extern "C" int mcrat_hip_observe_escaping(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_escape_observer *obs, double time_now,
+                                          mcrat_hip_escape_observation *out)
+{
+    if (!c || !obs || !out) return MCRAT_HIP_EINVAL;
+    if (!c->have_photons) return MCRAT_HIP_ESTATE;
+    if (c->is_pool) { c->last_error = "observe_escaping: a rank pool's lists have clocks of their own (mcrat_hip_pool_observe_escaping, or mcrat_hip_observe_escaping on a view)"; return MCRAT_HIP_ESTATE; }
+    int rc = flush_pending(c);
+    if (rc) return rc;
+    return escape_run(c, hydro, obs, c->ph.n, nullptr, 0, 1, time_now, out);
+}
+
+extern "C" int mcrat_hip_pool_observe_escaping(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_escape_observer *obs, const double *time_now,
+                                               mcrat_hip_escape_observation *out)
+{
+    if (!c || !obs || !time_now || !out) return MCRAT_HIP_EINVAL;
+    if (!c->is_pool) { c->last_error = "pool_observe_escaping: the context is no rank pool"; return MCRAT_HIP_ESTATE; }
+    // every slot of the pool, exactly as mcrat_hip_pool_observe_sky reads them, and like it without flush_pending
+    return escape_run(c, hydro, obs, c->ph.n, time_now, c->n_ranks, c->rank_stride, 0.0, out);
+}
+
+extern "C" int mcrat_hip_observe_escaping_path(const mcrat_hip_ctx *c) { return c ? c->esc_path : 0; }
 
 // ---------------------------------------------------------------------------------------------- the radiation field on the hydro mesh
 // The checks of radfield_plan.hpp on the caller's bins, then the frame: *h is the context whose staged frame the photons are located in, *plan the

@@ -187,6 +187,27 @@ struct SkyDev {
     unsigned long long *n_accepted, *n_outside;   // [n_obs]
 };
 hipError_t launch_sky(const PhotonDev &ph, const SkyDev &a, const SkyPlan &plan, bool stokes, int blocks, hipStream_t stream);
+// escape-weighted sky observations (escape.hip): the slots an observer accepts compacted into a list, those marched through the frame hy, and the
+// list binned by observer, optical depth, detection time, energy and, with image axes, sky-plane position -- three kernels on one stream.  The block
+// is laid out as escape_plan.hpp says; the caller zeroes planes, counters and head, copies the staged inputs and the clocks and sizes the three grids.
+struct EscapePlan;
+struct EscapeDev {
+    int n_slots, n_obs, n_tau, n_t, n_e, n_x, n_y, n_bins;
+    double step_frac, h_min;
+    int max_steps;
+    double tau_stop;
+    const double *staged;                // sky_plan.hpp's staged inputs, then tau_edges [n_tau + 1]
+    const double *clocks;
+    int slots_per_clock;
+    double time_now;
+    double *cube;                        // ESCAPE_PLANES planes of n_bins; plane 0 holds 64-bit integer counts
+    unsigned long long *counters;        // n_accepted, n_outside, n_opaque, n_unresolved: [n_obs] each
+    unsigned long long *head;            // n_status[5], n_selected, n_observable
+    double *tau;                         // the compacted list, room for n_slots entries: the march's tau ...
+    int *index, *status;                 // ... the slot, and how the march ended
+};
+hipError_t launch_escape(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, const EscapeDev &a, const EscapePlan &plan, bool stokes,
+                         int select_blocks, int march_blocks, int bin_blocks, hipStream_t stream);
 hipError_t launch_init_states_multi(LoopState *ranks, int n_ranks, const int *open, const double *time_now, const double *remaining, hipStream_t stream);
 hipError_t launch_aos_to_soa(const void *aos, const PhotonDev &ph, int n, hipStream_t stream);
 // many lists of a rank pool at once: desc = `count` device records {int rank, int n, long long first record in aos}; the rest of each window is cleared

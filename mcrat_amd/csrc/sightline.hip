@@ -6,7 +6,8 @@
 // shortcut: a frame may keep covered coarse cells, and "still inside the entry I hold" does not prove "lowest-index containing cell".
 //
 // A lane is a small state machine: idle, marching (phase 1), or marching a second time to find the surface (phase 2: the march is deterministic,
-// so the partial sums S_k come out bit for bit, and the ray's total T is known by then).  Both phases share one step body.
+// so the partial sums S_k come out bit for bit, and the ray's total T is known by then).  Both phases share one step body, sightline_step
+// (sightline_march.hpp), which the escape-weighted observation's march calls too.
 // Two forms of handing rays to lanes, same outputs per ray:
 //   plain    lane i of the grid takes ray i; a wavefront idles on its longest ray.
 //   refill   a lane whose ray has ended takes the next unclaimed ray: from its workgroup's own range first (an LDS counter), then from one global
@@ -18,6 +19,7 @@
 #include "observe_plan.hpp"
 #include "physics.hpp"
 #include "sightline_plan.hpp"
+#include "sightline_march.hpp"
 
 namespace mcrat {
 
@@ -139,36 +141,10 @@ __global__ __launch_bounds__(SIGHTLINE_BLOCK) void sightline_kernel(PhotonDev ph
                 surface_done = true;
             }
             if (status < 0 && !surface_done) {
-                const double h = sightline_step_length(x, y, z, a.step_frac, a.h_min);
-                double mx, my, mz, a0, a1, a2;
-                sightline_midpoint(x, y, z, h, nx, ny, nz, mx, my, mz);
-                phys::hydro_coords<DIMS, GEOM>(mx, my, mz, a0, a1, a2);
-                FatCell hit;
-                hit.cell = -1;
-                if (phys::in_domain<DIMS>(hy, a0, a1, a2))
-                    phys::find_in_bucket<DIMS>(hy, phys::grid_bucket_of<DIMS>(hy.grid, a0, a1, a2), a0, a1, a2, hit);
-                if (hit.cell < 0) {
-                    status = SIGHTLINE_LEFT_MESH;
-                } else {
-                    double cphi, sphi, beta[3], norm = 1.0;
-                    phys::relocation_azimuth<DIMS, GEOM>(mx, my, a0, cphi, sphi);
-                    phys::beta_from_record<DIMS>(hit.a, hit.b, hit.c, cphi, sphi, beta);
-                    bool off_table = false;
-                    if constexpr (TABLE) {
-                        double comv[4], eps, theta;
-                        phys::boost_with<false>(beta, hit.gam, phys::kf_of_gamma(hit.gam), p, comv);
-                        off_table = phys::thermal_cross_section_lookup(hy, comv[0], hy.temp[hit.cell], norm, eps, theta);
-                    }
-                    if (off_table) {
-                        status = SIGHTLINE_OFF_TABLE;
-                    } else {
-                        const double kappa = phys::optical_depth_staged(beta, hit.w, hit.nsig, p[1], p[2], p[3], norm);
-                        tau += kappa * h;
-                        path += h;
-                        sightline_advance(x, y, z, h, nx, ny, nz);
-                        k += 1;
-                        if (phase == 1 && tau >= a.tau_stop) status = SIGHTLINE_OPAQUE;
-                    }
+                status = sightline_step<DIMS, GEOM, TABLE>(hy, p, a.step_frac, a.h_min, nx, ny, nz, x, y, z, tau, path);
+                if (status < 0) {                             // the step was counted
+                    k += 1;
+                    if (phase == 1 && tau >= a.tau_stop) status = SIGHTLINE_OPAQUE;
                 }
                 if (phase == 2 && status >= 0) {              // (cannot happen: phase 2 repeats steps that phase 1 has counted)
                     write_surface(a, ray, -1, nan, nan, nan);

@@ -116,14 +116,23 @@ inline SightlineRefusal sightline_refill_switch(const char *env, int *forced)
 // profiles/sightline_forms.txt): refill becomes the default only where it wins on both by more than the run-to-run spread.
 constexpr bool SIGHTLINE_REFILL_DEFAULT = false;
 
-// The checks, in this order: n, step_frac, h_min, max_steps, tau_stop, surface_level; then the switch.  *plan is filled when SIGHTLINE_OK.
-inline SightlineRefusal sightline_plan(int n, const SightlineParams &p, int forced_refill, SightlinePlan *plan)
+// The four parameters of the march itself, in this order: step_frac, h_min, max_steps, tau_stop (surface_level is not looked at).  Also what the
+// escape-weighted observation checks of its march (escape_plan.hpp).
+inline SightlineRefusal sightline_march_check(const SightlineParams &p)
 {
-    if (n <= 0) return SIGHTLINE_NO_RAYS;
     if (!isfinite(p.step_frac) || p.step_frac < 0) return SIGHTLINE_BAD_STEP_FRAC;
     if (!isfinite(p.h_min) || !(p.h_min > 0)) return SIGHTLINE_BAD_H_MIN;
     if (p.max_steps < 1 || p.max_steps > SIGHTLINE_MAX_STEPS) return SIGHTLINE_BAD_MAX_STEPS;
     if (!(p.tau_stop > 0)) return SIGHTLINE_BAD_TAU_STOP;
+    return SIGHTLINE_OK;
+}
+
+// The checks, in this order: n, step_frac, h_min, max_steps, tau_stop, surface_level; then the switch.  *plan is filled when SIGHTLINE_OK.
+inline SightlineRefusal sightline_plan(int n, const SightlineParams &p, int forced_refill, SightlinePlan *plan)
+{
+    if (n <= 0) return SIGHTLINE_NO_RAYS;
+    const SightlineRefusal march = sightline_march_check(p);
+    if (march != SIGHTLINE_OK) return march;
     if (!(p.surface_level < INFINITY)) return SIGHTLINE_BAD_SURFACE_LEVEL;
     SightlinePlan pl{};
     pl.n = n; pl.p = p;

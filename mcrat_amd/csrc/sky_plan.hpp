@@ -154,11 +154,10 @@ inline double sky_dot(const double *a0, const double *a1, const double *a2, cons
 }
 inline bool sky_unit(const double *a, const double *b, const double *c, int o) { return !(fabs(sky_dot(a, b, c, a, b, c, o) - 1.0) > SKY_UNIT_TOLERANCE); }
 
-// The checks, in this order: the counts; the image axes' counts; the product; the directions finite, then unit; the cones; with image axes the
-// sky-plane vectors -- there, finite, unit, orthogonal --; the edges of t, e, x, y -- each finite, then ascending --; what must fit LDS; then the
-// switch `env` (MCRAT_HIP_SKY_PATH) -- its spelling, lds with a cube beyond the budget.  The path, the LDS and the workgroups per CU are
-// accumulate_rule's (observe_plan.hpp).  *plan is filled when SKY_OK.
-inline SkyRefusal sky_plan(const SkyArgs &a, const char *env, SkyPlan *plan)
+// The checks of the arguments alone, in this order: the counts; the image axes' counts; the product; the directions finite, then unit; the cones;
+// with image axes the sky-plane vectors -- there, finite, unit, orthogonal --; the edges of t, e, x, y -- each finite, then ascending.  *n_bins is
+// filled when SKY_OK.  Also what the escape-weighted observation checks of its observers (escape_plan.hpp).
+inline SkyRefusal sky_args_check(const SkyArgs &a, int *n_bins)
 {
     if (a.n_obs < 1 || a.n_t < 1 || a.n_e < 1) return SKY_NO_BINS;
     if (!((a.n_x == 0 && a.n_y == 0) || (a.n_x >= 1 && a.n_y >= 1))) return SKY_IMAGE_AXES_MISMATCH;
@@ -191,8 +190,20 @@ inline SkyRefusal sky_plan(const SkyArgs &a, const char *env, SkyPlan *plan)
     if (why == SKY_OK && image) why = sky_edges_check(a.x_edges, a.n_x, SKY_X_EDGES_NOT_FINITE, SKY_X_EDGES_NOT_ASCENDING);
     if (why == SKY_OK && image) why = sky_edges_check(a.y_edges, a.n_y, SKY_Y_EDGES_NOT_FINITE, SKY_Y_EDGES_NOT_ASCENDING);
     if (why != SKY_OK) return why;
+    *n_bins = (int)bins;
+    return SKY_OK;
+}
+
+// The checks, in this order: the arguments' (sky_args_check); what must fit LDS; then the switch `env` (MCRAT_HIP_SKY_PATH) -- its spelling, lds
+// with a cube beyond the budget.  The path, the LDS and the workgroups per CU are accumulate_rule's (observe_plan.hpp).  *plan is filled when SKY_OK.
+inline SkyRefusal sky_plan(const SkyArgs &a, const char *env, SkyPlan *plan)
+{
+    int bins = 0;
+    const SkyRefusal why = sky_args_check(a, &bins);
+    if (why != SKY_OK) return why;
+    const bool image = a.n_x >= 1;
     SkyPlan p{};
-    p.n_obs = a.n_obs; p.n_t = a.n_t; p.n_e = a.n_e; p.n_x = a.n_x; p.n_y = a.n_y; p.image = image; p.n_bins = (int)bins;
+    p.n_obs = a.n_obs; p.n_t = a.n_t; p.n_e = a.n_e; p.n_x = a.n_x; p.n_y = a.n_y; p.image = image; p.n_bins = bins;
     p.cube_bytes = (size_t)OBSERVE_PLANES * 8 * (size_t)p.n_bins;
     p.out_bytes = p.cube_bytes + (size_t)2 * 8 * (size_t)a.n_obs;
     p.staged_doubles = (size_t)(image ? 10 : 4) * a.n_obs + (size_t)a.n_t + 1 + (size_t)a.n_e + 1 + (image ? (size_t)a.n_x + 1 + (size_t)a.n_y + 1 : 0);

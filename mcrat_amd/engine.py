@@ -229,6 +229,31 @@ class Sightlines(C.Structure):
 SIGHTLINE_SKIPPED, SIGHTLINE_LEFT_MESH, SIGHTLINE_OPAQUE, SIGHTLINE_STEP_CAP, SIGHTLINE_OFF_TABLE = 0, 1, 2, 3, 4
 
 
+class EscapeObserver(C.Structure):
+    """mcrat_hip_escape_observer: a sky observation's inputs, the optical-depth edges and how the accepted photons are marched"""
+    _fields_ = [("sky", SkyObserver), ("n_tau", C.c_int), ("tau_edges", _dp), ("march", SightlineParams)]
+
+
+ESCAPE_SUMS = ("w", "we", "i", "q", "u", "v", "wx", "wex")
+ESCAPE_COUNTERS = ("n_accepted", "n_outside", "n_opaque", "n_unresolved")
+
+
+class EscapeObservation(C.Structure):
+    """mcrat_hip_escape_observation: the cube's nine planes, each [n_obs * n_tau * n_t * n_e * n_y * n_x], the per-observer counters and the
+    call's counters"""
+    _fields_ = ([("count", C.POINTER(C.c_longlong))] + [(k, _dp) for k in ESCAPE_SUMS] + [(k, C.POINTER(C.c_longlong)) for k in ESCAPE_COUNTERS] +
+                [("n_observable", C.c_longlong), ("n_selected", C.c_longlong), ("n_status", C.c_longlong * 5)])
+
+
+ESCAPE_PATH_LDS, ESCAPE_PATH_GLOBAL = 1, 2        # mcrat_hip_observe_escaping_path
+
+
+def escape_fraction(res):
+    """WX / W of an escape-weighted observation: the share of each bin's signal that is already streaming out; 0 / 0 -> NaN"""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(res["w"] != 0, res["wx"] / res["w"], np.nan)
+
+
 class RadfieldBins(C.Structure):
     """mcrat_hip_radfield_bins: the binning of a radiation field -- the hydro cells, or (r, mu) shells with their edges"""
     _fields_ = [("mode", C.c_int), ("n_r", C.c_int), ("r_edges", _dp), ("n_mu", C.c_int), ("mu_edges", _dp)]
@@ -374,6 +399,9 @@ SYMBOLS = {
     "mcrat_hip_observe_sky": (C.c_int, [_ctx, C.POINTER(SkyObserver), C.c_double, C.POINTER(SkyObservation)]),
     "mcrat_hip_pool_observe_sky": (C.c_int, [_ctx, C.POINTER(SkyObserver), _dp, C.POINTER(SkyObservation)]),
     "mcrat_hip_observe_sky_path": (C.c_int, [_ctx]),
+    "mcrat_hip_observe_escaping": (C.c_int, [_ctx, _ctx, C.POINTER(EscapeObserver), C.c_double, C.POINTER(EscapeObservation)]),
+    "mcrat_hip_pool_observe_escaping": (C.c_int, [_ctx, _ctx, C.POINTER(EscapeObserver), _dp, C.POINTER(EscapeObservation)]),
+    "mcrat_hip_observe_escaping_path": (C.c_int, [_ctx]),
     "mcrat_hip_synchronize": (C.c_int, [_ctx]),
     "mcrat_hip_device_bytes": (C.c_size_t, [_ctx]),
     "mcrat_hip_eval_function": (C.c_int, [_ctx, C.c_int, C.c_int, _dp, _dp, C.c_uint64]),
@@ -1153,7 +1181,10 @@ class Engine:
         return int(self.lib.mcrat_hip_observe_path(self.ctx))
 
     # ---- sky observers: mock observations from any direction, with images (include/mcrat_hip.h)
-    def _observe_sky(self, call, what, n, cos_acc, t_edges, e_edges, time_now, ex, ey, x_edges, y_edges):
+    @staticmethod
+    def _sky_observer(what, n, cos_acc, t_edges, e_edges, ex, ey, x_edges, y_edges):
+        """-> the ABI's SkyObserver for these arguments, the arrays it points at (to be kept alive for the call), the cube's shape with the
+        observers first, and whether there are image axes"""
         def vec(a, name):
             a = _f8(a)
             if a.ndim == 1 and a.shape[0] == 3:
@@ -1178,7 +1209,11 @@ class Engine:
         row = lambda a, k: ptr(a[k]) if a is not None else None
         obs = SkyObserver(n_obs, row(nv, 0), row(nv, 1), row(nv, 2), ptr(ca), row(xv, 0), row(xv, 1), row(xv, 2), row(yv, 0), row(yv, 1), row(yv, 2),
                           n_t, ptr(te), n_e, ptr(ee), n_x, ptr(xe), n_y, ptr(ye))
-        res, out = self._cube_result(tuple(max(m, 0) for m in ((n_obs, n_t, n_e, n_y, n_x) if image else (n_obs, n_t, n_e))), SkyObservation)
+        return obs, (nv, ca, te, ee, xe, ye, xv, yv), tuple(max(m, 0) for m in ((n_obs, n_t, n_e, n_y, n_x) if image else (n_obs, n_t, n_e))), image
+
+    def _observe_sky(self, call, what, n, cos_acc, t_edges, e_edges, time_now, ex, ey, x_edges, y_edges):
+        obs, _alive, shape, _ = self._sky_observer(what, n, cos_acc, t_edges, e_edges, ex, ey, x_edges, y_edges)
+        res, out = self._cube_result(shape, SkyObservation)
         self._check(call(self.ctx, C.byref(obs), time_now, C.byref(out)), what)
         return res
 
@@ -1200,6 +1235,49 @@ class Engine:
     def observe_sky_path(self):
         """how the last sky observation of this context was accumulated: SKY_PATH_LDS, SKY_PATH_GLOBAL, 0: none yet"""
         return int(self.lib.mcrat_hip_observe_sky_path(self.ctx))
+
+    # ---- escape-weighted sky observations: optical depth as an axis of the cube (include/mcrat_hip.h)
+    def _observe_escaping(self, call, what, n, cos_acc, t_edges, e_edges, tau_edges, time_now, step_frac, h_min, max_steps, tau_stop, hydro, ex, ey,
+                          x_edges, y_edges):
+        sky, _alive, sky_shape, _ = self._sky_observer(what, n, cos_acc, t_edges, e_edges, ex, ey, x_edges, y_edges)
+        tau = _f8(tau_edges).ravel()
+        n_tau = len(tau) - 1
+        obs = EscapeObserver(sky, n_tau, tau.ctypes.data_as(_dp), SightlineParams(float(step_frac), float(h_min), int(max_steps), float(tau_stop), -1.0))
+        shape = (sky_shape[0], max(n_tau, 0)) + sky_shape[1:]
+        res = {"count": np.zeros(shape, dtype=np.int64)}
+        for k in ESCAPE_SUMS:
+            res[k] = np.zeros(shape)
+        for k in ESCAPE_COUNTERS:
+            res[k] = np.zeros(shape[0], dtype=np.int64)
+        ll = C.POINTER(C.c_longlong)
+        out = EscapeObservation(res["count"].ctypes.data_as(ll), *([res[k].ctypes.data_as(_dp) for k in ESCAPE_SUMS] +
+                                                                     [res[k].ctypes.data_as(ll) for k in ESCAPE_COUNTERS]))
+        self._check(call(self.ctx, hydro.ctx if hydro is not None else None, C.byref(obs), time_now, C.byref(out)), what)
+        res.update(n_observable=int(out.n_observable), n_selected=int(out.n_selected), n_status=np.array(list(out.n_status), dtype=np.int64))
+        return res
+
+    def observe_escaping(self, n, cos_acc, t_edges, e_edges, tau_edges, time_now, step_frac, h_min, max_steps, tau_stop=np.inf, hydro=None, ex=None, ey=None,
+                         x_edges=None, y_edges=None):
+        """this list's photons as observe_sky bins them, with their optical depth to the edge of the staged frame as one more axis and the sums
+        weighted with exp(-tau) beside the raw ones (mcrat_hip_observe_escaping).  Only the photons that an observer accepts are marched, as
+        sightline_photons marches them (step_frac, h_min, max_steps, tau_stop); hydro: another Engine whose staged frame they cross (None: this
+        one's).  -> dict of (n_obs, n_tau, n_t, n_e[, n_y, n_x]) arrays count, w, we, i, q, u, v, wx, wex; the per-observer n_accepted, n_outside,
+        n_opaque, n_unresolved; n_observable, n_selected and n_status (5,).  escape_fraction(res) gives wx / w."""
+        return self._observe_escaping(self.lib.mcrat_hip_observe_escaping, "observe_escaping", n, cos_acc, t_edges, e_edges, tau_edges, float(time_now),
+                                      step_frac, h_min, max_steps, tau_stop, hydro, ex, ey, x_edges, y_edges)
+
+    def pool_observe_escaping(self, n, cos_acc, t_edges, e_edges, tau_edges, time_now, step_frac, h_min, max_steps, tau_stop=np.inf, hydro=None, ex=None,
+                              ey=None, x_edges=None, y_edges=None):
+        """every list of the pool at once, list r at its own clock time_now[r] (mcrat_hip_pool_observe_escaping)"""
+        tn = _f8(time_now).ravel()
+        if len(tn) != self.n_pool_ranks:
+            raise ValueError("pool_observe_escaping: time_now needs one clock per rank of the pool")
+        return self._observe_escaping(self.lib.mcrat_hip_pool_observe_escaping, "pool_observe_escaping", n, cos_acc, t_edges, e_edges, tau_edges,
+                                      tn.ctypes.data_as(_dp), step_frac, h_min, max_steps, tau_stop, hydro, ex, ey, x_edges, y_edges)
+
+    def observe_escaping_path(self):
+        """how the last escape-weighted observation of this context was accumulated: ESCAPE_PATH_LDS, ESCAPE_PATH_GLOBAL, 0: none yet"""
+        return int(self.lib.mcrat_hip_observe_escaping_path(self.ctx))
 
     # ---- line-of-sight optical depths and photospheres (include/mcrat_hip.h)
     def _sightlines(self, what, n, call, step_frac, h_min, max_steps, tau_stop, surface_level):
