@@ -1113,10 +1113,75 @@ int mcrat_hip_observe_escaping(mcrat_hip_ctx *ctx, const mcrat_hip_ctx *hydro /*
 int mcrat_hip_pool_observe_escaping(mcrat_hip_ctx *pool, const mcrat_hip_ctx *hydro, const mcrat_hip_escape_observer *obs, const double *time_now /* [n_ranks] */, mcrat_hip_escape_observation *out);
 int mcrat_hip_observe_escaping_path(const mcrat_hip_ctx *ctx);
 
+/* sky polarimetry: observer-frame Stokes sums and a resampling axis ---------------
+ * A sky observation (mcrat_hip_observe_sky) whose Q and U can be summed in the observer's sky-plane frame and whose cube has a replica axis behind
+ * the observer: jackknife groups for standard errors, Poisson-bootstrap replicas for the distribution of any derived quantity (polarisation degree
+ * and angle, <E> = WE / W, light-curve points).  Which slots are counted, acceptance, e, t_det, (X, Y), the bin rule, n_accepted and n_outside are
+ * mcrat_hip_observe_sky's, unchanged; `sky` is read exactly as that call reads its struct.
+ * The cube: the seven planes count, W, WE, I, Q, U, V, each [n_obs][n_rep][n_t][n_e][n_y][n_x] with x fastest ([n_obs][n_rep][n_t][n_e] without
+ * image axes).  An accepted, binned photon adds to replica rho:  k  to count and  (double)k * term  to each sum, term exactly mcrat_hip_observe_sky's
+ * -- w, w*e, w*s0 .. s3, with (s1, s2) possibly rotated (below).  k = k(photon identity, rho) does not depend on the observer.
+ * Photon identity: (rank, slot) -- rank the list's index in its pool (the view's rank for a view, slot / rank_stride in a pool call, 0 for a
+ * stand-alone context), slot the index within the list; a view and its pool give a photon the same k.  All draws are words w[0 .. 3] of the
+ * Philox4x32-10 block with counter {slot, rank, block, 2 | mode << 8} and key `seed` (2: this product's purpose word):
+ *   MCRAT_HIP_RESAMPLE_NONE        n_rep == 1, k = 1.
+ *   MCRAT_HIP_RESAMPLE_JACKKNIFE   n_rep = G >= 2 disjoint groups: block 0, g = ((uint64_t)w[0] * G) >> 32, k = [rho == g]; entry g holds group g's
+ *                                  own sums, so the sum over the entries is the sky observation.
+ *   MCRAT_HIP_RESAMPLE_BOOTSTRAP   n_rep = B + 1 >= 2: entry 0 is the sample itself (k = 1); for rho >= 1, j = rho - 1, the block is j >> 2, the word
+ *                                  w[j & 3] and k = #{m : word >= T_m}, T_m = floor(2^32 * sum_{i <= m} exp(-1) / i!) for m = 0 .. 11 (T_0 =
+ *                                  1580030168): a Poisson(1) draw, k <= 12, with a truncation bias below 2^-31.
+ * Integer arithmetic throughout: every count is exactly reproducible on the host.
+ * The Stokes frame.  MCRAT_HIP_STOKES_AS_STORED: Q and U are summed as the photons store them, as mcrat_hip_observe_sky does -- each in the
+ * photon's own frame (theta_hat, phi_hat of its direction), which turns against the observer's by about alpha * cot(theta_obs) for a photon alpha
+ * off the line of sight.  MCRAT_HIP_STOKES_SKY_PLANE: for every accepted (photon, observer) pair (Q, U) are carried from the photon's frame to the
+ * observer's with MCRaT's own rule (findPhi and mullerMatrixRotation, mcrat_scattering.c), written so that it stays well conditioned near zero
+ * angle.  With p = (p1, p2, p3) and ey the observer's second sky-plane vector, in exactly this order, IEEE double, correctly rounded, no contraction:
+ *     rho2 = p1*p1 + p2*p2;   pn = sqrt(rho2 + p3*p3);   d = p2*ey0 - p1*ey1;   s = (rho2*ey2 - p3*(p1*ey0 + p2*ey1)) / pn;
+ *     h = sqrt(d*d + s*s);   c = d / h;   sg = s / h;   c2 = c*c - sg*sg;   s2 = (-2.0*sg) * c;
+ *     Q' = Q*c2 - U*s2;   U' = Q*s2 + U*c2;   I and V are unchanged
+ * (d and s are y_ph . y_new and x_ph . y_new up to one positive factor: y_ph ~ (p2, -p1, 0), x_ph = y_ph x p_hat, y_new ~ ey - (ey . p_hat) p_hat).
+ * When h is 0 or not finite (p parallel to the polar axis, or to ey) the pair's Q and U are added as stored and n_frame_undefined[o] counts the
+ * accepted pair, binned or not.  SKY_PLANE needs ex and ey even without image axes.  With stokes_switch off there is nothing to rotate: I, Q, U, V
+ * stay zero and n_frame_undefined stays 0.
+ * The sense of U: a photon at azimuth phi_p infinitesimally off the axis, with stored (Q, U) = (1, 0), seen by the on-axis observer with
+ * ex = x_hat, ey = y_hat, contributes (cos 2 phi_p, -sin 2 phi_p).  It is MCRaT's sense of U.
+ * Exactness: counts and counters are exact; each sum is within (m + 2) * 2^-53 * sum|k * term| of the exact sum of its bin's m terms k * term.
+ * MCRAT_HIP_EINVAL, each with its own text in mcrat_hip_last_error, prefixed "observe_sky_resampled:", checked in this order: the checks of
+ * mcrat_hip_observe_sky on `sky`, in that call's order up to the edges; mode; stokes_frame; n_rep (NONE: not 1; otherwise < 2); the product of the
+ * six counts overflowing an int; SKY_PLANE without ex and ey, or with ex, ey not finite, not unit or not orthogonal to 1e-12; more edges and
+ * observers than the kernel can stage; MCRAT_HIP_RESAMPLE_PATH none of lds, sliced, global; a forced path that does not fit.
+ *   mcrat_hip_observe_sky_resampled        one list: a stand-alone context, or a view of a pool (that list alone); time_now is the list's clock.  A
+ *                                          pending advance is flushed first.  MCRAT_HIP_ESTATE without photons, and on a pool.
+ *   mcrat_hip_pool_observe_sky_resampled   every list of a pool in one launch, each with its own clock time_now[r]; it reads exactly what
+ *                                          mcrat_hip_pool_observe_sky reads, and like it flushes nothing a view holds pending.  MCRAT_HIP_ESTATE on
+ *                                          a context that is no pool.
+ *   mcrat_hip_observe_sky_resampled_path   how the context's last such observation was accumulated: 1 a copy of the whole cube per workgroup in LDS;
+ *                                          3 sliced -- the replica axis cut into slices, a workgroup owns one slice's part of the cube in LDS, walks
+ *                                          all slots and adds the replicas of its slice; 2 atomics straight into the cube in HBM; 0 none yet.
+ *                                          MCRAT_HIP_RESAMPLE_PATH=lds|sliced|global in the environment forces one.
+ * Both calls synchronise once, before they return.  No photon column changes. */
+#define MCRAT_HIP_RESAMPLE_NONE      0   /* n_rep == 1: a sky observation, with the Stokes frame below */
+#define MCRAT_HIP_RESAMPLE_JACKKNIFE 1   /* n_rep = G >= 2 disjoint groups; entry g holds group g's own sums */
+#define MCRAT_HIP_RESAMPLE_BOOTSTRAP 2   /* n_rep = B + 1 >= 2; entry 0 is the sample itself, entries 1..B are Poisson(1) resamples */
+#define MCRAT_HIP_STOKES_AS_STORED   0
+#define MCRAT_HIP_STOKES_SKY_PLANE   1
+typedef struct mcrat_hip_resample_observer {      /* inputs, host pointers */
+    mcrat_hip_sky_observer sky;                   /* read exactly as mcrat_hip_observe_sky reads it */
+    int mode, n_rep, stokes_frame;
+    uint64_t seed;
+} mcrat_hip_resample_observer;
+typedef struct mcrat_hip_resample_observation {   /* outputs, host pointers; any may be NULL */
+    long long *count; double *w, *we, *i, *q, *u, *v;        /* each [n_obs][n_rep][n_t][n_e][n_y][n_x], x fastest */
+    long long *n_accepted, *n_outside, *n_frame_undefined;   /* [n_obs] */
+} mcrat_hip_resample_observation;
+int mcrat_hip_observe_sky_resampled(mcrat_hip_ctx *ctx, const mcrat_hip_resample_observer *obs, double time_now, mcrat_hip_resample_observation *out);
+int mcrat_hip_pool_observe_sky_resampled(mcrat_hip_ctx *pool, const mcrat_hip_resample_observer *obs, const double *time_now /* [n_ranks] */, mcrat_hip_resample_observation *out);
+int mcrat_hip_observe_sky_resampled_path(const mcrat_hip_ctx *ctx);
+
 /* introspection used by bench.py / tests -------------------------------------- */
 int mcrat_hip_synchronize(mcrat_hip_ctx *ctx);
-/* HBM held by the context: photons, staged frame, cell-lookup grid, loop state and the device blocks of all six analysis products -- observe,
- * observe_sky, sightline_*, radiation_field, comoving_field and observe_escaping (the blocks of radiation_field and of observe_sky were left out
+/* HBM held by the context: photons, staged frame, cell-lookup grid, loop state and the device blocks of all seven analysis products -- observe,
+ * observe_sky, sightline_*, radiation_field, comoving_field, observe_escaping and observe_sky_resampled (the blocks of radiation_field and of observe_sky were left out
  * before they became one array).  A view holds no analysis block of its own: it uses its pool's, and they count there. */
 size_t mcrat_hip_device_bytes(const mcrat_hip_ctx *ctx);
 int mcrat_hip_lookup_cell(mcrat_hip_ctx *ctx, int n, const double *a0, const double *a1, const double *a2, int *cell_out); /* device cell search == findContainingBlock geometry.c:350 */

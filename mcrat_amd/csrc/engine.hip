@@ -22,6 +22,7 @@
 #include "sky_plan.hpp"
 #include "sightline_plan.hpp"
 #include "escape_plan.hpp"
+#include "resample_plan.hpp"
 #include "radfield_plan.hpp"
 #include "comoving_plan.hpp"
 #include "photon_cols.hpp"
@@ -170,14 +171,15 @@ struct mcrat_hip_ctx {
     // the device blocks of the analysis products, each laid out by its plan header: mcrat_hip_observe (the cube, the per-observer counters and the
     // staged inputs), mcrat_hip_sightline_* (the output block and the caller's rays), mcrat_hip_radiation_field (head, accumulator and staged
     // edges), mcrat_hip_observe_sky (as observe), mcrat_hip_comoving_field (as radiation_field), mcrat_hip_observe_escaping (planes, counters, head, staged
-    // inputs and the compacted list).  A view uses its pool's (analysis_block).
-    enum AnalysisBlock { BLOCK_OBSERVE = 0, BLOCK_SIGHTLINE, BLOCK_RADFIELD, BLOCK_SKY, BLOCK_COMOVING, BLOCK_ESCAPE, N_ANALYSIS_BLOCKS };
+    // inputs and the compacted list), mcrat_hip_observe_sky_resampled (as observe, with a third counter).  A view uses its pool's (analysis_block).
+    enum AnalysisBlock { BLOCK_OBSERVE = 0, BLOCK_SIGHTLINE, BLOCK_RADFIELD, BLOCK_SKY, BLOCK_COMOVING, BLOCK_ESCAPE, BLOCK_RESAMPLE, N_ANALYSIS_BLOCKS };
     struct DeviceBlock { void *buf = nullptr; size_t bytes = 0; } analysis[N_ANALYSIS_BLOCKS];
     int obs_path = 0;                 // the accumulation path of the last observation (ObservePath)
     int rf_path = 0;                  // the accumulation path of the last radiation field (ObservePath)
     int sky_path = 0;                 // the accumulation path of the last sky observation (ObservePath)
     int cf_path = 0;                  // the accumulation path of the last comoving field (ObservePath)
     int esc_path = 0;                 // the accumulation path of the last escape-weighted observation (ObservePath)
+    int rs_path = 0;                  // the accumulation path of the last resampled sky observation (ResamplePath)
 
     // profiling
     std::vector<hipEvent_t> ev;
@@ -4501,6 +4503,85 @@ extern "C" int mcrat_hip_pool_observe_escaping(mcrat_hip_ctx *c, const mcrat_hip
 }
 
 extern "C" int mcrat_hip_observe_escaping_path(const mcrat_hip_ctx *c) { return c ? c->esc_path : 0; }
+
+// ---------------------------------------------------------------------------------------------- sky observations with a resampling axis
+// The photons of c->ph -- n_slots of them -- binned as sky_run bins them, with a replica axis behind the observer and, on request, Q and U in the
+// observer's frame (resample_plan.hpp, resample.hip): a cube job like sky_run's, with a third per-observer counter read back beside the two.
+// rank_base, rank_stride: the photons' identities (launch.hpp, ResampleDev).
+static int resample_run(mcrat_hip_ctx *c, const mcrat_hip_resample_observer *obs, int n_slots, const double *clocks, int n_clocks, int slots_per_clock, double time_now,
+                        int rank_base, int rank_stride, mcrat_hip_resample_observation *out)
+{
+    c->rs_path = RESAMPLE_PATH_NONE;
+    ResampleArgs args{};
+    if (sky_args(c, &obs->sky, &args.sky)) {
+        c->last_error = "observe_sky_resampled: a null array in mcrat_hip_resample_observer";
+        return MCRAT_HIP_EINVAL;
+    }
+    args.mode = obs->mode; args.n_rep = obs->n_rep; args.stokes_frame = obs->stokes_frame;
+    ResamplePlan plan;
+    const ResampleRefusal why = resample_plan(args, getenv("MCRAT_HIP_RESAMPLE_PATH"), &plan);
+    if (why != RESAMPLE_OK) {
+        char text[RESAMPLE_TEXT_BYTES];
+        c->last_error = resample_refusal_text(why, text);
+        return MCRAT_HIP_EINVAL;
+    }
+    // the inputs in the order the kernel stages them (resample_plan.hpp: ex and ey for SKY_PLANE too), the clocks behind them
+    std::vector<double> in;
+    {
+        const SkyArgs &s = args.sky;
+        const size_t n_obs = (size_t)plan.n_obs;
+        in.reserve(plan.staged_doubles + (size_t)n_clocks);
+        for (const double *v : {s.n0, s.n1, s.n2, s.cos_acc}) in.insert(in.end(), v, v + n_obs);
+        if (plan.axes)
+            for (const double *v : {s.x0, s.x1, s.x2, s.y0, s.y1, s.y2}) in.insert(in.end(), v, v + n_obs);
+        in.insert(in.end(), s.t_edges, s.t_edges + plan.n_t + 1);
+        in.insert(in.end(), s.e_edges, s.e_edges + plan.n_e + 1);
+        if (plan.image) {
+            in.insert(in.end(), s.x_edges, s.x_edges + plan.n_x + 1);
+            in.insert(in.end(), s.y_edges, s.y_edges + plan.n_y + 1);
+        }
+        if (clocks) in.insert(in.end(), clocks, clocks + n_clocks);
+    }
+    const ResampleGrid grid = resample_grid(plan, n_slots, device_cus(c));
+    ResampleDev a{};
+    a.n_slots = n_slots; a.n_obs = plan.n_obs; a.n_rep = plan.n_rep; a.n_t = plan.n_t; a.n_e = plan.n_e; a.n_x = plan.n_x; a.n_y = plan.n_y;
+    a.n_bins = plan.n_bins; a.per_rep = plan.per_rep; a.mode = plan.mode; a.axes = plan.axes ? 1 : 0;
+    a.slice_reps = plan.slice_reps; a.n_slices = plan.n_slices; a.grid_x = grid.x; a.grid_y = grid.y;
+    a.seed = obs->seed; a.rank_base = rank_base; a.rank_stride = rank_stride;
+    a.slots_per_clock = slots_per_clock;
+    a.time_now = time_now;
+    const int rc = cube_run(c, mcrat_hip_ctx::BLOCK_RESAMPLE, plan, in, clocks != nullptr, a, [&](const ResampleDev &placed) -> int {
+        ResampleDev dev = placed;
+        dev.n_undefined = dev.n_outside + plan.n_obs;                  // the third counter, inside what cube_run has zeroed (plan.out_bytes)
+        HIPCHK(c, launch_resample(c->ph, dev, plan, c->kc.stokes != 0, grid.x, grid.y, c->stream));
+        if (out->n_frame_undefined)
+            HIPCHK(c, hipMemcpyAsync(out->n_frame_undefined, dev.n_undefined, sizeof(long long) * (size_t)plan.n_obs, hipMemcpyDeviceToHost, c->stream));
+        return MCRAT_HIP_OK;
+    }, out);
+    if (rc) return rc;
+    c->rs_path = plan.path;
+    return MCRAT_HIP_OK;
+}
+
+extern "C" int mcrat_hip_observe_sky_resampled(mcrat_hip_ctx *c, const mcrat_hip_resample_observer *obs, double time_now, mcrat_hip_resample_observation *out)
+{
+    if (!c || !obs || !out) return MCRAT_HIP_EINVAL;
+    if (!c->have_photons) return MCRAT_HIP_ESTATE;
+    if (c->is_pool) { c->last_error = "observe_sky_resampled: a rank pool's lists have clocks of their own (mcrat_hip_pool_observe_sky_resampled, or mcrat_hip_observe_sky_resampled on a view)"; return MCRAT_HIP_ESTATE; }
+    int rc = flush_pending(c);
+    if (rc) return rc;
+    return resample_run(c, obs, c->ph.n, nullptr, 0, 1, time_now, c->parent ? c->view_rank : 0, 0, out);
+}
+
+extern "C" int mcrat_hip_pool_observe_sky_resampled(mcrat_hip_ctx *c, const mcrat_hip_resample_observer *obs, const double *time_now, mcrat_hip_resample_observation *out)
+{
+    if (!c || !obs || !time_now || !out) return MCRAT_HIP_EINVAL;
+    if (!c->is_pool) { c->last_error = "pool_observe_sky_resampled: the context is no rank pool"; return MCRAT_HIP_ESTATE; }
+    // every slot of the pool, exactly as mcrat_hip_pool_observe_sky reads them, and like it without flush_pending
+    return resample_run(c, obs, c->ph.n, time_now, c->n_ranks, c->rank_stride, 0.0, 0, c->rank_stride, out);
+}
+
+extern "C" int mcrat_hip_observe_sky_resampled_path(const mcrat_hip_ctx *c) { return c ? c->rs_path : 0; }
 
 // ---------------------------------------------------------------------------------------------- the radiation field on the hydro mesh
 // The checks of radfield_plan.hpp on the caller's bins, then the frame: *h is the context whose staged frame the photons are located in, *plan the

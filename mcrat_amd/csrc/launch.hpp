@@ -208,6 +208,26 @@ struct EscapeDev {
 };
 hipError_t launch_escape(const KernelConfig &kc, const PhotonDev &ph, const HydroDev &hy, const EscapeDev &a, const EscapePlan &plan, bool stokes,
                          int select_blocks, int march_blocks, int bin_blocks, hipStream_t stream);
+// sky observations with a resampling axis and a choice of Stokes frame (resample.hip): observe_sky's pass with a replica axis behind the observer
+// and a multiplicity per (photon, replica).  The block and the staged inputs are laid out as resample_plan.hpp says; clocks as in ObserveDev.  The
+// caller zeroes the cube and the counters and sizes the grid (resample_grid).  A photon's identity: rank = rank_base + i / rank_stride and slot =
+// i % rank_stride for slot i of a pool (rank_stride > 0), rank = rank_base and slot = i otherwise.
+struct ResamplePlan;
+struct ResampleDev {
+    int n_slots, n_obs, n_rep, n_t, n_e, n_x, n_y, n_bins, per_rep;
+    int mode, axes;                      // ResampleMode; whether ex and ey are staged
+    int slice_reps, n_slices;            // LDS and sliced: the replicas a workgroup's sub-cube holds, and how many such slices the replica axis has
+    int grid_x, grid_y;                  // the launch is grid_x * grid_y workgroups: workgroup b walks the slots as number b % grid_x of grid_x, for the slices b / grid_x, + grid_y, ..
+    unsigned long long seed;
+    int rank_base, rank_stride;
+    const double *staged;                // n0, n1, n2, cos_acc [n_obs each]; (axes) x0 .. x2, y0 .. y2 [n_obs each]; t_edges, e_edges; (image) x_edges, y_edges
+    const double *clocks;
+    int slots_per_clock;
+    double time_now;
+    double *cube;                        // OBSERVE_PLANES planes of n_bins; plane 0 holds 64-bit integer counts
+    unsigned long long *n_accepted, *n_outside, *n_undefined;   // [n_obs]
+};
+hipError_t launch_resample(const PhotonDev &ph, const ResampleDev &a, const ResamplePlan &plan, bool stokes, int blocks_x, int blocks_y, hipStream_t stream);
 hipError_t launch_init_states_multi(LoopState *ranks, int n_ranks, const int *open, const double *time_now, const double *remaining, hipStream_t stream);
 hipError_t launch_aos_to_soa(const void *aos, const PhotonDev &ph, int n, hipStream_t stream);
 // many lists of a rank pool at once: desc = `count` device records {int rank, int n, long long first record in aos}; the rest of each window is cleared

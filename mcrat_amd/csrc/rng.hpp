@@ -27,6 +27,7 @@ namespace mcrat {
 
 constexpr uint32_t RNG_FREEPATH = 0u;
 constexpr uint32_t RNG_EVENT = 1u;
+constexpr uint32_t RNG_RESAMPLE = 2u;           // the multiplicities of a resampled sky observation (resample_plan.hpp)
 
 struct Philox4 {
     uint32_t w[4];

@@ -254,6 +254,99 @@ def escape_fraction(res):
         return np.where(res["w"] != 0, res["wx"] / res["w"], np.nan)
 
 
+class ResampleObserver(C.Structure):
+    """mcrat_hip_resample_observer: a sky observation's inputs, the resampling mode with its replicas and seed, and the Stokes frame"""
+    _fields_ = [("sky", SkyObserver), ("mode", C.c_int), ("n_rep", C.c_int), ("stokes_frame", C.c_int), ("seed", C.c_uint64)]
+
+
+RESAMPLE_COUNTERS = ("n_accepted", "n_outside", "n_frame_undefined")
+
+
+class ResampleObservation(C.Structure):
+    """mcrat_hip_resample_observation: the cube's seven planes, each [n_obs * n_rep * n_t * n_e * n_y * n_x], and the per-observer counters"""
+    _fields_ = ([("count", C.POINTER(C.c_longlong))] + [(k, _dp) for k in ("w", "we", "i", "q", "u", "v")] +
+                [(k, C.POINTER(C.c_longlong)) for k in RESAMPLE_COUNTERS])
+
+
+RESAMPLE_NONE, RESAMPLE_JACKKNIFE, RESAMPLE_BOOTSTRAP = 0, 1, 2       # mcrat_hip_resample_observer.mode
+STOKES_AS_STORED, STOKES_SKY_PLANE = 0, 1                             # mcrat_hip_resample_observer.stokes_frame
+RESAMPLE_PATH_LDS, RESAMPLE_PATH_GLOBAL, RESAMPLE_PATH_SLICED = 1, 2, 3      # mcrat_hip_observe_sky_resampled_path
+
+
+def _wrap_half_pi(d):
+    """an angle difference into (-pi/2, pi/2]: polarisation angles are defined modulo pi"""
+    return d - np.pi * np.ceil((d - 0.5 * np.pi) / np.pi)
+
+
+def resampled_estimates(res, mode, reduce=(), percentiles=None):
+    """Estimates with errors from the cube of Engine.observe_sky_resampled.  res: its dict, arrays (n_obs, n_rep, n_t, n_e[, n_y, n_x]); mode: the
+    mode it was made with; reduce: the axes summed first, any of "time" (spectra), "energy" (light curves) and "pixels".
+    -> dict with w, we, e_mean = WE / W, pi = sqrt(Q^2 + U^2) / I and angle = atan2(U, Q) / 2, each a dict of value and stderr over
+    (n_obs, the axes that are left); a bin without photons gives NaN.
+    RESAMPLE_JACKKNIFE: entry g holds group g's own sums x_g.  With T = sum_g x_g the estimate is f(T), replicate g is f((T - x_g) G / (G - 1)) --
+    the rescale makes totals unbiased when the number of photons is itself Poisson; it cancels in ratios -- and
+    var = (G - 1) / G sum_g (theta_g - mean theta)^2.
+    RESAMPLE_BOOTSTRAP: the estimate is f(entry 0), stderr the sample standard deviation (ddof = 1) of f over entries 1 .. B; percentiles = (lo, hi)
+    in per cent adds the bounds lo and hi of f over those entries.
+    RESAMPLE_NONE: the estimates alone, stderr NaN.
+    The angle's differences are wrapped into (-pi/2, pi/2] about the estimate before they are averaged."""
+    axes = {"time": (2,), "energy": (3,), "pixels": (4, 5)}
+    names = (reduce,) if isinstance(reduce, str) else tuple(reduce)
+    for k in names:
+        if k not in axes:
+            raise ValueError("resampled_estimates: reduce takes time, energy and pixels, not %r" % (k,))
+    ndim = res["count"].ndim
+    over = tuple(sorted(a for k in set(names) for a in axes[k] if a < ndim))
+    x = {k: np.asarray(res[k], dtype=np.float64).sum(axis=over) for k in ("w", "we", "i", "q", "u")}      # (n_obs, n_rep, ...)
+    count = np.asarray(res["count"]).sum(axis=over)
+    n_rep = count.shape[1]
+
+    def stats(s):
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return {"w": s["w"], "we": s["we"], "e_mean": s["we"] / s["w"], "pi": np.sqrt(s["q"] * s["q"] + s["u"] * s["u"]) / s["i"],
+                    "angle": 0.5 * np.arctan2(s["u"], s["q"])}
+
+    if mode == RESAMPLE_JACKKNIFE:
+        if n_rep < 2:
+            raise ValueError("resampled_estimates: a jackknife needs at least two groups")
+        total = {k: v.sum(axis=1) for k, v in x.items()}
+        filled = count.sum(axis=1) > 0
+        value = stats(total)
+        scale = n_rep / (n_rep - 1.0)
+        reps = stats({k: (total[k][:, None] - v) * scale for k, v in x.items()})
+    elif mode == RESAMPLE_BOOTSTRAP:
+        if n_rep < 3:
+            raise ValueError("resampled_estimates: a bootstrap error needs at least two replicas beside the sample")
+        filled = count[:, 0] > 0
+        value = stats({k: v[:, 0] for k, v in x.items()})
+        reps = stats({k: v[:, 1:] for k, v in x.items()})
+    elif mode == RESAMPLE_NONE:
+        filled = count[:, 0] > 0
+        value = stats({k: v[:, 0] for k, v in x.items()})
+        reps = None
+    else:
+        raise ValueError("resampled_estimates: mode must be RESAMPLE_NONE, RESAMPLE_JACKKNIFE or RESAMPLE_BOOTSTRAP")
+    out = {}
+    for k, val in value.items():
+        val = np.where(filled, val, np.nan)
+        est = {"value": val, "stderr": np.full(val.shape, np.nan)}
+        if reps is not None:
+            with np.errstate(invalid="ignore"):
+                dev = reps[k] - val[:, None]
+                if k == "angle":
+                    dev = _wrap_half_pi(dev)
+                if mode == RESAMPLE_JACKKNIFE:
+                    var = (n_rep - 1.0) / n_rep * ((dev - dev.mean(axis=1, keepdims=True)) ** 2).sum(axis=1)
+                else:
+                    var = dev.var(axis=1, ddof=1)
+                    if percentiles is not None:
+                        lo, hi = np.percentile(dev, list(percentiles), axis=1)
+                        est["lo"], est["hi"] = np.where(filled, val + lo, np.nan), np.where(filled, val + hi, np.nan)
+                est["stderr"] = np.where(filled, np.sqrt(var), np.nan)
+        out[k] = est
+    return out
+
+
 class RadfieldBins(C.Structure):
     """mcrat_hip_radfield_bins: the binning of a radiation field -- the hydro cells, or (r, mu) shells with their edges"""
     _fields_ = [("mode", C.c_int), ("n_r", C.c_int), ("r_edges", _dp), ("n_mu", C.c_int), ("mu_edges", _dp)]
@@ -402,6 +495,9 @@ SYMBOLS = {
     "mcrat_hip_observe_escaping": (C.c_int, [_ctx, _ctx, C.POINTER(EscapeObserver), C.c_double, C.POINTER(EscapeObservation)]),
     "mcrat_hip_pool_observe_escaping": (C.c_int, [_ctx, _ctx, C.POINTER(EscapeObserver), _dp, C.POINTER(EscapeObservation)]),
     "mcrat_hip_observe_escaping_path": (C.c_int, [_ctx]),
+    "mcrat_hip_observe_sky_resampled": (C.c_int, [_ctx, C.POINTER(ResampleObserver), C.c_double, C.POINTER(ResampleObservation)]),
+    "mcrat_hip_pool_observe_sky_resampled": (C.c_int, [_ctx, C.POINTER(ResampleObserver), _dp, C.POINTER(ResampleObservation)]),
+    "mcrat_hip_observe_sky_resampled_path": (C.c_int, [_ctx]),
     "mcrat_hip_synchronize": (C.c_int, [_ctx]),
     "mcrat_hip_device_bytes": (C.c_size_t, [_ctx]),
     "mcrat_hip_eval_function": (C.c_int, [_ctx, C.c_int, C.c_int, _dp, _dp, C.c_uint64]),
@@ -1278,6 +1374,46 @@ class Engine:
     def observe_escaping_path(self):
         """how the last escape-weighted observation of this context was accumulated: ESCAPE_PATH_LDS, ESCAPE_PATH_GLOBAL, 0: none yet"""
         return int(self.lib.mcrat_hip_observe_escaping_path(self.ctx))
+
+    # ---- sky polarimetry: observer-frame Stokes sums and a resampling axis (include/mcrat_hip.h)
+    def _observe_sky_resampled(self, call, what, n, cos_acc, t_edges, e_edges, time_now, mode, n_rep, stokes_frame, seed, ex, ey, x_edges, y_edges):
+        sky, _alive, sky_shape, _ = self._sky_observer(what, n, cos_acc, t_edges, e_edges, ex, ey, x_edges, y_edges)
+        obs = ResampleObserver(sky, int(mode), int(n_rep), int(stokes_frame), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        shape = (sky_shape[0], max(int(n_rep), 0)) + sky_shape[1:]
+        res = {"count": np.zeros(shape, dtype=np.int64)}
+        for k in ("w", "we", "i", "q", "u", "v"):
+            res[k] = np.zeros(shape)
+        for k in RESAMPLE_COUNTERS:
+            res[k] = np.zeros(shape[0], dtype=np.int64)
+        ll = C.POINTER(C.c_longlong)
+        out = ResampleObservation(res["count"].ctypes.data_as(ll), *([res[k].ctypes.data_as(_dp) for k in ("w", "we", "i", "q", "u", "v")] +
+                                                                       [res[k].ctypes.data_as(ll) for k in RESAMPLE_COUNTERS]))
+        self._check(call(self.ctx, C.byref(obs), time_now, C.byref(out)), what)
+        return res
+
+    def observe_sky_resampled(self, n, cos_acc, t_edges, e_edges, time_now, mode=RESAMPLE_JACKKNIFE, n_rep=32, stokes_frame=STOKES_AS_STORED, seed=0,
+                              ex=None, ey=None, x_edges=None, y_edges=None):
+        """this list's photons as observe_sky bins them, with a replica axis behind the observer -- RESAMPLE_JACKKNIFE: n_rep disjoint groups;
+        RESAMPLE_BOOTSTRAP: the sample and n_rep - 1 Poisson(1) resamples; RESAMPLE_NONE: n_rep = 1 -- and, with STOKES_SKY_PLANE, Q and U carried
+        into the observer's frame (ex, ey) before they are summed (mcrat_hip_observe_sky_resampled).  -> dict of (n_obs, n_rep, n_t, n_e[, n_y, n_x])
+        arrays count, w, we, i, q, u, v and the per-observer n_accepted, n_outside, n_frame_undefined.  resampled_estimates(res, mode) turns it into
+        estimates with errors."""
+        return self._observe_sky_resampled(self.lib.mcrat_hip_observe_sky_resampled, "observe_sky_resampled", n, cos_acc, t_edges, e_edges, float(time_now),
+                                           mode, n_rep, stokes_frame, seed, ex, ey, x_edges, y_edges)
+
+    def pool_observe_sky_resampled(self, n, cos_acc, t_edges, e_edges, time_now, mode=RESAMPLE_JACKKNIFE, n_rep=32, stokes_frame=STOKES_AS_STORED, seed=0,
+                                   ex=None, ey=None, x_edges=None, y_edges=None):
+        """every list of the pool in one launch, list r at its own clock time_now[r] (mcrat_hip_pool_observe_sky_resampled)"""
+        tn = _f8(time_now).ravel()
+        if len(tn) != self.n_pool_ranks:
+            raise ValueError("pool_observe_sky_resampled: time_now needs one clock per rank of the pool")
+        return self._observe_sky_resampled(self.lib.mcrat_hip_pool_observe_sky_resampled, "pool_observe_sky_resampled", n, cos_acc, t_edges, e_edges,
+                                           tn.ctypes.data_as(_dp), mode, n_rep, stokes_frame, seed, ex, ey, x_edges, y_edges)
+
+    def observe_sky_resampled_path(self):
+        """how the last resampled sky observation of this context was accumulated: RESAMPLE_PATH_LDS, RESAMPLE_PATH_SLICED, RESAMPLE_PATH_GLOBAL,
+        0: none yet"""
+        return int(self.lib.mcrat_hip_observe_sky_resampled_path(self.ctx))
 
     # ---- line-of-sight optical depths and photospheres (include/mcrat_hip.h)
     def _sightlines(self, what, n, call, step_frac, h_min, max_steps, tau_stop, surface_level):
