@@ -1178,11 +1178,74 @@ int mcrat_hip_observe_sky_resampled(mcrat_hip_ctx *ctx, const mcrat_hip_resample
 int mcrat_hip_pool_observe_sky_resampled(mcrat_hip_ctx *pool, const mcrat_hip_resample_observer *obs, const double *time_now /* [n_ranks] */, mcrat_hip_resample_observation *out);
 int mcrat_hip_observe_sky_resampled_path(const mcrat_hip_ctx *ctx);
 
+/* detected-photon event lists: time-ordered rows per observer ---------------------
+ * The list of photons each observer detects, one row per accepted (photon, observer) pair inside a window of detection time and energy, made where
+ * the photons live: what ProcessMCRaT calls an ObservedPhotonList.  It is what comes before any binning -- T90 from the cumulative fluence, bins of
+ * equal counts, Bayesian blocks, unbinned fits, other edges without another pass over the photons, a look at single photons.
+ * Counted slots: as for mcrat_hip_observe.
+ * Observers: n_obs, n0 n1 n2 (unit, towards the observer) and cos_acc as in mcrat_hip_sky_observer.  The sky-plane vectors x0 .. x2 (ex) and
+ * y0 .. y2 (ey) are optional: they are read when all six are given, and only then are the X and Y columns produced; MCRAT_HIP_STOKES_SKY_PLANE
+ * needs them.  Without them the X and Y output pointers must be NULL.
+ * Acceptance, e, t_det, (X, Y): observer o accepts a photon by the rule of mcrat_hip_observe_sky, and e = p0 * C_LIGHT, t_det and (X, Y) are that
+ * call's -- the same expressions in the same order, evaluated by the same functions.
+ * The window:  t_lo <= t_det < t_hi  and  e_lo <= e < e_hi, by comparisons only; a bound may be -inf or +inf.  An accepted pair outside the window,
+ * or with a coordinate that is not a number, adds to n_outside[o]; every other accepted pair is an event:
+ * n_events[o] + n_outside[o] == n_accepted[o].
+ * The Stokes frame: stokes_frame is MCRAT_HIP_STOKES_AS_STORED -- s1 and s2 as the photon stores them -- or MCRAT_HIP_STOKES_SKY_PLANE -- (s1, s2)
+ * carried into the observer's frame by the rotation of mcrat_hip_observe_sky_resampled, per pair.  n_frame_undefined[o] counts the accepted pairs,
+ * inside the window or not, for which that rotation is undefined; their rows hold s1 and s2 as stored.  With stokes_switch off the s0 .. s3 columns
+ * are zero and n_frame_undefined stays 0.
+ * Rows: the columns are optional output pointers, each [capacity]: rank and slot (int) -- the photon's identity exactly as
+ * mcrat_hip_observe_sky_resampled defines it, so a view and its pool agree --; t, e, w (the weight), s0, s1, s2, s3, X, Y, num_scatt (double); type
+ * (char).  offsets [n_obs + 1]: observer o's rows are [offsets[o], offsets[o + 1]); offsets[n_obs] == n_total.
+ * Order.  MCRAT_HIP_EVENTS_BY_PHOTON: rows ordered by (observer, rank, slot).  MCRAT_HIP_EVENTS_BY_TIME: by (observer, key(t), rank, slot), key(t)
+ * the usual order-preserving map of the double's bits to a uint64_t: with the sign bit set all bits are inverted, otherwise the sign bit is set.
+ * So -0.0 sorts before +0.0, -inf is a legal key, and a NaN never reaches a row.  The order is fully specified and every value of a row is one of
+ * the documented IEEE expressions: every output is bit-reproducible from run to run.
+ * Capacity: handled on the device, with no host round trip between the kernels.  Rows at index >= capacity are not written; n_events, n_accepted,
+ * n_outside, n_frame_undefined, offsets and n_total are always exact.  When n_total > capacity the call returns MCRAT_HIP_EREFUSED with its own text;
+ * the row outputs are then unspecified -- no partial list is to be trusted.  capacity == 0 with all row pointers NULL is the counting call: it
+ * returns 0 whatever n_total.  Each row column is copied back in full, `capacity` entries; those behind n_total are unspecified.
+ * The sort (BY_TIME): a stable LSD radix sort over 8-bit digits of key(t), then of the observer index.  A digit that is the same in all keys -- the
+ * OR and the AND of all keys agree in it -- is skipped on the device.  key_or and key_and return the two masks (0 and ~0 for an empty list),
+ * sort_passes_run and sort_passes_skipped what followed from them (both 0 for BY_PHOTON, for an empty list and for one that did not fit).
+ * MCRAT_HIP_EINVAL, each with its own text in mcrat_hip_last_error, prefixed "observe_events:", checked in this order: the checks of
+ * mcrat_hip_observe_sky on the observers in that call's order up to the cosines -- n_obs < 1, a direction not finite, not unit, cos_acc no number in
+ * [-1, 1] --; order; stokes_frame; ex and ey given but not finite, not unit or not orthogonal to 1e-12; SKY_PLANE without them; X or Y pointers
+ * without them; a bound of the window that is not a number, then t_lo >= t_hi or e_lo >= e_hi; capacity < 0, then capacity beyond INT_MAX; more than
+ * 512 observers.
+ *   mcrat_hip_observe_events        one list: a stand-alone context, or a view of a pool (that list alone); time_now is the list's clock.  A
+ *                                   pending advance is flushed first.  MCRAT_HIP_ESTATE without photons, and on a pool.
+ *   mcrat_hip_pool_observe_events   every list of a pool, each with its own clock time_now[r]; it reads exactly what mcrat_hip_pool_observe_sky
+ *                                   reads, and like it flushes nothing a view holds pending.  MCRAT_HIP_ESTATE on a context that is no pool.
+ * Both calls synchronise once, before they return.  No photon column changes. */
+#define MCRAT_HIP_EVENTS_BY_PHOTON 0
+#define MCRAT_HIP_EVENTS_BY_TIME   1
+typedef struct mcrat_hip_events_observer {        /* inputs, host pointers */
+    int n_obs; const double *n0, *n1, *n2, *cos_acc;               /* [n_obs] */
+    const double *x0, *x1, *x2, *y0, *y1, *y2;                     /* [n_obs]: ex and ey; all six, or NULL */
+    double t_lo, t_hi, e_lo, e_hi;                                 /* the window: seconds, erg */
+    int order, stokes_frame;
+    long long capacity;                                            /* rows the column outputs have room for */
+} mcrat_hip_events_observer;
+typedef struct mcrat_hip_events {                 /* outputs, host pointers; any may be NULL */
+    int *rank, *slot;                                              /* [capacity] */
+    double *t, *e, *w, *s0, *s1, *s2, *s3, *X, *Y, *num_scatt;     /* [capacity] */
+    char *type;                                                    /* [capacity] */
+    long long *offsets;                                            /* [n_obs + 1] */
+    long long *n_events, *n_accepted, *n_outside, *n_frame_undefined;   /* [n_obs] */
+    long long n_total;
+    unsigned long long key_or, key_and;
+    int sort_passes_run, sort_passes_skipped;
+} mcrat_hip_events;
+int mcrat_hip_observe_events(mcrat_hip_ctx *ctx, const mcrat_hip_events_observer *obs, double time_now, mcrat_hip_events *out);
+int mcrat_hip_pool_observe_events(mcrat_hip_ctx *pool, const mcrat_hip_events_observer *obs, const double *time_now /* [n_ranks] */, mcrat_hip_events *out);
+
 /* introspection used by bench.py / tests -------------------------------------- */
 int mcrat_hip_synchronize(mcrat_hip_ctx *ctx);
-/* HBM held by the context: photons, staged frame, cell-lookup grid, loop state and the device blocks of all seven analysis products -- observe,
- * observe_sky, sightline_*, radiation_field, comoving_field, observe_escaping and observe_sky_resampled (the blocks of radiation_field and of observe_sky were left out
- * before they became one array).  A view holds no analysis block of its own: it uses its pool's, and they count there. */
+/* HBM held by the context: photons, staged frame, cell-lookup grid, loop state and the device blocks of all eight analysis products -- observe,
+ * observe_sky, sightline_*, radiation_field, comoving_field, observe_escaping, observe_sky_resampled and observe_events (the blocks of radiation_field
+ * and of observe_sky were left out before they became one array).  A view holds no analysis block of its own: it uses its pool's, and they count there. */
 size_t mcrat_hip_device_bytes(const mcrat_hip_ctx *ctx);
 int mcrat_hip_lookup_cell(mcrat_hip_ctx *ctx, int n, const double *a0, const double *a1, const double *a2, int *cell_out); /* device cell search == findContainingBlock geometry.c:350 */
 /* The staged frame's covered-octant table (one int per lookup bucket and octant, bucket-major: the cell that covers the octant, or -1): returns its

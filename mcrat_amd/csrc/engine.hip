@@ -23,6 +23,7 @@
 #include "sightline_plan.hpp"
 #include "escape_plan.hpp"
 #include "resample_plan.hpp"
+#include "events_plan.hpp"
 #include "radfield_plan.hpp"
 #include "comoving_plan.hpp"
 #include "photon_cols.hpp"
@@ -171,8 +172,9 @@ struct mcrat_hip_ctx {
     // the device blocks of the analysis products, each laid out by its plan header: mcrat_hip_observe (the cube, the per-observer counters and the
     // staged inputs), mcrat_hip_sightline_* (the output block and the caller's rays), mcrat_hip_radiation_field (head, accumulator and staged
     // edges), mcrat_hip_observe_sky (as observe), mcrat_hip_comoving_field (as radiation_field), mcrat_hip_observe_escaping (planes, counters, head, staged
-    // inputs and the compacted list), mcrat_hip_observe_sky_resampled (as observe, with a third counter).  A view uses its pool's (analysis_block).
-    enum AnalysisBlock { BLOCK_OBSERVE = 0, BLOCK_SIGHTLINE, BLOCK_RADFIELD, BLOCK_SKY, BLOCK_COMOVING, BLOCK_ESCAPE, BLOCK_RESAMPLE, N_ANALYSIS_BLOCKS };
+    // inputs and the compacted list), mcrat_hip_observe_sky_resampled (as observe, with a third counter), mcrat_hip_observe_events (head, staged
+    // observers, count table, row columns, the sort's buffers).  Eight products.  A view uses its pool's (analysis_block).
+    enum AnalysisBlock { BLOCK_OBSERVE = 0, BLOCK_SIGHTLINE, BLOCK_RADFIELD, BLOCK_SKY, BLOCK_COMOVING, BLOCK_ESCAPE, BLOCK_RESAMPLE, BLOCK_EVENTS, N_ANALYSIS_BLOCKS };
     struct DeviceBlock { void *buf = nullptr; size_t bytes = 0; } analysis[N_ANALYSIS_BLOCKS];
     int obs_path = 0;                 // the accumulation path of the last observation (ObservePath)
     int rf_path = 0;                  // the accumulation path of the last radiation field (ObservePath)
@@ -4582,6 +4584,133 @@ extern "C" int mcrat_hip_pool_observe_sky_resampled(mcrat_hip_ctx *c, const mcra
 }
 
 extern "C" int mcrat_hip_observe_sky_resampled_path(const mcrat_hip_ctx *c) { return c ? c->rs_path : 0; }
+
+// ---------------------------------------------------------------------------------------------- detected-photon event lists
+// The photons of c->ph -- n_slots of them -- as rows per observer (events_plan.hpp, events.hip): check, block, stage, the launches, the read-back, one
+// synchronise, the counters handed over.  clocks: one per slots_per_clock slots (a rank pool's lists), or nullptr and time_now for all.  rank_base,
+// rank_stride: the photons' identities (launch.hpp, ResampleDev).
+static int events_run(mcrat_hip_ctx *c, const mcrat_hip_events_observer *obs, int n_slots, const double *clocks, int n_clocks, int slots_per_clock, double time_now,
+                      int rank_base, int rank_stride, mcrat_hip_events *out)
+{
+    if (!obs->n0 || !obs->n1 || !obs->n2 || !obs->cos_acc) {
+        c->last_error = "observe_events: a null array in mcrat_hip_events_observer";
+        return MCRAT_HIP_EINVAL;
+    }
+    const EventsArgs args{obs->n_obs, obs->n0, obs->n1, obs->n2, obs->cos_acc, obs->x0, obs->x1, obs->x2, obs->y0, obs->y1, obs->y2,
+                          obs->t_lo, obs->t_hi, obs->e_lo, obs->e_hi, obs->order, obs->stokes_frame, obs->capacity, out->X != nullptr || out->Y != nullptr};
+    EventsPlan plan;
+    const EventsRefusal why = events_plan(args, &plan);
+    if (why != EVENTS_OK) {
+        char text[EVENTS_TEXT_BYTES];
+        c->last_error = events_refusal_text(why, text);
+        return MCRAT_HIP_EINVAL;
+    }
+    const EventsLayout lay = events_layout(plan, n_slots, clocks ? n_clocks : 0);
+    char *d = nullptr;
+    int rc = analysis_block(c, nullptr, mcrat_hip_ctx::BLOCK_EVENTS, lay.total_bytes, &d);
+    if (rc) return rc;
+
+    // the observers in the order the kernels read them, the clocks in their own part of the block
+    const size_t n_obs = (size_t)plan.n_obs;
+    std::vector<double> in;
+    in.reserve(plan.staged_doubles);
+    for (const double *v : {args.n0, args.n1, args.n2, args.cos_acc}) in.insert(in.end(), v, v + n_obs);
+    if (plan.axes)
+        for (const double *v : {args.x0, args.x1, args.x2, args.y0, args.y1, args.y2}) in.insert(in.end(), v, v + n_obs);
+    HIPCHK(c, hipMemsetAsync(d, 0, 8 * plan.head_words, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + lay.staged_offset, in.data(), sizeof(double) * in.size(), hipMemcpyHostToDevice, c->stream));
+    if (clocks) HIPCHK(c, hipMemcpyAsync(d + lay.clocks_offset, clocks, sizeof(double) * (size_t)n_clocks, hipMemcpyHostToDevice, c->stream));
+
+    EventsDev a{};
+    a.n_slots = n_slots; a.n_obs = plan.n_obs; a.n_chunks = events_n_chunks(n_slots); a.chunk_slots = events_chunk_slots(n_slots);
+    a.order = plan.order; a.sky_plane = plan.frame == STOKES_SKY_PLANE ? 1 : 0; a.axes = plan.axes ? 1 : 0;
+    a.capacity = plan.capacity; a.n_tiles = plan.order == EVENTS_BY_TIME ? events_sort_tiles(plan.capacity) : 0;
+    a.t_lo = args.t_lo; a.t_hi = args.t_hi; a.e_lo = args.e_lo; a.e_hi = args.e_hi;
+    a.rank_base = rank_base; a.rank_stride = rank_stride;
+    a.staged = reinterpret_cast<const double *>(d + lay.staged_offset);
+    a.clocks = clocks ? reinterpret_cast<const double *>(d + lay.clocks_offset) : nullptr;
+    a.slots_per_clock = slots_per_clock;
+    a.time_now = time_now;
+    unsigned long long *head = reinterpret_cast<unsigned long long *>(d);
+    a.n_accepted = head; a.n_outside = head + n_obs; a.n_undefined = head + 2 * n_obs;
+    a.offsets = head + events_head_offsets_word(plan);
+    a.key_or = head + events_head_or_word(plan); a.key_nand = a.key_or + 1;
+    a.table = reinterpret_cast<unsigned long long *>(d + lay.table_offset);
+    a.rank = reinterpret_cast<int *>(d + lay.rank_offset); a.slot = reinterpret_cast<int *>(d + lay.slot_offset);
+    double **f8[EVENTS_F8_COLUMNS] = {&a.t, &a.e, &a.w, &a.s0, &a.s1, &a.s2, &a.s3, &a.num_scatt, &a.X, &a.Y};
+    for (int k = 0; k < (plan.axes ? EVENTS_F8_COLUMNS : EVENTS_F8_COLUMNS - 2); ++k) *f8[k] = reinterpret_cast<double *>(d + lay.f8_offset + lay.f8_pitch * (size_t)k);
+    a.type = d + lay.type_offset;
+    if (plan.order == EVENTS_BY_TIME) {
+        a.sort_table = reinterpret_cast<unsigned *>(d + lay.sort_table_offset);
+        a.source = reinterpret_cast<unsigned *>(d + lay.source_offset);
+        for (int b = 0; b < 2; ++b) {
+            a.keys[b] = reinterpret_cast<unsigned long long *>(d + lay.keys_offset + lay.keys_pitch * (size_t)b);
+            a.index[b] = reinterpret_cast<unsigned *>(d + lay.index_offset + lay.index_pitch * (size_t)b);
+        }
+    }
+    HIPCHK(c, launch_events(c->ph, a, plan, c->kc.stokes != 0, c->stream));
+
+    // the head in one copy; every column that is asked for in full (what lies behind n_total is unspecified)
+    std::vector<unsigned long long> host(plan.head_words);
+    HIPCHK(c, hipMemcpyAsync(host.data(), d, 8 * plan.head_words, hipMemcpyDeviceToHost, c->stream));
+    const size_t cap = (size_t)plan.capacity;
+    if (cap) {
+        if (out->rank) HIPCHK(c, hipMemcpyAsync(out->rank, a.rank, sizeof(int) * cap, hipMemcpyDeviceToHost, c->stream));
+        if (out->slot) HIPCHK(c, hipMemcpyAsync(out->slot, a.slot, sizeof(int) * cap, hipMemcpyDeviceToHost, c->stream));
+        double *wanted[EVENTS_F8_COLUMNS] = {out->t, out->e, out->w, out->s0, out->s1, out->s2, out->s3, out->num_scatt, out->X, out->Y};
+        for (int k = 0; k < (plan.axes ? EVENTS_F8_COLUMNS : EVENTS_F8_COLUMNS - 2); ++k)
+            if (wanted[k]) HIPCHK(c, hipMemcpyAsync(wanted[k], *f8[k], sizeof(double) * cap, hipMemcpyDeviceToHost, c->stream));
+        if (out->type) HIPCHK(c, hipMemcpyAsync(out->type, a.type, cap, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+
+    static_assert(sizeof(long long) == 8, "the counters and offsets are handed over as they are");
+    const unsigned long long *offsets = host.data() + events_head_offsets_word(plan);
+    long long *per_observer[EVENTS_COUNTERS] = {out->n_accepted, out->n_outside, out->n_frame_undefined};
+    for (int k = 0; k < EVENTS_COUNTERS; ++k)
+        if (per_observer[k]) memcpy(per_observer[k], host.data() + n_obs * (size_t)k, 8 * n_obs);
+    if (out->offsets) memcpy(out->offsets, offsets, 8 * (n_obs + 1));
+    if (out->n_events)
+        for (size_t o = 0; o < n_obs; ++o) out->n_events[o] = (long long)(offsets[o + 1] - offsets[o]);
+    out->n_total = (long long)offsets[n_obs];
+    out->key_or = host[events_head_or_word(plan)];
+    out->key_and = ~host[events_head_or_word(plan) + 1];
+    out->sort_passes_run = out->sort_passes_skipped = 0;
+    const bool fits = out->n_total <= (long long)plan.capacity;
+    if (plan.order == EVENTS_BY_TIME && out->n_total > 0 && fits) {
+        EventsPass launched[EVENTS_MAX_PASSES], run[EVENTS_MAX_PASSES];
+        const int n_launched = events_launch_list(plan.n_obs, launched);
+        out->sort_passes_run = events_pass_list(out->key_or, out->key_and, plan.n_obs, run);
+        out->sort_passes_skipped = n_launched - out->sort_passes_run;
+    }
+    const bool counting = plan.capacity == 0 && !out->rank && !out->slot && !out->t && !out->e && !out->w && !out->s0 && !out->s1 && !out->s2 && !out->s3 &&
+                          !out->X && !out->Y && !out->num_scatt && !out->type;
+    if (!fits && !counting) {
+        char text[EVENTS_TEXT_BYTES];
+        snprintf(text, sizeof text, "observe_events: the list has %lld rows, capacity is %d: no row is to be trusted (the counters are exact)", out->n_total, plan.capacity);
+        c->last_error = text;
+        return MCRAT_HIP_EREFUSED;
+    }
+    return MCRAT_HIP_OK;
+}
+
+extern "C" int mcrat_hip_observe_events(mcrat_hip_ctx *c, const mcrat_hip_events_observer *obs, double time_now, mcrat_hip_events *out)
+{
+    if (!c || !obs || !out) return MCRAT_HIP_EINVAL;
+    if (!c->have_photons) return MCRAT_HIP_ESTATE;
+    if (c->is_pool) { c->last_error = "observe_events: a rank pool's lists have clocks of their own (mcrat_hip_pool_observe_events, or mcrat_hip_observe_events on a view)"; return MCRAT_HIP_ESTATE; }
+    int rc = flush_pending(c);
+    if (rc) return rc;
+    return events_run(c, obs, c->ph.n, nullptr, 0, 1, time_now, c->parent ? c->view_rank : 0, 0, out);
+}
+
+extern "C" int mcrat_hip_pool_observe_events(mcrat_hip_ctx *c, const mcrat_hip_events_observer *obs, const double *time_now, mcrat_hip_events *out)
+{
+    if (!c || !obs || !time_now || !out) return MCRAT_HIP_EINVAL;
+    if (!c->is_pool) { c->last_error = "pool_observe_events: the context is no rank pool"; return MCRAT_HIP_ESTATE; }
+    // every slot of the pool, exactly as mcrat_hip_pool_observe_sky reads them, and like it without flush_pending
+    return events_run(c, obs, c->ph.n, time_now, c->n_ranks, c->rank_stride, 0.0, 0, c->rank_stride, out);
+}
 
 // ---------------------------------------------------------------------------------------------- the radiation field on the hydro mesh
 // The checks of radfield_plan.hpp on the caller's bins, then the frame: *h is the context whose staged frame the photons are located in, *plan the

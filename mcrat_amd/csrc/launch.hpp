@@ -228,6 +228,34 @@ struct ResampleDev {
     unsigned long long *n_accepted, *n_outside, *n_undefined;   // [n_obs]
 };
 hipError_t launch_resample(const PhotonDev &ph, const ResampleDev &a, const ResamplePlan &plan, bool stokes, int blocks_x, int blocks_y, hipStream_t stream);
+// detected-photon event lists (events.hip): the accepted (photon, observer) pairs inside a window of detection time and energy as rows, ordered by
+// (observer, rank, slot) or by (observer, key(t_det), rank, slot) -- count, scan, write and, for BY_TIME, a stable radix sort of (key, row) pairs and
+// one gather, all on one stream with no host round trip.  The block is laid out as events_plan.hpp says; the caller zeroes the head and copies the
+// staged observers and the clocks.  Clocks and a photon's identity as in ResampleDev.
+struct EventsPlan;
+struct EventsDev {
+    int n_slots, n_obs, n_chunks, chunk_slots;
+    int order, sky_plane, axes;          // EventsOrder; whether Q and U are carried into the observer's frame; whether ex and ey are staged
+    int capacity, n_tiles;               // rows there is room for; tiles of the sort (BY_TIME)
+    double t_lo, t_hi, e_lo, e_hi;
+    int rank_base, rank_stride;
+    const double *staged;                // n0, n1, n2, cos_acc [n_obs each]; (axes) x0 .. x2, y0 .. y2 [n_obs each]
+    const double *clocks;
+    int slots_per_clock;
+    double time_now;
+    unsigned long long *n_accepted, *n_outside, *n_undefined;   // [n_obs]
+    unsigned long long *offsets;         // [n_obs + 1]; offsets[n_obs]: n_total
+    unsigned long long *key_or, *key_nand;   // the OR of all event keys and of all inverted event keys
+    unsigned long long *table;           // [n_obs][n_chunks]: the events of a chunk, after the scan the chunk's first row
+    int *rank, *slot;                    // the row columns, [capacity] each
+    double *t, *e, *w, *s0, *s1, *s2, *s3, *num_scatt, *X, *Y;
+    char *type;
+    unsigned *sort_table;                // [EVENTS_DIGITS][n_tiles] (BY_TIME, like all that follows)
+    unsigned *source;                    // the pool slot behind each unsorted row
+    unsigned long long *keys[2];
+    unsigned *index[2];
+};
+hipError_t launch_events(const PhotonDev &ph, const EventsDev &a, const EventsPlan &plan, bool stokes, hipStream_t stream);
 hipError_t launch_init_states_multi(LoopState *ranks, int n_ranks, const int *open, const double *time_now, const double *remaining, hipStream_t stream);
 hipError_t launch_aos_to_soa(const void *aos, const PhotonDev &ph, int n, hipStream_t stream);
 // many lists of a rank pool at once: desc = `count` device records {int rank, int n, long long first record in aos}; the rest of each window is cleared

@@ -273,6 +273,81 @@ STOKES_AS_STORED, STOKES_SKY_PLANE = 0, 1                             # mcrat_hi
 RESAMPLE_PATH_LDS, RESAMPLE_PATH_GLOBAL, RESAMPLE_PATH_SLICED = 1, 2, 3      # mcrat_hip_observe_sky_resampled_path
 
 
+class EventsObserver(C.Structure):
+    """mcrat_hip_events_observer: the observers' directions, cones and optional sky-plane vectors, the window, the order, the Stokes frame and the
+    rows there is room for"""
+    _fields_ = [("n_obs", C.c_int), ("n0", _dp), ("n1", _dp), ("n2", _dp), ("cos_acc", _dp),
+                ("x0", _dp), ("x1", _dp), ("x2", _dp), ("y0", _dp), ("y1", _dp), ("y2", _dp),
+                ("t_lo", C.c_double), ("t_hi", C.c_double), ("e_lo", C.c_double), ("e_hi", C.c_double),
+                ("order", C.c_int), ("stokes_frame", C.c_int), ("capacity", C.c_longlong)]
+
+
+EVENTS_F8_COLUMNS = ("t", "e", "w", "s0", "s1", "s2", "s3", "X", "Y", "num_scatt")
+EVENTS_COUNTERS = ("n_events", "n_accepted", "n_outside", "n_frame_undefined")
+
+
+class Events(C.Structure):
+    """mcrat_hip_events: the row columns, each [capacity], offsets [n_obs + 1], the per-observer counters and the call's figures"""
+    _fields_ = ([("rank", _ip), ("slot", _ip)] + [(k, _dp) for k in EVENTS_F8_COLUMNS] + [("type", C.c_char_p), ("offsets", C.POINTER(C.c_longlong))] +
+                [(k, C.POINTER(C.c_longlong)) for k in EVENTS_COUNTERS] +
+                [("n_total", C.c_longlong), ("key_or", C.c_ulonglong), ("key_and", C.c_ulonglong), ("sort_passes_run", C.c_int), ("sort_passes_skipped", C.c_int)])
+
+
+EVENTS_BY_PHOTON, EVENTS_BY_TIME = 0, 1                               # mcrat_hip_events_observer.order
+
+
+def bin_events(res, t_edges, e_edges, x_edges=None, y_edges=None):
+    """An event list (Engine.observe_events) binned on the host -> dict with the seven planes count, w, we, i, q, u, v, each (n_obs, n_t, n_e) or with
+    x_edges and y_edges (n_obs, n_t, n_e, n_y, n_x), and n_outside (n_obs,), as Engine.observe_sky gives them: bin k of an axis holds
+    edges[k] <= x < edges[k + 1]; n_outside counts the accepted pairs in no bin -- those outside the list's window and the rows outside an axis."""
+    def find(edges, x):
+        edges = np.asarray(edges, dtype=np.float64)
+        k = np.searchsorted(edges, x, side="right") - 1
+        return np.where((k >= 0) & (k < len(edges) - 1) & (x == x), k, -1), len(edges) - 1
+    image = x_edges is not None
+    if image != (y_edges is not None):
+        raise ValueError("bin_events: x_edges and y_edges come together")
+    if image and "X" not in res:
+        raise ValueError("bin_events: the list has no X and Y columns (observe_events without ex and ey)")
+    offsets = np.asarray(res["offsets"])
+    n_obs, n = len(offsets) - 1, int(offsets[-1])
+    (it, n_t), (ie, n_e) = find(t_edges, res["t"][:n]), find(e_edges, res["e"][:n])
+    (ix, n_x), (iy, n_y) = (find(x_edges, res["X"][:n]), find(y_edges, res["Y"][:n])) if image else ((np.zeros(n, dtype=np.int64), 1), (np.zeros(n, dtype=np.int64), 1))
+    o = np.repeat(np.arange(n_obs), np.diff(offsets))
+    inside = (it >= 0) & (ie >= 0) & (ix >= 0) & (iy >= 0)
+    per_obs = n_t * n_e * n_y * n_x
+    flat = (o * per_obs + ((it * n_e + ie) * n_y + iy) * n_x + ix)[inside]
+    shape = (n_obs, n_t, n_e, n_y, n_x) if image else (n_obs, n_t, n_e)
+    w = np.asarray(res["w"][:n], dtype=np.float64)
+    out = {"count": np.bincount(flat, minlength=n_obs * per_obs).astype(np.int64).reshape(shape)}
+    for k, term in (("w", w), ("we", w * res["e"][:n]), ("i", w * res["s0"][:n]), ("q", w * res["s1"][:n]), ("u", w * res["s2"][:n]), ("v", w * res["s3"][:n])):
+        out[k] = np.bincount(flat, weights=term[inside], minlength=n_obs * per_obs).reshape(shape)
+    out["n_outside"] = np.asarray(res["n_outside"], dtype=np.int64) + np.bincount(o[~inside], minlength=n_obs).astype(np.int64)
+    return out
+
+
+def event_durations(res, fractions=(0.05, 0.95), weight="we"):
+    """Per observer of an event list the detection times at which the cumulative weight reaches the given fractions of its total -- T90 is the
+    difference of the pair for (0.05, 0.95), T50 that for (0.25, 0.75).  weight: "we" the fluence w * e, "w" the photon number, "count" the rows.
+    The rows are taken in the order of (t, row); the time for fraction f is that of the first row at which the running sum is >= f * total.
+    -> a list with one array (len(fractions),) per observer, None for an observer without events."""
+    if weight not in ("we", "w", "count"):
+        raise ValueError("event_durations: weight takes we, w and count, not %r" % (weight,))
+    offsets = np.asarray(res["offsets"])
+    out = []
+    for a, b in zip(offsets[:-1], offsets[1:]):
+        if b == a:
+            out.append(None)
+            continue
+        t = np.asarray(res["t"][a:b], dtype=np.float64)
+        order = np.argsort(t, kind="stable")
+        term = np.ones(b - a) if weight == "count" else np.asarray(res["w"][a:b], dtype=np.float64) * (res["e"][a:b] if weight == "we" else 1.0)
+        run = np.cumsum(term[order])
+        first = np.minimum(np.searchsorted(run, np.asarray(fractions, dtype=np.float64) * run[-1], side="left"), b - a - 1)
+        out.append(t[order][first])
+    return out
+
+
 def _wrap_half_pi(d):
     """an angle difference into (-pi/2, pi/2]: polarisation angles are defined modulo pi"""
     return d - np.pi * np.ceil((d - 0.5 * np.pi) / np.pi)
@@ -498,6 +573,8 @@ SYMBOLS = {
     "mcrat_hip_observe_sky_resampled": (C.c_int, [_ctx, C.POINTER(ResampleObserver), C.c_double, C.POINTER(ResampleObservation)]),
     "mcrat_hip_pool_observe_sky_resampled": (C.c_int, [_ctx, C.POINTER(ResampleObserver), _dp, C.POINTER(ResampleObservation)]),
     "mcrat_hip_observe_sky_resampled_path": (C.c_int, [_ctx]),
+    "mcrat_hip_observe_events": (C.c_int, [_ctx, C.POINTER(EventsObserver), C.c_double, C.POINTER(Events)]),
+    "mcrat_hip_pool_observe_events": (C.c_int, [_ctx, C.POINTER(EventsObserver), _dp, C.POINTER(Events)]),
     "mcrat_hip_synchronize": (C.c_int, [_ctx]),
     "mcrat_hip_device_bytes": (C.c_size_t, [_ctx]),
     "mcrat_hip_eval_function": (C.c_int, [_ctx, C.c_int, C.c_int, _dp, _dp, C.c_uint64]),
@@ -1414,6 +1491,75 @@ class Engine:
         """how the last resampled sky observation of this context was accumulated: RESAMPLE_PATH_LDS, RESAMPLE_PATH_SLICED, RESAMPLE_PATH_GLOBAL,
         0: none yet"""
         return int(self.lib.mcrat_hip_observe_sky_resampled_path(self.ctx))
+
+    # ---- detected-photon event lists: time-ordered rows per observer (include/mcrat_hip.h)
+    def _observe_events(self, call, what, n, cos_acc, time_now, order, stokes_frame, ex, ey, t_window, e_window, capacity):
+        t_window, e_window = (t_window or (-np.inf, np.inf)), (e_window or (-np.inf, np.inf))
+        sky, _alive, _, _ = self._sky_observer(what, n, cos_acc, [0.0, 1.0], [0.0, 1.0], ex, ey, None, None)
+        axes = ex is not None and ey is not None
+        obs = EventsObserver(sky.n_obs, sky.n0, sky.n1, sky.n2, sky.cos_acc, sky.x0, sky.x1, sky.x2, sky.y0, sky.y1, sky.y2,
+                             float(t_window[0]), float(t_window[1]), float(e_window[0]), float(e_window[1]), int(order), int(stokes_frame), 0)
+        n_obs = max(sky.n_obs, 0)
+
+        def one(cap, rows):
+            obs.capacity = cap
+            res = {"offsets": np.zeros(n_obs + 1, dtype=np.int64)}
+            for k in EVENTS_COUNTERS:
+                res[k] = np.zeros(n_obs, dtype=np.int64)
+            out = Events()
+            ll = C.POINTER(C.c_longlong)
+            out.offsets = res["offsets"].ctypes.data_as(ll)
+            for k in EVENTS_COUNTERS:
+                setattr(out, k, res[k].ctypes.data_as(ll))
+            if rows:
+                m = max(int(cap), 0)
+                res["rank"], res["slot"] = np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int32)
+                out.rank, out.slot = res["rank"].ctypes.data_as(_ip), res["slot"].ctypes.data_as(_ip)
+                for k in EVENTS_F8_COLUMNS:
+                    if k in ("X", "Y") and not axes:
+                        continue
+                    res[k] = np.zeros(m)
+                    setattr(out, k, res[k].ctypes.data_as(_dp))
+                res["type"] = np.zeros(m, dtype="S1")
+                out.type = C.cast(res["type"].ctypes.data, C.c_char_p)
+            rc = call(self.ctx, C.byref(obs), time_now, C.byref(out))
+            res.update(n_total=int(out.n_total), key_or=int(out.key_or), key_and=int(out.key_and), sort_passes_run=int(out.sort_passes_run),
+                       sort_passes_skipped=int(out.sort_passes_skipped))
+            return rc, res
+
+        if capacity is None:
+            rc, counted = one(0, False)
+            self._check(rc, what)
+            capacity = counted["n_total"]
+        rc, res = one(int(capacity), True)
+        self.last_events = res                   # (a refused call's counters are exact: kept for the caller that catches the error)
+        self._check(rc, what)
+        for k in ("rank", "slot", "type") + EVENTS_F8_COLUMNS:
+            if k in res:
+                res[k] = res[k][:res["n_total"]]
+        return res
+
+    def observe_events(self, n, cos_acc, time_now, order=EVENTS_BY_TIME, stokes_frame=STOKES_AS_STORED, ex=None, ey=None, t_window=None, e_window=None,
+                       capacity=None):
+        """the photons each observer detects as rows (mcrat_hip_observe_events): every accepted (photon, observer) pair with
+        t_window[0] <= t_det < t_window[1] and e_window[0] <= e < e_window[1] (None: no bound), observer o's rows at [offsets[o], offsets[o + 1]),
+        ordered by (rank, slot) -- EVENTS_BY_PHOTON -- or by (t_det, rank, slot) -- EVENTS_BY_TIME.  n, ex, ey: (3, n_obs) as for observe_sky; with
+        ex and ey the rows have X and Y, and STOKES_SKY_PLANE carries s1, s2 into the observer's frame.  capacity: the rows there is room for; None
+        asks the device for the count first.  -> dict of the columns rank, slot, t, e, w, s0 .. s3, [X, Y,] num_scatt, type (n_total rows each),
+        offsets (n_obs + 1,), the per-observer n_events, n_accepted, n_outside, n_frame_undefined, and n_total, key_or, key_and, sort_passes_run,
+        sort_passes_skipped.  A list beyond `capacity` raises McratHipError; its exact counters are in self.last_events.  bin_events and
+        event_durations work on the result."""
+        return self._observe_events(self.lib.mcrat_hip_observe_events, "observe_events", n, cos_acc, float(time_now), order, stokes_frame, ex, ey, t_window,
+                                    e_window, capacity)
+
+    def pool_observe_events(self, n, cos_acc, time_now, order=EVENTS_BY_TIME, stokes_frame=STOKES_AS_STORED, ex=None, ey=None, t_window=None, e_window=None,
+                            capacity=None):
+        """every list of the pool as one event list, list r at its own clock time_now[r] (mcrat_hip_pool_observe_events)"""
+        tn = _f8(time_now).ravel()
+        if len(tn) != self.n_pool_ranks:
+            raise ValueError("pool_observe_events: time_now needs one clock per rank of the pool")
+        return self._observe_events(self.lib.mcrat_hip_pool_observe_events, "pool_observe_events", n, cos_acc, tn.ctypes.data_as(_dp), order, stokes_frame, ex, ey,
+                                    t_window, e_window, capacity)
 
     # ---- line-of-sight optical depths and photospheres (include/mcrat_hip.h)
     def _sightlines(self, what, n, call, step_frac, h_min, max_steps, tau_stop, surface_level):
