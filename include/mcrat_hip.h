@@ -1241,10 +1241,59 @@ typedef struct mcrat_hip_events {                 /* outputs, host pointers; any
 int mcrat_hip_observe_events(mcrat_hip_ctx *ctx, const mcrat_hip_events_observer *obs, double time_now, mcrat_hip_events *out);
 int mcrat_hip_pool_observe_events(mcrat_hip_ctx *pool, const mcrat_hip_events_observer *obs, const double *time_now /* [n_ranks] */, mcrat_hip_events *out);
 
+/* spectral fits: Band function and cutoff power law, every row of a cube at once ---
+ * What comes after a spectrum: every row of a [n_spec][n_e] pair (count, w) -- an observer, a time bin and a jackknife or bootstrap entry each, as
+ * the observe calls give them -- fitted to a cutoff power law (MCRAT_HIP_FIT_COMP) or a Band function (MCRAT_HIP_FIT_BAND) by a deterministic,
+ * derivative-free chi^2 search.  The arrays are host arrays: the call uploads them, fits on the device -- a wavefront per spectrum -- and copies the
+ * columns back.  It reads no photon and no frame; any context will do.
+ * Data.  Bin i has the edges e_edges[i], e_edges[i + 1] (erg) and the width dE_i.  log_e[i] = ln(E_i / e_piv) at the geometric centre is an input,
+ * so that every implementation sees the same bits.  y_i = w_i / dE_i, the weight g_i = count_i / y_i^2 (sigma_i = y_i / sqrt(count_i)).  A bin is
+ * used iff count_i >= min_count, w_i is finite and w_i > 0; the used bins are compacted in bin order.  With fewer used bins than parameters + 1
+ * (COMP 2, BAND 3) the status is MCRAT_HIP_FIT_TOO_FEW_BINS, the double outputs are NaN and no search runs.
+ * Models, in u = (alpha, lambda, beta), lambda = ln(E_pk / e_piv): with x_i = (2 + alpha) exp(L_i - lambda), COMP is ln m_i = alpha L_i - x_i; BAND
+ * the same where x_i < alpha - beta and ln m_i = (alpha - beta)(ln(alpha - beta) - ln(2 + alpha) + lambda - 1) + beta L_i elsewhere.  A candidate
+ * with 2 + alpha <= 0 or (BAND) alpha <= beta has chi^2 = +inf.  The amplitude is profiled out: A = sum g y m / sum g m^2, chi^2 = sum g (y - A m)^2,
+ * two passes over the used bins in order.  exp and log are fixed sequences of IEEE operations (fit_plan.hpp: fit_exp, fit_log; within 4 ulp).
+ * Search.  Round 0: the cell centres of a grid of g_alpha x g_lambda x g_beta cells over the bounds (COMP: g_beta counts as 1).  Rounds
+ * 1 .. n_rounds: 4 x 4 x 4 (BAND) or 8 x 8 (COMP) cell centres of a box whose side is the previous side times shrink, centred on the best candidate
+ * of all rounds so far and shifted, not clipped, into the bounds.  Best: the lowest chi^2; among equals the earliest round, then the lowest index
+ * (alpha fastest).  Every operation and its order are fit_plan.hpp's: the outputs are bit-reproducible, on the device, in g++ and in NumPy.
+ * Outputs, [n_spec] each, any may be NULL: alpha; beta (NaN for COMP); e_peak = e_piv * exp(lambda); amplitude; chi2; n_used; dof = n_used -
+ * parameters; status, a bit set: TOO_FEW_BINS; AT_BOUND_ALPHA, _LAMBDA, _BETA -- the result lies within one cell of the last round of a bound --;
+ * NO_FINITE_CANDIDATE -- no candidate had a finite chi^2: chi2 is +inf, the other doubles NaN.
+ * MCRAT_HIP_EINVAL, each with its own text in mcrat_hip_last_error, prefixed "fit_spectra:", checked in this order: model; a NULL array; n_e < 1 or
+ * above 512; an edge not finite, the edges not strictly ascending, not positive; log_e not finite; e_piv not positive and finite; a bound not
+ * finite, lo >= hi, no candidate allowed (alpha_hi <= -2, or BAND alpha_hi <= beta_lo); a grid count < 1, the coarse grid above 2^20 candidates;
+ * n_rounds outside [0, 4096]; shrink outside (0.25, 1); min_count < 1; n_spec outside [0, INT_MAX].  COMP does not read beta's bounds.
+ * The call synchronises the stream twice: before it sizes its device block, and before it returns. */
+#define MCRAT_HIP_FIT_COMP 0
+#define MCRAT_HIP_FIT_BAND 1
+#define MCRAT_HIP_FIT_TOO_FEW_BINS         1
+#define MCRAT_HIP_FIT_AT_BOUND_ALPHA       2
+#define MCRAT_HIP_FIT_AT_BOUND_LAMBDA      4
+#define MCRAT_HIP_FIT_AT_BOUND_BETA        8
+#define MCRAT_HIP_FIT_NO_FINITE_CANDIDATE 16
+typedef struct mcrat_hip_fit_args {               /* inputs, host pointers */
+    int model;
+    long long n_spec; int n_e;
+    const long long *count; const double *w;                       /* [n_spec][n_e] */
+    const double *e_edges, *log_e;                                 /* [n_e + 1] (erg), [n_e] */
+    double e_piv;                                                  /* erg */
+    double alpha_lo, alpha_hi, lambda_lo, lambda_hi, beta_lo, beta_hi;
+    int g_alpha, g_lambda, g_beta, n_rounds;
+    double shrink;
+    long long min_count;
+} mcrat_hip_fit_args;
+typedef struct mcrat_hip_fit_result {             /* outputs, host pointers; any may be NULL */
+    double *alpha, *beta, *e_peak, *amplitude, *chi2;              /* [n_spec] */
+    int *n_used, *dof, *status;                                    /* [n_spec] */
+} mcrat_hip_fit_result;
+int mcrat_hip_fit_spectra(mcrat_hip_ctx *ctx, const mcrat_hip_fit_args *args, mcrat_hip_fit_result *out);
+
 /* introspection used by bench.py / tests -------------------------------------- */
 int mcrat_hip_synchronize(mcrat_hip_ctx *ctx);
-/* HBM held by the context: photons, staged frame, cell-lookup grid, loop state and the device blocks of all eight analysis products -- observe,
- * observe_sky, sightline_*, radiation_field, comoving_field, observe_escaping, observe_sky_resampled and observe_events (the blocks of radiation_field
+/* HBM held by the context: photons, staged frame, cell-lookup grid, loop state and the device blocks of all nine analysis products -- observe,
+ * observe_sky, sightline_*, radiation_field, comoving_field, observe_escaping, observe_sky_resampled, observe_events and fit_spectra (the blocks of radiation_field
  * and of observe_sky were left out before they became one array).  A view holds no analysis block of its own: it uses its pool's, and they count there. */
 size_t mcrat_hip_device_bytes(const mcrat_hip_ctx *ctx);
 int mcrat_hip_lookup_cell(mcrat_hip_ctx *ctx, int n, const double *a0, const double *a1, const double *a2, int *cell_out); /* device cell search == findContainingBlock geometry.c:350 */

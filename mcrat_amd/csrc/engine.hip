@@ -24,6 +24,7 @@
 #include "escape_plan.hpp"
 #include "resample_plan.hpp"
 #include "events_plan.hpp"
+#include "fit_plan.hpp"
 #include "radfield_plan.hpp"
 #include "comoving_plan.hpp"
 #include "photon_cols.hpp"
@@ -173,8 +174,9 @@ struct mcrat_hip_ctx {
     // staged inputs), mcrat_hip_sightline_* (the output block and the caller's rays), mcrat_hip_radiation_field (head, accumulator and staged
     // edges), mcrat_hip_observe_sky (as observe), mcrat_hip_comoving_field (as radiation_field), mcrat_hip_observe_escaping (planes, counters, head, staged
     // inputs and the compacted list), mcrat_hip_observe_sky_resampled (as observe, with a third counter), mcrat_hip_observe_events (head, staged
-    // observers, count table, row columns, the sort's buffers).  Eight products.  A view uses its pool's (analysis_block).
-    enum AnalysisBlock { BLOCK_OBSERVE = 0, BLOCK_SIGHTLINE, BLOCK_RADFIELD, BLOCK_SKY, BLOCK_COMOVING, BLOCK_ESCAPE, BLOCK_RESAMPLE, BLOCK_EVENTS, N_ANALYSIS_BLOCKS };
+    // observers, count table, row columns, the sort's buffers), mcrat_hip_fit_spectra (the edges, log_e, the spectra and the output columns).  Nine
+    // products.  A view uses its pool's (analysis_block).
+    enum AnalysisBlock { BLOCK_OBSERVE = 0, BLOCK_SIGHTLINE, BLOCK_RADFIELD, BLOCK_SKY, BLOCK_COMOVING, BLOCK_ESCAPE, BLOCK_RESAMPLE, BLOCK_EVENTS, BLOCK_FIT, N_ANALYSIS_BLOCKS };
     struct DeviceBlock { void *buf = nullptr; size_t bytes = 0; } analysis[N_ANALYSIS_BLOCKS];
     int obs_path = 0;                 // the accumulation path of the last observation (ObservePath)
     int rf_path = 0;                  // the accumulation path of the last radiation field (ObservePath)
@@ -4710,6 +4712,50 @@ extern "C" int mcrat_hip_pool_observe_events(mcrat_hip_ctx *c, const mcrat_hip_e
     if (!c->is_pool) { c->last_error = "pool_observe_events: the context is no rank pool"; return MCRAT_HIP_ESTATE; }
     // every slot of the pool, exactly as mcrat_hip_pool_observe_sky reads them, and like it without flush_pending
     return events_run(c, obs, c->ph.n, time_now, c->n_ranks, c->rank_stride, 0.0, 0, c->rank_stride, out);
+}
+
+// ---------------------------------------------------------------------------------------------- spectral fits
+// Every row of (count, W) fitted to a cutoff power law or a Band function (fit_plan.hpp, fit.hip): check, block, the inputs copied, one launch, the
+// output columns read back, one synchronise.  The call reads no photon and no frame: any context will do, a view uses its pool's block.
+extern "C" int mcrat_hip_fit_spectra(mcrat_hip_ctx *c, const mcrat_hip_fit_args *args, mcrat_hip_fit_result *out)
+{
+    if (!c || !args || !out) return MCRAT_HIP_EINVAL;
+    const FitArgs fa{args->model, args->n_spec, args->n_e, args->count, args->w, args->e_edges, args->log_e, args->e_piv,
+                     args->alpha_lo, args->alpha_hi, args->lambda_lo, args->lambda_hi, args->beta_lo, args->beta_hi,
+                     args->g_alpha, args->g_lambda, args->g_beta, args->n_rounds, args->shrink, args->min_count};
+    FitPlan plan;
+    const FitRefusal why = fit_plan(fa, &plan);
+    if (why != FIT_OK) { c->last_error = fit_refusal_text(why); return MCRAT_HIP_EINVAL; }
+    char *d = nullptr;
+    int rc = analysis_block(c, nullptr, mcrat_hip_ctx::BLOCK_FIT, plan.total_bytes, &d);
+    if (rc) return rc;
+    const size_t cells = (size_t)plan.n_spec * (size_t)plan.n_e, rows = (size_t)plan.n_spec;
+    HIPCHK(c, hipMemcpyAsync(d + plan.edges_offset, fa.e_edges, 8 * ((size_t)plan.n_e + 1), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + plan.log_e_offset, fa.log_e, 8 * (size_t)plan.n_e, hipMemcpyHostToDevice, c->stream));
+    if (cells) {
+        static_assert(sizeof(long long) == 8, "the counts are uploaded as they are");
+        HIPCHK(c, hipMemcpyAsync(d + plan.count_offset, fa.count, 8 * cells, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d + plan.w_offset, fa.w, 8 * cells, hipMemcpyHostToDevice, c->stream));
+    }
+    FitDev a{};
+    a.search = plan.search; a.n_spec = plan.n_spec; a.n_e = plan.n_e;
+    a.e_edges = reinterpret_cast<const double *>(d + plan.edges_offset); a.log_e = reinterpret_cast<const double *>(d + plan.log_e_offset);
+    a.count = reinterpret_cast<const long long *>(d + plan.count_offset); a.w = reinterpret_cast<const double *>(d + plan.w_offset);
+    double **f8[FIT_F8_COLUMNS] = {&a.alpha, &a.beta, &a.e_peak, &a.amplitude, &a.chi2};
+    for (int k = 0; k < FIT_F8_COLUMNS; ++k) *f8[k] = reinterpret_cast<double *>(d + plan.f8_offset + plan.f8_pitch * (size_t)k);
+    int **i4[FIT_I4_COLUMNS] = {&a.n_used, &a.dof, &a.status};
+    for (int k = 0; k < FIT_I4_COLUMNS; ++k) *i4[k] = reinterpret_cast<int *>(d + plan.i4_offset + plan.i4_pitch * (size_t)k);
+    HIPCHK(c, launch_fit(a, plan, c->stream));
+    if (rows) {
+        double *wanted[FIT_F8_COLUMNS] = {out->alpha, out->beta, out->e_peak, out->amplitude, out->chi2};
+        for (int k = 0; k < FIT_F8_COLUMNS; ++k)
+            if (wanted[k]) HIPCHK(c, hipMemcpyAsync(wanted[k], *f8[k], sizeof(double) * rows, hipMemcpyDeviceToHost, c->stream));
+        int *wanted_i[FIT_I4_COLUMNS] = {out->n_used, out->dof, out->status};
+        for (int k = 0; k < FIT_I4_COLUMNS; ++k)
+            if (wanted_i[k]) HIPCHK(c, hipMemcpyAsync(wanted_i[k], *i4[k], sizeof(int) * rows, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MCRAT_HIP_OK;
 }
 
 // ---------------------------------------------------------------------------------------------- the radiation field on the hydro mesh

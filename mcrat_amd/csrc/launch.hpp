@@ -256,6 +256,11 @@ struct EventsDev {
     unsigned *index[2];
 };
 hipError_t launch_events(const PhotonDev &ph, const EventsDev &a, const EventsPlan &plan, bool stokes, hipStream_t stream);
+// the spectral fit (fit.hip): every row of (count, W) fitted to a cutoff power law or a Band function, one wavefront per spectrum.  The block is laid
+// out as fit_plan.hpp says -- FitDev is defined there --; the caller copies the inputs.
+struct FitPlan;
+struct FitDev;
+hipError_t launch_fit(const FitDev &a, const FitPlan &plan, hipStream_t stream);
 hipError_t launch_init_states_multi(LoopState *ranks, int n_ranks, const int *open, const double *time_now, const double *remaining, hipStream_t stream);
 hipError_t launch_aos_to_soa(const void *aos, const PhotonDev &ph, int n, hipStream_t stream);
 // many lists of a rank pool at once: desc = `count` device records {int rank, int n, long long first record in aos}; the rest of each window is cleared

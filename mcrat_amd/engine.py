@@ -422,6 +422,101 @@ def resampled_estimates(res, mode, reduce=(), percentiles=None):
     return out
 
 
+class FitArgs(C.Structure):
+    """mcrat_hip_fit_args: the spectra (count, w), the edges and log_e, the pivot, the bounds, the coarse grid, the rounds, shrink and min_count"""
+    _fields_ = [("model", C.c_int), ("n_spec", C.c_longlong), ("n_e", C.c_int), ("count", C.POINTER(C.c_longlong)), ("w", _dp), ("e_edges", _dp), ("log_e", _dp),
+                ("e_piv", C.c_double), ("alpha_lo", C.c_double), ("alpha_hi", C.c_double), ("lambda_lo", C.c_double), ("lambda_hi", C.c_double),
+                ("beta_lo", C.c_double), ("beta_hi", C.c_double), ("g_alpha", C.c_int), ("g_lambda", C.c_int), ("g_beta", C.c_int), ("n_rounds", C.c_int),
+                ("shrink", C.c_double), ("min_count", C.c_longlong)]
+
+
+FIT_F8_COLUMNS = ("alpha", "beta", "e_peak", "amplitude", "chi2")
+FIT_I4_COLUMNS = ("n_used", "dof", "status")
+
+
+class FitResult(C.Structure):
+    """mcrat_hip_fit_result: the output columns, each [n_spec]"""
+    _fields_ = [(k, _dp) for k in FIT_F8_COLUMNS] + [(k, _ip) for k in FIT_I4_COLUMNS]
+
+
+FIT_COMP, FIT_BAND = 0, 1                                              # mcrat_hip_fit_args.model
+FIT_TOO_FEW_BINS, FIT_AT_BOUND_ALPHA, FIT_AT_BOUND_LAMBDA, FIT_AT_BOUND_BETA, FIT_NO_FINITE_CANDIDATE = 1, 2, 4, 8, 16      # bits of status
+FIT_E_PIV = 100.0 * 1.602176634e-9                                     # 100 keV in erg
+# The defaults of Engine.fit_spectra.  shrink, n_rounds and the coarse grid are chosen so that the NumPy restatement recovers 24 noise-free spectra
+# to 1e-6 (tests/test_fit_checker_cpu.py; DESIGN.md section 1): a faster shrink (0.9 and below) loses the minimum in the narrow valleys of Band fits.
+FIT_DEFAULTS = dict(alpha=(-1.9, 2.0), beta=(-6.0, -2.05), grid=(16, 16, 8), n_rounds=320, shrink=0.95, min_count=1)
+
+
+def spectra_from(res, mode, reduce=()):
+    """The (count, w) spectra of a dict from Engine.observe, observe_sky or observe_sky_resampled, ready for Engine.fit_spectra.  reduce: the axes
+    summed first, "time" and "pixels" (not "energy": it is the spectrum's axis).  Whether the cube has a replica axis behind the observer is read from its
+    rank -- (n_obs, n_t, n_e[, n_y, n_x]) from observe and observe_sky, (n_obs, n_rep, n_t, n_e[, n_y, n_x]) from observe_sky_resampled.  mode:
+    RESAMPLE_NONE leaves every entry as it stands; RESAMPLE_BOOTSTRAP leaves the entries as they are (entry 0 the sample);
+    RESAMPLE_JACKKNIFE turns the G groups into G + 1 entries: entry 0 the total, entries 1 .. G the leave-one-out spectra -- the counts subtracted
+    exactly, w scaled by G / (G - 1) as resampled_estimates scales it.  -> (count int64, w float64), energy as the last axis."""
+    names = (reduce,) if isinstance(reduce, str) else tuple(reduce)
+    for k in names:
+        if k not in ("time", "pixels"):
+            raise ValueError("spectra_from: reduce takes time and pixels, not %r" % (k,))
+    count, w = np.asarray(res["count"], dtype=np.int64), np.asarray(res["w"], dtype=np.float64)
+    if mode not in (RESAMPLE_NONE, RESAMPLE_JACKKNIFE, RESAMPLE_BOOTSTRAP):
+        raise ValueError("spectra_from: mode must be RESAMPLE_NONE, RESAMPLE_JACKKNIFE or RESAMPLE_BOOTSTRAP")
+    if count.shape != w.shape or count.ndim not in (3, 4, 5, 6):
+        raise ValueError("spectra_from: count and w need one shape, (n_obs[, n_rep], n_t, n_e[, n_y, n_x])")
+    replicas = count.ndim in (4, 6)                                    # (n_obs, n_rep, n_t, n_e[, n_y, n_x]): a replica axis behind the observer
+    if mode != RESAMPLE_NONE and not replicas:
+        raise ValueError("spectra_from: a jackknife or bootstrap cube has a replica axis, (n_obs, n_rep, n_t, n_e[, n_y, n_x])")
+    lead = 2 if replicas else 1                                        # (n_obs[, n_rep]), then n_t, n_e[, n_y, n_x]
+    if count.ndim > lead + 2:                                          # energy last
+        count, w = np.moveaxis(count, lead + 1, -1), np.moveaxis(w, lead + 1, -1)
+        if "pixels" in names:
+            count, w = count.sum(axis=(-3, -2)), w.sum(axis=(-3, -2))
+    if "time" in names:
+        count, w = count.sum(axis=lead), w.sum(axis=lead)
+    if mode == RESAMPLE_JACKKNIFE:
+        G = count.shape[1]
+        if G < 2:
+            raise ValueError("spectra_from: a jackknife needs at least two groups")
+        total_c, total_w = count.sum(axis=1, keepdims=True), w.sum(axis=1, keepdims=True)
+        count = np.concatenate([total_c, total_c - count], axis=1)
+        w = np.concatenate([total_w, (total_w - w) * (G / (G - 1.0))], axis=1)
+    return np.ascontiguousarray(count), np.ascontiguousarray(w)
+
+
+def fitted_estimates(fit, mode, percentiles=None):
+    """Value, stderr and percentile bounds of alpha, beta, e_peak and ln_e_peak over the replica axis (axis 1) of a dict from Engine.fit_spectra on
+    spectra_from's spectra, by the formulas of resampled_estimates.  RESAMPLE_JACKKNIFE: value is entry 0 (the total's fit), the replicates are
+    entries 1 .. G, var = (G - 1) / G sum_g (theta_g - mean theta)^2.  RESAMPLE_BOOTSTRAP: value is entry 0, stderr the sample standard deviation
+    (ddof = 1) over entries 1 .. B; percentiles = (lo, hi) in per cent adds the bounds.  RESAMPLE_NONE: the values alone, stderr NaN.  A replicate
+    without a fit (TOO_FEW_BINS, NO_FINITE_CANDIDATE) is NaN and makes its stderr NaN."""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        x = {"alpha": np.asarray(fit["alpha"]), "beta": np.asarray(fit["beta"]), "e_peak": np.asarray(fit["e_peak"]), "ln_e_peak": np.log(np.asarray(fit["e_peak"]))}
+    if mode not in (RESAMPLE_NONE, RESAMPLE_JACKKNIFE, RESAMPLE_BOOTSTRAP):
+        raise ValueError("fitted_estimates: mode must be RESAMPLE_NONE, RESAMPLE_JACKKNIFE or RESAMPLE_BOOTSTRAP")
+    out = {}
+    for k, v in x.items():
+        if mode == RESAMPLE_NONE:
+            out[k] = {"value": v, "stderr": np.full(v.shape, np.nan)}
+            continue
+        if v.ndim < 2 or v.shape[1] < 3:
+            raise ValueError("fitted_estimates: the replica axis needs the estimate and at least two replicates")
+        val, reps = v[:, 0], v[:, 1:]
+        n = reps.shape[1]
+        est = {"value": val}
+        with np.errstate(invalid="ignore"):
+            dev = reps - val[:, None]
+            if mode == RESAMPLE_JACKKNIFE:
+                var = (n - 1.0) / n * ((dev - dev.mean(axis=1, keepdims=True)) ** 2).sum(axis=1)
+            else:
+                var = dev.var(axis=1, ddof=1)
+                if percentiles is not None:
+                    lo, hi = np.percentile(dev, list(percentiles), axis=1)
+                    est["lo"], est["hi"] = val + lo, val + hi
+            est["stderr"] = np.sqrt(var)
+        out[k] = est
+    return out
+
+
 class RadfieldBins(C.Structure):
     """mcrat_hip_radfield_bins: the binning of a radiation field -- the hydro cells, or (r, mu) shells with their edges"""
     _fields_ = [("mode", C.c_int), ("n_r", C.c_int), ("r_edges", _dp), ("n_mu", C.c_int), ("mu_edges", _dp)]
@@ -575,6 +670,7 @@ SYMBOLS = {
     "mcrat_hip_observe_sky_resampled_path": (C.c_int, [_ctx]),
     "mcrat_hip_observe_events": (C.c_int, [_ctx, C.POINTER(EventsObserver), C.c_double, C.POINTER(Events)]),
     "mcrat_hip_pool_observe_events": (C.c_int, [_ctx, C.POINTER(EventsObserver), _dp, C.POINTER(Events)]),
+    "mcrat_hip_fit_spectra": (C.c_int, [_ctx, C.POINTER(FitArgs), C.POINTER(FitResult)]),
     "mcrat_hip_synchronize": (C.c_int, [_ctx]),
     "mcrat_hip_device_bytes": (C.c_size_t, [_ctx]),
     "mcrat_hip_eval_function": (C.c_int, [_ctx, C.c_int, C.c_int, _dp, _dp, C.c_uint64]),
@@ -1560,6 +1656,40 @@ class Engine:
             raise ValueError("pool_observe_events: time_now needs one clock per rank of the pool")
         return self._observe_events(self.lib.mcrat_hip_pool_observe_events, "pool_observe_events", n, cos_acc, tn.ctypes.data_as(_dp), order, stokes_frame, ex, ey,
                                     t_window, e_window, capacity)
+
+    # ---- spectral fits: Band function and cutoff power law (include/mcrat_hip.h)
+    def fit_spectra(self, count, w, e_edges, model=FIT_BAND, e_piv=FIT_E_PIV, alpha=FIT_DEFAULTS["alpha"], lam=None, beta=FIT_DEFAULTS["beta"],
+                    grid=FIT_DEFAULTS["grid"], n_rounds=FIT_DEFAULTS["n_rounds"], shrink=FIT_DEFAULTS["shrink"], min_count=FIT_DEFAULTS["min_count"], log_e=None):
+        """every spectrum of (count, w) -- arrays (..., n_e), e_edges (n_e + 1,) in erg -- fitted to FIT_BAND or FIT_COMP on the device
+        (mcrat_hip_fit_spectra).  alpha, lam, beta: the (lo, hi) bounds of the search in alpha, lambda = ln(E_pk / e_piv) and beta; lam=None takes
+        the edges' range.  grid: the coarse grid's cells (alpha, lambda, beta).  log_e: ln(E_i / e_piv) at the bins' geometric centres, computed here
+        with NumPy when None.  -> dict of alpha, beta (NaN for FIT_COMP), e_peak (erg), amplitude, chi2 (float64) and n_used, dof, status (int32),
+        each with the input's leading shape.  spectra_from makes the input from an observation, fitted_estimates the error bars from the output."""
+        count, w = np.ascontiguousarray(count, dtype=np.int64), _f8(w)
+        edges = _f8(e_edges).ravel()
+        if count.shape != w.shape or count.ndim < 1:
+            raise ValueError("fit_spectra: count and w need the same shape (..., n_e)")
+        n_e = count.shape[-1]
+        if len(edges) != n_e + 1:
+            raise ValueError("fit_spectra: e_edges needs n_e + 1 values")
+        with np.errstate(all="ignore"):
+            if log_e is None:
+                log_e = np.log(np.sqrt(edges[:-1] * edges[1:]) / e_piv)
+            if lam is None:
+                lam = (np.log(edges[0] / e_piv), np.log(edges[-1] / e_piv))
+        log_e = _f8(log_e).ravel()
+        if len(log_e) != n_e:
+            raise ValueError("fit_spectra: log_e needs n_e values")
+        lead = count.shape[:-1]
+        n_spec = int(np.prod(lead, dtype=np.int64))
+        args = FitArgs(int(model), n_spec, n_e, count.ctypes.data_as(C.POINTER(C.c_longlong)), w.ctypes.data_as(_dp), edges.ctypes.data_as(_dp),
+                       log_e.ctypes.data_as(_dp), float(e_piv), float(alpha[0]), float(alpha[1]), float(lam[0]), float(lam[1]), float(beta[0]), float(beta[1]),
+                       int(grid[0]), int(grid[1]), int(grid[2]), int(n_rounds), float(shrink), int(min_count))
+        res = {k: np.zeros(n_spec) for k in FIT_F8_COLUMNS}
+        res.update({k: np.zeros(n_spec, dtype=np.int32) for k in FIT_I4_COLUMNS})
+        out = FitResult(*([res[k].ctypes.data_as(_dp) for k in FIT_F8_COLUMNS] + [res[k].ctypes.data_as(_ip) for k in FIT_I4_COLUMNS]))
+        self._check(self.lib.mcrat_hip_fit_spectra(self.ctx, C.byref(args), C.byref(out)), "fit_spectra")
+        return {k: v.reshape(lead) for k, v in res.items()}
 
     # ---- line-of-sight optical depths and photospheres (include/mcrat_hip.h)
     def _sightlines(self, what, n, call, step_frac, h_min, max_steps, tau_stop, surface_level):
