@@ -16,7 +16,7 @@ LIB = os.path.join(HERE, "libmcrat_hip.so")
 ABI_HEADER = os.path.join("..", "..", "include", "mcrat_hip.h")        # the C ABI, relative to csrc
 KERNEL_TUS = ["kernels%s_d%d.hip" % (m, d) for m in ("", "_table") for d in (0, 1, 2)]   # kernels.hip per TAU_CALCULATION x DIMENSIONS
 SOURCES = KERNEL_TUS + ["launchers.hip", "rank_launch.hip", "grid_build.hip", "staging.hip", "inject.hip", "ingest.hip", "hot_table.hip", "functions.hip", "observe.hip", "sightline.hip", "radfield.hip", "comoving.hip", "sky.hip", "escape.hip", "resample.hip", "events.hip", "fit.hip", "engine.hip"]
-HEADERS = ["kernels.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp", "hydro_plan.hpp", "rank_form_plan.hpp", "observe_plan.hpp", "sightline_plan.hpp", "radfield_plan.hpp", "comoving_plan.hpp", "sky_plan.hpp", "escape_plan.hpp", "resample_plan.hpp", "events_plan.hpp", "fit_plan.hpp", "sightline_march.hpp", "bin_accumulate.hpp", "photon_plan.hpp", "photon_cols.hpp", "sc_exchange.hpp", "physics.hpp", "rng.hpp", "cs_device.hpp", ABI_HEADER]
+HEADERS = ["kernels.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp", "hydro_plan.hpp", "rank_form_plan.hpp", "observe_plan.hpp", "sightline_plan.hpp", "radfield_plan.hpp", "comoving_plan.hpp", "sky_plan.hpp", "escape_plan.hpp", "resample_plan.hpp", "events_plan.hpp", "fit_plan.hpp", "analysis_plan.hpp", "sightline_march.hpp", "bin_accumulate.hpp", "photon_plan.hpp", "photon_cols.hpp", "sc_exchange.hpp", "physics.hpp", "rng.hpp", "cs_device.hpp", ABI_HEADER]
 # -amdgpu-prealloc-sgpr-spill-vgprs: the loop kernels sit at 256 VGPRs with hundreds of scalar registers spilled to lanes of vector registers; with the
 #   compiler's default (those vector registers chosen after everything else is allocated) single instantiations wrote a wrong Stokes V -- another
 #   instantiation after every larger edit (round 3: 3-D spherical; round 4: 3-D polar; without the shadow draws: 3-D spherical again), every time cured
@@ -52,7 +52,7 @@ DEPS = {"launchers.hip": ["launchers.hip", "device_types.hpp", "launch.hpp", "fr
         "events.hip": ["events.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp", "hydro_plan.hpp", "observe_plan.hpp", "sky_plan.hpp",
                        "resample_plan.hpp", "events_plan.hpp", "rng.hpp"],
         "fit.hip": ["fit.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp", "hydro_plan.hpp", "fit_plan.hpp"],
-        "engine.hip": ["engine.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp", "hydro_plan.hpp", "observe_plan.hpp", "sightline_plan.hpp", "radfield_plan.hpp", "comoving_plan.hpp", "sky_plan.hpp", "escape_plan.hpp", "resample_plan.hpp", "events_plan.hpp", "fit_plan.hpp", "photon_cols.hpp", "photon_plan.hpp", "rng.hpp",
+        "engine.hip": ["engine.hip", "device_types.hpp", "launch.hpp", "frame_queue.hpp", "list_plan.hpp", "hydro_plan.hpp", "observe_plan.hpp", "sightline_plan.hpp", "radfield_plan.hpp", "comoving_plan.hpp", "sky_plan.hpp", "escape_plan.hpp", "resample_plan.hpp", "events_plan.hpp", "fit_plan.hpp", "analysis_plan.hpp", "photon_cols.hpp", "photon_plan.hpp", "rng.hpp",
                        ABI_HEADER]}
 for _tu in KERNEL_TUS:
     DEPS[_tu] = _KERNEL_DEPS + [_tu]

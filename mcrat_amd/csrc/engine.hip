@@ -27,6 +27,7 @@
 #include "fit_plan.hpp"
 #include "radfield_plan.hpp"
 #include "comoving_plan.hpp"
+#include "analysis_plan.hpp"
 #include "photon_cols.hpp"
 #include "photon_plan.hpp"
 #include "rng.hpp"
@@ -4096,6 +4097,52 @@ static int analysis_block(mcrat_hip_ctx *c, const mcrat_hip_ctx *h, int which, s
     return MCRAT_HIP_OK;
 }
 
+// The read-back of n columns of bytes_each bytes that lie pitch_bytes apart from `base` (device) on: column k to dst[k], where the caller wants it;
+// a column that is not asked for (nullptr) is not copied.  Copies on c's stream, not waited for.
+static int read_columns(mcrat_hip_ctx *c, const char *base, size_t pitch_bytes, size_t bytes_each, void *const *dst, int n)
+{
+    for (int k = 0; k < n; ++k)
+        if (dst[k]) HIPCHK(c, hipMemcpyAsync(dst[k], base + pitch_bytes * (size_t)k, bytes_each, hipMemcpyDeviceToHost, c->stream));
+    return MCRAT_HIP_OK;
+}
+
+// The photons of a call on one list (analysis_plan.hpp): c is a stand-alone context or a view, and what a pass left pending is applied.
+// on_a_pool: the family's text for a pool, which is not one list.  may_be_empty: a context without photons passes, with no slots (the two fields:
+// their "no photons" comes behind their other checks); the observers and the sightlines refuse it here.
+static int list_photons(mcrat_hip_ctx *c, double time_now, const char *on_a_pool, bool may_be_empty, PhotonSource *src)
+{
+    if (!c->have_photons && !may_be_empty) return MCRAT_HIP_ESTATE;
+    if (c->is_pool) { c->last_error = on_a_pool; return MCRAT_HIP_ESTATE; }
+    if (c->have_photons) {
+        int rc = flush_pending(c);
+        if (rc) return rc;
+    }
+    *src = list_source(c->have_photons ? c->ph.n : 0, time_now, c->parent ? c->view_rank : 0);
+    return MCRAT_HIP_OK;
+}
+
+// The photons of a call on a pool: every slot -- those beyond a list's length, and those of lists never created, are not FLAG_VALID and contribute
+// nothing (windows are cleared on upload, lists only grow, grown slots are type 'N'; a selected capture included: c->ph is that capture's
+// columns).  no_pool: the family's text.  No flush_pending, as in mcrat_hip_pool_summaries: a list stepped one by one through its view is read
+// through the view, which flushes it -- the header says so.  (The sightlines' and the two fields' pool calls add it themselves.  They, and their
+// list calls, have no clocks to give -- nullptr, 0.0 -- and read n_slots alone: such a source is not one for an observer's *_run.)
+static int pool_photons(mcrat_hip_ctx *c, const double *clocks, const char *no_pool, PhotonSource *src)
+{
+    if (!c->is_pool) { c->last_error = no_pool; return MCRAT_HIP_ESTATE; }
+    *src = pool_source(c->ph.n, c->n_ranks, c->rank_stride, clocks);
+    return MCRAT_HIP_OK;
+}
+
+// Whose staged frame a product of c reads -- *h: `hydro`, or c itself for nullptr -- and what analysis_plan.hpp's rule says of it.  The callers
+// have their own texts for a mismatch and for no frame; FRAME_NO_TABLE has one.
+static const char *const NO_HOT_TABLE = "TAU_CALCULATION == TABLE needs mcrat_hip_set_hot_cross_section first";
+static FrameVerdict frame_of(const mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, bool with_table, bool need_cells, const mcrat_hip_ctx **h)
+{
+    const mcrat_hip_ctx *f = *h = hydro ? hydro : c;
+    return frame_verdict(FrameSwitches{c->kc.dimensions, c->kc.geometry, c->kc.table, c->cfg.device}, FrameSwitches{f->kc.dimensions, f->kc.geometry, f->kc.table, f->cfg.device},
+                         f == c, f->have_hydro, f->hy.M, f->hy.hot_table != nullptr, with_table, need_cells);
+}
+
 // A cube job, what mcrat_hip_observe and mcrat_hip_observe_sky share (observe_plan.hpp, sky_plan.hpp): the block is the cube's seven planes, the
 // per-observer counters and, behind them, `in` -- the kernel's inputs in the order it stages them, then the lists' clocks when there are any.  One
 // memset, one copy of the inputs, one launch, the planes and counters read back to wherever *out wants them.  `a` comes with everything but its
@@ -4117,20 +4164,16 @@ static int cube_run(mcrat_hip_ctx *c, int which, const Plan &plan, const std::ve
     if ((rc = launch(a))) return rc;
     const size_t plane = sizeof(double) * (size_t)plan.n_bins, counters = sizeof(long long) * (size_t)plan.n_obs;
     void *planes[OBSERVE_PLANES] = {out->count, out->w, out->we, out->i, out->q, out->u, out->v};
+    void *per_observer[2] = {out->n_accepted, out->n_outside};
     static_assert(sizeof(long long) == 8, "the count plane and the counters are read back as they are");
-    for (int k = 0; k < OBSERVE_PLANES; ++k)
-        if (planes[k]) HIPCHK(c, hipMemcpyAsync(planes[k], d + plane * (size_t)k, plane, hipMemcpyDeviceToHost, c->stream));
-    if (out->n_accepted) HIPCHK(c, hipMemcpyAsync(out->n_accepted, d + plan.cube_bytes, counters, hipMemcpyDeviceToHost, c->stream));
-    if (out->n_outside) HIPCHK(c, hipMemcpyAsync(out->n_outside, d + plan.cube_bytes + counters, counters, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = read_columns(c, d, plane, plane, planes, OBSERVE_PLANES)) || (rc = read_columns(c, d + plan.cube_bytes, counters, counters, per_observer, 2))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return MCRAT_HIP_OK;
 }
 
 // ---------------------------------------------------------------------------------------------- mock observations
-// The photons of c->ph -- n_slots of them -- binned by observer, detection time and energy (observe_plan.hpp, observe.hip), and the cube read back.
-// clocks: one per slots_per_clock slots (a rank pool's lists), or nullptr and time_now for all.
-static int observe_run(mcrat_hip_ctx *c, const mcrat_hip_observer *obs, int n_slots, const double *clocks, int n_clocks, int slots_per_clock, double time_now,
-                       mcrat_hip_observation *out)
+// The photons of c->ph that src names binned by observer, detection time and energy (observe_plan.hpp, observe.hip), and the cube read back.
+static int observe_run(mcrat_hip_ctx *c, const mcrat_hip_observer *obs, const PhotonSource &src, mcrat_hip_observation *out)
 {
     c->obs_path = OBSERVE_PATH_NONE;
     if (!obs->cos_obs || !obs->sin_obs || !obs->cos_lo || !obs->cos_hi || !obs->t_edges || !obs->e_edges) {
@@ -4146,16 +4189,16 @@ static int observe_run(mcrat_hip_ctx *c, const mcrat_hip_observer *obs, int n_sl
     // the inputs in the order the kernel stages them, the clocks behind them
     const size_t n_obs = (size_t)plan.n_obs;
     std::vector<double> in;
-    in.reserve(plan.staged_doubles + (size_t)n_clocks);
+    in.reserve(plan.staged_doubles + (size_t)src.n_clocks);
     for (const double *v : {obs->cos_obs, obs->sin_obs, obs->cos_lo, obs->cos_hi}) in.insert(in.end(), v, v + n_obs);
     in.insert(in.end(), obs->t_edges, obs->t_edges + plan.n_t + 1); in.insert(in.end(), obs->e_edges, obs->e_edges + plan.n_e + 1);
-    if (clocks) in.insert(in.end(), clocks, clocks + n_clocks);
+    if (src.clocks) in.insert(in.end(), src.clocks, src.clocks + src.n_clocks);
 
     ObserveDev a{};
-    a.n_slots = n_slots; a.n_obs = plan.n_obs; a.n_t = plan.n_t; a.n_e = plan.n_e; a.n_bins = plan.n_bins;
-    a.slots_per_clock = slots_per_clock;
-    a.time_now = time_now;
-    const int rc = cube_run(c, mcrat_hip_ctx::BLOCK_OBSERVE, plan, in, clocks != nullptr, a, [&](const ObserveDev &dev) -> int {
+    a.n_slots = src.n_slots; a.n_obs = plan.n_obs; a.n_t = plan.n_t; a.n_e = plan.n_e; a.n_bins = plan.n_bins;
+    a.slots_per_clock = src.slots_per_clock;
+    a.time_now = src.time_now;
+    const int rc = cube_run(c, mcrat_hip_ctx::BLOCK_OBSERVE, plan, in, src.clocks != nullptr, a, [&](const ObserveDev &dev) -> int {
         HIPCHK(c, launch_observe(c->ph, dev, plan, c->kc.stokes != 0, device_cus(c), c->stream));
         return MCRAT_HIP_OK;
     }, out);
@@ -4167,21 +4210,17 @@ static int observe_run(mcrat_hip_ctx *c, const mcrat_hip_observer *obs, int n_sl
 extern "C" int mcrat_hip_observe(mcrat_hip_ctx *c, const mcrat_hip_observer *obs, double time_now, mcrat_hip_observation *out)
 {
     if (!c || !obs || !out) return MCRAT_HIP_EINVAL;
-    if (!c->have_photons) return MCRAT_HIP_ESTATE;
-    if (c->is_pool) { c->last_error = "observe: a rank pool's lists have clocks of their own (mcrat_hip_pool_observe, or mcrat_hip_observe on a view)"; return MCRAT_HIP_ESTATE; }
-    int rc = flush_pending(c);
-    if (rc) return rc;
-    return observe_run(c, obs, c->ph.n, nullptr, 0, 1, time_now, out);
+    PhotonSource src;
+    int rc = list_photons(c, time_now, "observe: a rank pool's lists have clocks of their own (mcrat_hip_pool_observe, or mcrat_hip_observe on a view)", false, &src);
+    return rc ? rc : observe_run(c, obs, src, out);
 }
 
 extern "C" int mcrat_hip_pool_observe(mcrat_hip_ctx *c, const mcrat_hip_observer *obs, const double *time_now, mcrat_hip_observation *out)
 {
     if (!c || !obs || !time_now || !out) return MCRAT_HIP_EINVAL;
-    if (!c->is_pool) return MCRAT_HIP_ESTATE;
-    // every slot of the pool: those beyond a list's length, and those of lists never created, are not FLAG_VALID and contribute nothing (windows
-    // are cleared on upload, lists only grow, grown slots are type 'N').  No flush_pending, as in mcrat_hip_pool_summaries: a list stepped one by
-    // one through its view is read through the view (mcrat_hip_observe), which flushes it -- the header says so.
-    return observe_run(c, obs, c->ph.n, time_now, c->n_ranks, c->rank_stride, 0.0, out);
+    PhotonSource src;
+    int rc = pool_photons(c, time_now, "pool_observe: the context is no rank pool", &src);
+    return rc ? rc : observe_run(c, obs, src, out);
 }
 
 extern "C" int mcrat_hip_observe_path(const mcrat_hip_ctx *c) { return c ? c->obs_path : 0; }
@@ -4199,29 +4238,21 @@ static int sky_args(mcrat_hip_ctx *c, const mcrat_hip_sky_observer *obs, SkyArgs
     return MCRAT_HIP_OK;
 }
 
-// The kernel's inputs in the order it stages them (sky_plan.hpp), the lists' clocks behind them.
-static std::vector<double> sky_staged_inputs(const SkyArgs &s, const SkyPlan &plan, const double *clocks, int n_clocks)
+// A cube job's inputs: the observers' in the order the kernel stages them (analysis_plan.hpp), `more` further edges behind them (nullptr: none), then
+// the lists' clocks when there are any.
+static std::vector<double> staged_inputs(const SkyArgs &s, bool axes, bool image, size_t staged_doubles, const double *more, size_t n_more, const PhotonSource &src)
 {
     std::vector<double> in;
-    in.reserve(plan.staged_doubles + (size_t)n_clocks);
-    const size_t n_obs = (size_t)plan.n_obs;
-    for (const double *v : {s.n0, s.n1, s.n2, s.cos_acc}) in.insert(in.end(), v, v + n_obs);
-    if (plan.image)
-        for (const double *v : {s.x0, s.x1, s.x2, s.y0, s.y1, s.y2}) in.insert(in.end(), v, v + n_obs);
-    in.insert(in.end(), s.t_edges, s.t_edges + plan.n_t + 1);
-    in.insert(in.end(), s.e_edges, s.e_edges + plan.n_e + 1);
-    if (plan.image) {
-        in.insert(in.end(), s.x_edges, s.x_edges + plan.n_x + 1);
-        in.insert(in.end(), s.y_edges, s.y_edges + plan.n_y + 1);
-    }
-    if (clocks) in.insert(in.end(), clocks, clocks + n_clocks);
+    in.reserve(staged_doubles + (size_t)src.n_clocks);
+    stage_observer_inputs(s, axes, true, image, &in);
+    if (more) in.insert(in.end(), more, more + n_more);
+    if (src.clocks) in.insert(in.end(), src.clocks, src.clocks + src.n_clocks);
     return in;
 }
 
-// The photons of c->ph -- n_slots of them -- binned by observer, detection time, energy and sky-plane position (sky_plan.hpp, sky.hip), and the cube
-// read back.  clocks: one per slots_per_clock slots (a rank pool's lists), or nullptr and time_now for all.
-static int sky_run(mcrat_hip_ctx *c, const mcrat_hip_sky_observer *obs, int n_slots, const double *clocks, int n_clocks, int slots_per_clock, double time_now,
-                   mcrat_hip_sky_observation *out)
+// The photons of c->ph that src names binned by observer, detection time, energy and sky-plane position (sky_plan.hpp, sky.hip), and the cube read
+// back.
+static int sky_run(mcrat_hip_ctx *c, const mcrat_hip_sky_observer *obs, const PhotonSource &src, mcrat_hip_sky_observation *out)
 {
     c->sky_path = OBSERVE_PATH_NONE;
     SkyArgs args;
@@ -4232,11 +4263,12 @@ static int sky_run(mcrat_hip_ctx *c, const mcrat_hip_sky_observer *obs, int n_sl
     if (why != SKY_OK) { c->last_error = sky_refusal_text(why); return MCRAT_HIP_EINVAL; }
 
     SkyDev a{};
-    a.n_slots = n_slots; a.n_obs = plan.n_obs; a.n_t = plan.n_t; a.n_e = plan.n_e; a.n_x = plan.n_x; a.n_y = plan.n_y; a.n_bins = plan.n_bins;
-    a.slots_per_clock = slots_per_clock;
-    a.time_now = time_now;
-    rc = cube_run(c, mcrat_hip_ctx::BLOCK_SKY, plan, sky_staged_inputs(args, plan, clocks, n_clocks), clocks != nullptr, a, [&](const SkyDev &dev) -> int {
-        HIPCHK(c, launch_sky(c->ph, dev, plan, c->kc.stokes != 0, sky_grid(plan, n_slots, device_cus(c)), c->stream));
+    a.n_slots = src.n_slots; a.n_obs = plan.n_obs; a.n_t = plan.n_t; a.n_e = plan.n_e; a.n_x = plan.n_x; a.n_y = plan.n_y; a.n_bins = plan.n_bins;
+    a.slots_per_clock = src.slots_per_clock;
+    a.time_now = src.time_now;
+    const std::vector<double> in = staged_inputs(args, plan.image, plan.image, plan.staged_doubles, nullptr, 0, src);
+    rc = cube_run(c, mcrat_hip_ctx::BLOCK_SKY, plan, in, src.clocks != nullptr, a, [&](const SkyDev &dev) -> int {
+        HIPCHK(c, launch_sky(c->ph, dev, plan, c->kc.stokes != 0, sky_grid(plan, src.n_slots, device_cus(c)), c->stream));
         return MCRAT_HIP_OK;
     }, out);
     if (rc) return rc;
@@ -4247,19 +4279,17 @@ static int sky_run(mcrat_hip_ctx *c, const mcrat_hip_sky_observer *obs, int n_sl
 extern "C" int mcrat_hip_observe_sky(mcrat_hip_ctx *c, const mcrat_hip_sky_observer *obs, double time_now, mcrat_hip_sky_observation *out)
 {
     if (!c || !obs || !out) return MCRAT_HIP_EINVAL;
-    if (!c->have_photons) return MCRAT_HIP_ESTATE;
-    if (c->is_pool) { c->last_error = "observe_sky: a rank pool's lists have clocks of their own (mcrat_hip_pool_observe_sky, or mcrat_hip_observe_sky on a view)"; return MCRAT_HIP_ESTATE; }
-    int rc = flush_pending(c);
-    if (rc) return rc;
-    return sky_run(c, obs, c->ph.n, nullptr, 0, 1, time_now, out);
+    PhotonSource src;
+    int rc = list_photons(c, time_now, "observe_sky: a rank pool's lists have clocks of their own (mcrat_hip_pool_observe_sky, or mcrat_hip_observe_sky on a view)", false, &src);
+    return rc ? rc : sky_run(c, obs, src, out);
 }
 
 extern "C" int mcrat_hip_pool_observe_sky(mcrat_hip_ctx *c, const mcrat_hip_sky_observer *obs, const double *time_now, mcrat_hip_sky_observation *out)
 {
     if (!c || !obs || !time_now || !out) return MCRAT_HIP_EINVAL;
-    if (!c->is_pool) { c->last_error = "pool_observe_sky: the context is no rank pool"; return MCRAT_HIP_ESTATE; }
-    // every slot of the pool, exactly as mcrat_hip_pool_observe reads them, and like it without flush_pending
-    return sky_run(c, obs, c->ph.n, time_now, c->n_ranks, c->rank_stride, 0.0, out);
+    PhotonSource src;
+    int rc = pool_photons(c, time_now, "pool_observe_sky: the context is no rank pool", &src);
+    return rc ? rc : sky_run(c, obs, src, out);
 }
 
 extern "C" int mcrat_hip_observe_sky_path(const mcrat_hip_ctx *c) { return c ? c->sky_path : 0; }
@@ -4271,16 +4301,14 @@ extern "C" int mcrat_hip_observe_sky_path(const mcrat_hip_ctx *c) { return c ? c
 static int sightline_run(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_sightline_params *params, int n, const double *const *rays,
                          mcrat_hip_sightlines *out)
 {
-    const mcrat_hip_ctx *h = hydro ? hydro : c;
-    if (!h->have_hydro) { c->last_error = "sightline: no staged hydro frame"; return MCRAT_HIP_ESTATE; }
-    if (h != c && (h->kc.dimensions != c->kc.dimensions || h->kc.geometry != c->kc.geometry || h->kc.table != c->kc.table || h->cfg.device != c->cfg.device)) {
+    const mcrat_hip_ctx *h = nullptr;
+    const FrameVerdict frame = frame_of(c, hydro, true, false, &h);
+    if (!h->have_hydro) { c->last_error = "sightline: no staged hydro frame"; return MCRAT_HIP_ESTATE; }       // (here the frame comes first, the arguments last)
+    if (frame == FRAME_MISMATCH) {
         c->last_error = "sightline: a frame staged on a context with other switches (DIMENSIONS, GEOMETRY, TAU_CALCULATION) or on another device";
         return MCRAT_HIP_EINVAL;
     }
-    if (c->kc.table && !h->hy.hot_table) {
-        c->last_error = "TAU_CALCULATION == TABLE needs mcrat_hip_set_hot_cross_section first";
-        return MCRAT_HIP_ESTATE;
-    }
+    if (frame == FRAME_NO_TABLE) { c->last_error = NO_HOT_TABLE; return MCRAT_HIP_ESTATE; }
     const SightlineParams p{params->step_frac, params->h_min, params->max_steps, params->tau_stop, params->surface_level};
     int forced;
     SightlinePlan plan;
@@ -4309,12 +4337,11 @@ static int sightline_run(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcr
         a.ray = d_ray;
     }
     HIPCHK(c, launch_sightline(c->kc, c->ph, h->hy, a, blocks, c->stream));
-    double *f8[SIGHTLINE_F8_PLANES] = {out->tau, out->path, out->surface_r0, out->surface_r1, out->surface_r2};
-    int *i4[SIGHTLINE_I4_PLANES] = {out->steps, out->status, out->surface_step};
-    for (int k = 0; k < SIGHTLINE_F8_PLANES; ++k)
-        if (f8[k]) HIPCHK(c, hipMemcpyAsync(f8[k], d + sightline_f8_plane(plan, k), sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    for (int k = 0; k < SIGHTLINE_I4_PLANES; ++k)
-        if (i4[k]) HIPCHK(c, hipMemcpyAsync(i4[k], d + sightline_i4_plane(plan, k), sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    void *f8[SIGHTLINE_F8_PLANES] = {out->tau, out->path, out->surface_r0, out->surface_r1, out->surface_r2};
+    void *i4[SIGHTLINE_I4_PLANES] = {out->steps, out->status, out->surface_step};
+    const size_t f8_bytes = sizeof(double) * (size_t)n, i4_bytes = sizeof(int) * (size_t)n;           // (the planes' pitch: sightline_f8_plane, sightline_i4_plane)
+    if ((rc = read_columns(c, d + plan.f8_offset, f8_bytes, f8_bytes, f8, SIGHTLINE_F8_PLANES)) ||
+        (rc = read_columns(c, d + plan.i4_offset, i4_bytes, i4_bytes, i4, SIGHTLINE_I4_PLANES))) return rc;
     static_assert(sizeof(long long) == 8, "the status counts are read back as they are");
     HIPCHK(c, hipMemcpyAsync(out->n_status, d, sizeof(long long) * SIGHTLINE_N_STATUS, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -4338,21 +4365,18 @@ extern "C" int mcrat_hip_sightline_rays(mcrat_hip_ctx *c, const mcrat_hip_ctx *h
 extern "C" int mcrat_hip_sightline_photons(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_sightline_params *params, mcrat_hip_sightlines *out)
 {
     if (!c || !params || !out) return MCRAT_HIP_EINVAL;
-    if (!c->have_photons) return MCRAT_HIP_ESTATE;
-    if (c->is_pool) { c->last_error = "sightline: one list is a stand-alone context or a view of a pool (mcrat_hip_pool_sightline_photons takes the pool)"; return MCRAT_HIP_ESTATE; }
-    int rc = flush_pending(c);
-    if (rc) return rc;
-    return sightline_run(c, hydro, params, c->ph.n, nullptr, out);
+    PhotonSource src;
+    int rc = list_photons(c, 0.0, "sightline: one list is a stand-alone context or a view of a pool (mcrat_hip_pool_sightline_photons takes the pool)", false, &src);
+    return rc ? rc : sightline_run(c, hydro, params, src.n_slots, nullptr, out);
 }
 
 extern "C" int mcrat_hip_pool_sightline_photons(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_sightline_params *params, mcrat_hip_sightlines *out)
 {
     if (!c || !params || !out) return MCRAT_HIP_EINVAL;
-    if (!c->is_pool) return MCRAT_HIP_ESTATE;
-    // every slot of the pool, as mcrat_hip_pool_observe reads them: slots beyond a list's length and lists never created are not FLAG_VALID
-    int rc = flush_pending(c);
-    if (rc) return rc;
-    return sightline_run(c, hydro, params, c->ph.n, nullptr, out);
+    PhotonSource src;                            // (the rays have no clocks)
+    int rc = pool_photons(c, nullptr, "pool_sightline_photons: the context is no rank pool", &src);
+    if (!rc) rc = flush_pending(c);              // (unlike the observers' pool calls)
+    return rc ? rc : sightline_run(c, hydro, params, src.n_slots, nullptr, out);
 }
 
 // ---------------------------------------------------------------------------------------------- escape-weighted sky observations
@@ -4370,30 +4394,13 @@ static int escape_check(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcra
     args->march = SightlineParams{obs->march.step_frac, obs->march.h_min, obs->march.max_steps, obs->march.tau_stop, -1.0};
     const EscapeRefusal why = escape_plan(*args, getenv("MCRAT_HIP_ESCAPE_PATH"), plan);
     if (why != ESCAPE_OK) { c->last_error = escape_refusal_text(why, text); return MCRAT_HIP_EINVAL; }
-    const mcrat_hip_ctx *h = hydro ? hydro : c;
-    if (h != c && (h->kc.dimensions != c->kc.dimensions || h->kc.geometry != c->kc.geometry || h->kc.table != c->kc.table || h->cfg.device != c->cfg.device)) {
-        c->last_error = escape_refusal_text(ESCAPE_HYDRO_MISMATCH, text);
-        return MCRAT_HIP_EINVAL;
+    switch (frame_of(c, hydro, true, false, h_out)) {
+    case FRAME_MISMATCH: c->last_error = escape_refusal_text(ESCAPE_HYDRO_MISMATCH, text); return MCRAT_HIP_EINVAL;
+    case FRAME_NONE: c->last_error = "observe_escaping: no staged hydro frame"; return MCRAT_HIP_ESTATE;
+    case FRAME_NO_TABLE: c->last_error = NO_HOT_TABLE; return MCRAT_HIP_ESTATE;
+    case FRAME_OK: break;
     }
-    if (!h->have_hydro) { c->last_error = "observe_escaping: no staged hydro frame"; return MCRAT_HIP_ESTATE; }
-    if (c->kc.table && !h->hy.hot_table) {
-        c->last_error = "TAU_CALCULATION == TABLE needs mcrat_hip_set_hot_cross_section first";
-        return MCRAT_HIP_ESTATE;
-    }
-    *h_out = h;
     return MCRAT_HIP_OK;
-}
-
-// The kernels' inputs in the order the binning kernel stages them (escape_plan.hpp): the sky observation's, then tau_edges; the clocks behind them.
-static std::vector<double> escape_staged_inputs(const EscapeArgs &args, const EscapePlan &plan, const double *clocks, int n_clocks)
-{
-    SkyPlan sky{};                               // (what sky_staged_inputs reads of a plan)
-    sky.n_obs = plan.n_obs; sky.n_t = plan.n_t; sky.n_e = plan.n_e; sky.n_x = plan.n_x; sky.n_y = plan.n_y; sky.image = plan.image;
-    sky.staged_doubles = plan.staged_doubles;
-    std::vector<double> in = sky_staged_inputs(args.sky, sky, nullptr, 0);
-    in.insert(in.end(), args.tau_edges, args.tau_edges + plan.n_tau + 1);
-    if (clocks) in.insert(in.end(), clocks, clocks + n_clocks);
-    return in;
 }
 
 // How the block's results come back.  A small block -- light curves, spectra -- is read back whole by one copy and handed out on the host: fourteen
@@ -4422,26 +4429,10 @@ static void escape_fill_outputs(const EscapePlan &plan, const char *block, size_
     out->n_observable = head[ESCAPE_OBSERVABLE_WORD];
 }
 
-// The read-back of a block beyond ESCAPE_ONE_COPY_BYTES: the planes and per-observer counters that *out asks for, each straight to where it wants
-// them, and the head into `head`; copies on c's stream, not waited for.
-static int escape_read_planes(mcrat_hip_ctx *c, const EscapePlan &plan, const char *d, mcrat_hip_escape_observation *out, char *head)
-{
-    const size_t plane = sizeof(double) * (size_t)plan.n_bins, counters = sizeof(long long) * (size_t)plan.n_obs;
-    void *planes[ESCAPE_PLANES] = {out->count, out->w, out->we, out->i, out->q, out->u, out->v, out->wx, out->wex};
-    for (int k = 0; k < ESCAPE_PLANES; ++k)
-        if (planes[k]) HIPCHK(c, hipMemcpyAsync(planes[k], d + plane * (size_t)k, plane, hipMemcpyDeviceToHost, c->stream));
-    long long *per_observer[ESCAPE_COUNTERS] = {out->n_accepted, out->n_outside, out->n_opaque, out->n_unresolved};
-    for (int k = 0; k < ESCAPE_COUNTERS; ++k)
-        if (per_observer[k]) HIPCHK(c, hipMemcpyAsync(per_observer[k], d + plan.counters_offset + counters * (size_t)k, counters, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(head, d + plan.head_offset, sizeof(long long) * ESCAPE_HEAD_WORDS, hipMemcpyDeviceToHost, c->stream));
-    return MCRAT_HIP_OK;
-}
-
-// The photons of c->ph -- n_slots of them -- that an observer accepts, marched through h's staged frame and binned (escape_plan.hpp, escape.hip):
-// check, block, stage, three launches, the read-back (escape_fill_outputs), one synchronise, the outputs filled in.  clocks: one per slots_per_clock slots (a rank pool's lists), or nullptr and
-// time_now for all.
-static int escape_run(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_escape_observer *obs, int n_slots, const double *clocks, int n_clocks,
-                      int slots_per_clock, double time_now, mcrat_hip_escape_observation *out)
+// The photons of c->ph that src names and an observer accepts, marched through h's staged frame and binned (escape_plan.hpp, escape.hip): check,
+// block, stage -- the sky observation's inputs, then tau_edges, the clocks behind them --, three launches, the read-back (escape_fill_outputs), one
+// synchronise, the outputs filled in.
+static int escape_run(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_escape_observer *obs, const PhotonSource &src, mcrat_hip_escape_observation *out)
 {
     c->esc_path = OBSERVE_PATH_NONE;
     EscapeArgs args{};
@@ -4450,11 +4441,12 @@ static int escape_run(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_
     int rc = escape_check(c, hydro, obs, &args, &plan, &h);
     if (rc) return rc;
 
-    const EscapeLayout lay = escape_layout(plan, n_slots, clocks ? n_clocks : 0);
+    const int n_slots = src.n_slots;
+    const EscapeLayout lay = escape_layout(plan, n_slots, src.clocks ? src.n_clocks : 0);
     char *d = nullptr;
     if ((rc = analysis_block(c, h, mcrat_hip_ctx::BLOCK_ESCAPE, lay.total_bytes, &d))) return rc;
 
-    const std::vector<double> in = escape_staged_inputs(args, plan, clocks, n_clocks);
+    const std::vector<double> in = staged_inputs(args.sky, plan.image, plan.image, plan.staged_doubles, args.tau_edges, (size_t)plan.n_tau + 1, src);
     HIPCHK(c, hipMemsetAsync(d, 0, plan.out_bytes, c->stream));
     HIPCHK(c, hipMemcpyAsync(d + lay.staged_offset, in.data(), sizeof(double) * in.size(), hipMemcpyHostToDevice, c->stream));
 
@@ -4462,9 +4454,9 @@ static int escape_run(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_
     a.n_slots = n_slots; a.n_obs = plan.n_obs; a.n_tau = plan.n_tau; a.n_t = plan.n_t; a.n_e = plan.n_e; a.n_x = plan.n_x; a.n_y = plan.n_y; a.n_bins = plan.n_bins;
     a.step_frac = plan.march.step_frac; a.h_min = plan.march.h_min; a.max_steps = plan.march.max_steps; a.tau_stop = plan.march.tau_stop;
     a.staged = reinterpret_cast<const double *>(d + lay.staged_offset);
-    a.clocks = clocks ? reinterpret_cast<const double *>(d + lay.clocks_offset) : nullptr;
-    a.slots_per_clock = slots_per_clock;
-    a.time_now = time_now;
+    a.clocks = src.clocks ? reinterpret_cast<const double *>(d + lay.clocks_offset) : nullptr;
+    a.slots_per_clock = src.slots_per_clock;
+    a.time_now = src.time_now;
     a.cube = reinterpret_cast<double *>(d);
     a.counters = reinterpret_cast<unsigned long long *>(d + plan.counters_offset);
     a.head = reinterpret_cast<unsigned long long *>(d + plan.head_offset);
@@ -4478,8 +4470,14 @@ static int escape_run(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_
     const bool whole = plan.out_bytes <= ESCAPE_ONE_COPY_BYTES;
     const size_t first = whole ? 0 : plan.head_offset;
     std::vector<char> host(plan.out_bytes - first);
-    if (whole) HIPCHK(c, hipMemcpyAsync(host.data(), d, plan.out_bytes, hipMemcpyDeviceToHost, c->stream));
-    else if ((rc = escape_read_planes(c, plan, d, out, host.data()))) return rc;
+    if (!whole) {                                // the planes and per-observer counters that *out asks for, each straight to where it wants them
+        const size_t plane = sizeof(double) * (size_t)plan.n_bins, counters = sizeof(long long) * (size_t)plan.n_obs;
+        void *planes[ESCAPE_PLANES] = {out->count, out->w, out->we, out->i, out->q, out->u, out->v, out->wx, out->wex};
+        void *per_observer[ESCAPE_COUNTERS] = {out->n_accepted, out->n_outside, out->n_opaque, out->n_unresolved};
+        if ((rc = read_columns(c, d, plane, plane, planes, ESCAPE_PLANES)) ||
+            (rc = read_columns(c, d + plan.counters_offset, counters, counters, per_observer, ESCAPE_COUNTERS))) return rc;
+    }
+    HIPCHK(c, hipMemcpyAsync(host.data(), d + first, host.size(), hipMemcpyDeviceToHost, c->stream));          // all of it, or the head, which lies last
     HIPCHK(c, hipStreamSynchronize(c->stream));
     escape_fill_outputs(plan, host.data(), first, out);
     c->esc_path = plan.path;
@@ -4490,30 +4488,26 @@ extern "C" int mcrat_hip_observe_escaping(mcrat_hip_ctx *c, const mcrat_hip_ctx 
                                           mcrat_hip_escape_observation *out)
 {
     if (!c || !obs || !out) return MCRAT_HIP_EINVAL;
-    if (!c->have_photons) return MCRAT_HIP_ESTATE;
-    if (c->is_pool) { c->last_error = "observe_escaping: a rank pool's lists have clocks of their own (mcrat_hip_pool_observe_escaping, or mcrat_hip_observe_escaping on a view)"; return MCRAT_HIP_ESTATE; }
-    int rc = flush_pending(c);
-    if (rc) return rc;
-    return escape_run(c, hydro, obs, c->ph.n, nullptr, 0, 1, time_now, out);
+    PhotonSource src;
+    int rc = list_photons(c, time_now, "observe_escaping: a rank pool's lists have clocks of their own (mcrat_hip_pool_observe_escaping, or mcrat_hip_observe_escaping on a view)", false, &src);
+    return rc ? rc : escape_run(c, hydro, obs, src, out);
 }
 
 extern "C" int mcrat_hip_pool_observe_escaping(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_escape_observer *obs, const double *time_now,
                                                mcrat_hip_escape_observation *out)
 {
     if (!c || !obs || !time_now || !out) return MCRAT_HIP_EINVAL;
-    if (!c->is_pool) { c->last_error = "pool_observe_escaping: the context is no rank pool"; return MCRAT_HIP_ESTATE; }
-    // every slot of the pool, exactly as mcrat_hip_pool_observe_sky reads them, and like it without flush_pending
-    return escape_run(c, hydro, obs, c->ph.n, time_now, c->n_ranks, c->rank_stride, 0.0, out);
+    PhotonSource src;
+    int rc = pool_photons(c, time_now, "pool_observe_escaping: the context is no rank pool", &src);
+    return rc ? rc : escape_run(c, hydro, obs, src, out);
 }
 
 extern "C" int mcrat_hip_observe_escaping_path(const mcrat_hip_ctx *c) { return c ? c->esc_path : 0; }
 
 // ---------------------------------------------------------------------------------------------- sky observations with a resampling axis
-// The photons of c->ph -- n_slots of them -- binned as sky_run bins them, with a replica axis behind the observer and, on request, Q and U in the
+// The photons of c->ph that src names binned as sky_run bins them, with a replica axis behind the observer and, on request, Q and U in the
 // observer's frame (resample_plan.hpp, resample.hip): a cube job like sky_run's, with a third per-observer counter read back beside the two.
-// rank_base, rank_stride: the photons' identities (launch.hpp, ResampleDev).
-static int resample_run(mcrat_hip_ctx *c, const mcrat_hip_resample_observer *obs, int n_slots, const double *clocks, int n_clocks, int slots_per_clock, double time_now,
-                        int rank_base, int rank_stride, mcrat_hip_resample_observation *out)
+static int resample_run(mcrat_hip_ctx *c, const mcrat_hip_resample_observer *obs, const PhotonSource &src, mcrat_hip_resample_observation *out)
 {
     c->rs_path = RESAMPLE_PATH_NONE;
     ResampleArgs args{};
@@ -4529,32 +4523,16 @@ static int resample_run(mcrat_hip_ctx *c, const mcrat_hip_resample_observer *obs
         c->last_error = resample_refusal_text(why, text);
         return MCRAT_HIP_EINVAL;
     }
-    // the inputs in the order the kernel stages them (resample_plan.hpp: ex and ey for SKY_PLANE too), the clocks behind them
-    std::vector<double> in;
-    {
-        const SkyArgs &s = args.sky;
-        const size_t n_obs = (size_t)plan.n_obs;
-        in.reserve(plan.staged_doubles + (size_t)n_clocks);
-        for (const double *v : {s.n0, s.n1, s.n2, s.cos_acc}) in.insert(in.end(), v, v + n_obs);
-        if (plan.axes)
-            for (const double *v : {s.x0, s.x1, s.x2, s.y0, s.y1, s.y2}) in.insert(in.end(), v, v + n_obs);
-        in.insert(in.end(), s.t_edges, s.t_edges + plan.n_t + 1);
-        in.insert(in.end(), s.e_edges, s.e_edges + plan.n_e + 1);
-        if (plan.image) {
-            in.insert(in.end(), s.x_edges, s.x_edges + plan.n_x + 1);
-            in.insert(in.end(), s.y_edges, s.y_edges + plan.n_y + 1);
-        }
-        if (clocks) in.insert(in.end(), clocks, clocks + n_clocks);
-    }
-    const ResampleGrid grid = resample_grid(plan, n_slots, device_cus(c));
+    const std::vector<double> in = staged_inputs(args.sky, plan.axes, plan.image, plan.staged_doubles, nullptr, 0, src);     // (ex and ey for SKY_PLANE too)
+    const ResampleGrid grid = resample_grid(plan, src.n_slots, device_cus(c));
     ResampleDev a{};
-    a.n_slots = n_slots; a.n_obs = plan.n_obs; a.n_rep = plan.n_rep; a.n_t = plan.n_t; a.n_e = plan.n_e; a.n_x = plan.n_x; a.n_y = plan.n_y;
+    a.n_slots = src.n_slots; a.n_obs = plan.n_obs; a.n_rep = plan.n_rep; a.n_t = plan.n_t; a.n_e = plan.n_e; a.n_x = plan.n_x; a.n_y = plan.n_y;
     a.n_bins = plan.n_bins; a.per_rep = plan.per_rep; a.mode = plan.mode; a.axes = plan.axes ? 1 : 0;
     a.slice_reps = plan.slice_reps; a.n_slices = plan.n_slices; a.grid_x = grid.x; a.grid_y = grid.y;
-    a.seed = obs->seed; a.rank_base = rank_base; a.rank_stride = rank_stride;
-    a.slots_per_clock = slots_per_clock;
-    a.time_now = time_now;
-    const int rc = cube_run(c, mcrat_hip_ctx::BLOCK_RESAMPLE, plan, in, clocks != nullptr, a, [&](const ResampleDev &placed) -> int {
+    a.seed = obs->seed; a.rank_base = src.rank_base; a.rank_stride = src.rank_stride;
+    a.slots_per_clock = src.slots_per_clock;
+    a.time_now = src.time_now;
+    const int rc = cube_run(c, mcrat_hip_ctx::BLOCK_RESAMPLE, plan, in, src.clocks != nullptr, a, [&](const ResampleDev &placed) -> int {
         ResampleDev dev = placed;
         dev.n_undefined = dev.n_outside + plan.n_obs;                  // the third counter, inside what cube_run has zeroed (plan.out_bytes)
         HIPCHK(c, launch_resample(c->ph, dev, plan, c->kc.stokes != 0, grid.x, grid.y, c->stream));
@@ -4570,30 +4548,27 @@ static int resample_run(mcrat_hip_ctx *c, const mcrat_hip_resample_observer *obs
 extern "C" int mcrat_hip_observe_sky_resampled(mcrat_hip_ctx *c, const mcrat_hip_resample_observer *obs, double time_now, mcrat_hip_resample_observation *out)
 {
     if (!c || !obs || !out) return MCRAT_HIP_EINVAL;
-    if (!c->have_photons) return MCRAT_HIP_ESTATE;
-    if (c->is_pool) { c->last_error = "observe_sky_resampled: a rank pool's lists have clocks of their own (mcrat_hip_pool_observe_sky_resampled, or mcrat_hip_observe_sky_resampled on a view)"; return MCRAT_HIP_ESTATE; }
-    int rc = flush_pending(c);
-    if (rc) return rc;
-    return resample_run(c, obs, c->ph.n, nullptr, 0, 1, time_now, c->parent ? c->view_rank : 0, 0, out);
+    PhotonSource src;
+    int rc = list_photons(c, time_now, "observe_sky_resampled: a rank pool's lists have clocks of their own (mcrat_hip_pool_observe_sky_resampled, or mcrat_hip_observe_sky_resampled on a view)", false, &src);
+    return rc ? rc : resample_run(c, obs, src, out);
 }
 
 extern "C" int mcrat_hip_pool_observe_sky_resampled(mcrat_hip_ctx *c, const mcrat_hip_resample_observer *obs, const double *time_now, mcrat_hip_resample_observation *out)
 {
     if (!c || !obs || !time_now || !out) return MCRAT_HIP_EINVAL;
-    if (!c->is_pool) { c->last_error = "pool_observe_sky_resampled: the context is no rank pool"; return MCRAT_HIP_ESTATE; }
-    // every slot of the pool, exactly as mcrat_hip_pool_observe_sky reads them, and like it without flush_pending
-    return resample_run(c, obs, c->ph.n, time_now, c->n_ranks, c->rank_stride, 0.0, 0, c->rank_stride, out);
+    PhotonSource src;
+    int rc = pool_photons(c, time_now, "pool_observe_sky_resampled: the context is no rank pool", &src);
+    return rc ? rc : resample_run(c, obs, src, out);
 }
 
 extern "C" int mcrat_hip_observe_sky_resampled_path(const mcrat_hip_ctx *c) { return c ? c->rs_path : 0; }
 
 // ---------------------------------------------------------------------------------------------- detected-photon event lists
-// The photons of c->ph -- n_slots of them -- as rows per observer (events_plan.hpp, events.hip): check, block, stage, the launches, the read-back, one
-// synchronise, the counters handed over.  clocks: one per slots_per_clock slots (a rank pool's lists), or nullptr and time_now for all.  rank_base,
-// rank_stride: the photons' identities (launch.hpp, ResampleDev).
-static int events_run(mcrat_hip_ctx *c, const mcrat_hip_events_observer *obs, int n_slots, const double *clocks, int n_clocks, int slots_per_clock, double time_now,
-                      int rank_base, int rank_stride, mcrat_hip_events *out)
+// The photons of c->ph that src names as rows per observer (events_plan.hpp, events.hip): check, block, stage, the launches, the read-back, one
+// synchronise, the counters handed over.
+static int events_run(mcrat_hip_ctx *c, const mcrat_hip_events_observer *obs, const PhotonSource &src, mcrat_hip_events *out)
 {
+    const int n_slots = src.n_slots;
     if (!obs->n0 || !obs->n1 || !obs->n2 || !obs->cos_acc) {
         c->last_error = "observe_events: a null array in mcrat_hip_events_observer";
         return MCRAT_HIP_EINVAL;
@@ -4607,32 +4582,31 @@ static int events_run(mcrat_hip_ctx *c, const mcrat_hip_events_observer *obs, in
         c->last_error = events_refusal_text(why, text);
         return MCRAT_HIP_EINVAL;
     }
-    const EventsLayout lay = events_layout(plan, n_slots, clocks ? n_clocks : 0);
+    const EventsLayout lay = events_layout(plan, n_slots, src.clocks ? src.n_clocks : 0);
     char *d = nullptr;
     int rc = analysis_block(c, nullptr, mcrat_hip_ctx::BLOCK_EVENTS, lay.total_bytes, &d);
     if (rc) return rc;
 
-    // the observers in the order the kernels read them, the clocks in their own part of the block
+    // the observers' vectors in the order the kernels read them, no edges; the clocks in their own part of the block
     const size_t n_obs = (size_t)plan.n_obs;
+    const SkyArgs vectors{plan.n_obs, args.n0, args.n1, args.n2, args.cos_acc, args.x0, args.x1, args.x2, args.y0, args.y1, args.y2};
     std::vector<double> in;
     in.reserve(plan.staged_doubles);
-    for (const double *v : {args.n0, args.n1, args.n2, args.cos_acc}) in.insert(in.end(), v, v + n_obs);
-    if (plan.axes)
-        for (const double *v : {args.x0, args.x1, args.x2, args.y0, args.y1, args.y2}) in.insert(in.end(), v, v + n_obs);
+    stage_observer_inputs(vectors, plan.axes, false, false, &in);
     HIPCHK(c, hipMemsetAsync(d, 0, 8 * plan.head_words, c->stream));
     HIPCHK(c, hipMemcpyAsync(d + lay.staged_offset, in.data(), sizeof(double) * in.size(), hipMemcpyHostToDevice, c->stream));
-    if (clocks) HIPCHK(c, hipMemcpyAsync(d + lay.clocks_offset, clocks, sizeof(double) * (size_t)n_clocks, hipMemcpyHostToDevice, c->stream));
+    if (src.clocks) HIPCHK(c, hipMemcpyAsync(d + lay.clocks_offset, src.clocks, sizeof(double) * (size_t)src.n_clocks, hipMemcpyHostToDevice, c->stream));
 
     EventsDev a{};
     a.n_slots = n_slots; a.n_obs = plan.n_obs; a.n_chunks = events_n_chunks(n_slots); a.chunk_slots = events_chunk_slots(n_slots);
     a.order = plan.order; a.sky_plane = plan.frame == STOKES_SKY_PLANE ? 1 : 0; a.axes = plan.axes ? 1 : 0;
     a.capacity = plan.capacity; a.n_tiles = plan.order == EVENTS_BY_TIME ? events_sort_tiles(plan.capacity) : 0;
     a.t_lo = args.t_lo; a.t_hi = args.t_hi; a.e_lo = args.e_lo; a.e_hi = args.e_hi;
-    a.rank_base = rank_base; a.rank_stride = rank_stride;
+    a.rank_base = src.rank_base; a.rank_stride = src.rank_stride;
     a.staged = reinterpret_cast<const double *>(d + lay.staged_offset);
-    a.clocks = clocks ? reinterpret_cast<const double *>(d + lay.clocks_offset) : nullptr;
-    a.slots_per_clock = slots_per_clock;
-    a.time_now = time_now;
+    a.clocks = src.clocks ? reinterpret_cast<const double *>(d + lay.clocks_offset) : nullptr;
+    a.slots_per_clock = src.slots_per_clock;
+    a.time_now = src.time_now;
     unsigned long long *head = reinterpret_cast<unsigned long long *>(d);
     a.n_accepted = head; a.n_outside = head + n_obs; a.n_undefined = head + 2 * n_obs;
     a.offsets = head + events_head_offsets_word(plan);
@@ -4659,9 +4633,8 @@ static int events_run(mcrat_hip_ctx *c, const mcrat_hip_events_observer *obs, in
     if (cap) {
         if (out->rank) HIPCHK(c, hipMemcpyAsync(out->rank, a.rank, sizeof(int) * cap, hipMemcpyDeviceToHost, c->stream));
         if (out->slot) HIPCHK(c, hipMemcpyAsync(out->slot, a.slot, sizeof(int) * cap, hipMemcpyDeviceToHost, c->stream));
-        double *wanted[EVENTS_F8_COLUMNS] = {out->t, out->e, out->w, out->s0, out->s1, out->s2, out->s3, out->num_scatt, out->X, out->Y};
-        for (int k = 0; k < (plan.axes ? EVENTS_F8_COLUMNS : EVENTS_F8_COLUMNS - 2); ++k)
-            if (wanted[k]) HIPCHK(c, hipMemcpyAsync(wanted[k], *f8[k], sizeof(double) * cap, hipMemcpyDeviceToHost, c->stream));
+        void *wanted[EVENTS_F8_COLUMNS] = {out->t, out->e, out->w, out->s0, out->s1, out->s2, out->s3, out->num_scatt, out->X, out->Y};
+        if ((rc = read_columns(c, d + lay.f8_offset, lay.f8_pitch, sizeof(double) * cap, wanted, plan.axes ? EVENTS_F8_COLUMNS : EVENTS_F8_COLUMNS - 2))) return rc;
         if (out->type) HIPCHK(c, hipMemcpyAsync(out->type, a.type, cap, hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -4699,19 +4672,17 @@ static int events_run(mcrat_hip_ctx *c, const mcrat_hip_events_observer *obs, in
 extern "C" int mcrat_hip_observe_events(mcrat_hip_ctx *c, const mcrat_hip_events_observer *obs, double time_now, mcrat_hip_events *out)
 {
     if (!c || !obs || !out) return MCRAT_HIP_EINVAL;
-    if (!c->have_photons) return MCRAT_HIP_ESTATE;
-    if (c->is_pool) { c->last_error = "observe_events: a rank pool's lists have clocks of their own (mcrat_hip_pool_observe_events, or mcrat_hip_observe_events on a view)"; return MCRAT_HIP_ESTATE; }
-    int rc = flush_pending(c);
-    if (rc) return rc;
-    return events_run(c, obs, c->ph.n, nullptr, 0, 1, time_now, c->parent ? c->view_rank : 0, 0, out);
+    PhotonSource src;
+    int rc = list_photons(c, time_now, "observe_events: a rank pool's lists have clocks of their own (mcrat_hip_pool_observe_events, or mcrat_hip_observe_events on a view)", false, &src);
+    return rc ? rc : events_run(c, obs, src, out);
 }
 
 extern "C" int mcrat_hip_pool_observe_events(mcrat_hip_ctx *c, const mcrat_hip_events_observer *obs, const double *time_now, mcrat_hip_events *out)
 {
     if (!c || !obs || !time_now || !out) return MCRAT_HIP_EINVAL;
-    if (!c->is_pool) { c->last_error = "pool_observe_events: the context is no rank pool"; return MCRAT_HIP_ESTATE; }
-    // every slot of the pool, exactly as mcrat_hip_pool_observe_sky reads them, and like it without flush_pending
-    return events_run(c, obs, c->ph.n, time_now, c->n_ranks, c->rank_stride, 0.0, 0, c->rank_stride, out);
+    PhotonSource src;
+    int rc = pool_photons(c, time_now, "pool_observe_events: the context is no rank pool", &src);
+    return rc ? rc : events_run(c, obs, src, out);
 }
 
 // ---------------------------------------------------------------------------------------------- spectral fits
@@ -4747,38 +4718,83 @@ extern "C" int mcrat_hip_fit_spectra(mcrat_hip_ctx *c, const mcrat_hip_fit_args 
     for (int k = 0; k < FIT_I4_COLUMNS; ++k) *i4[k] = reinterpret_cast<int *>(d + plan.i4_offset + plan.i4_pitch * (size_t)k);
     HIPCHK(c, launch_fit(a, plan, c->stream));
     if (rows) {
-        double *wanted[FIT_F8_COLUMNS] = {out->alpha, out->beta, out->e_peak, out->amplitude, out->chi2};
-        for (int k = 0; k < FIT_F8_COLUMNS; ++k)
-            if (wanted[k]) HIPCHK(c, hipMemcpyAsync(wanted[k], *f8[k], sizeof(double) * rows, hipMemcpyDeviceToHost, c->stream));
-        int *wanted_i[FIT_I4_COLUMNS] = {out->n_used, out->dof, out->status};
-        for (int k = 0; k < FIT_I4_COLUMNS; ++k)
-            if (wanted_i[k]) HIPCHK(c, hipMemcpyAsync(wanted_i[k], *i4[k], sizeof(int) * rows, hipMemcpyDeviceToHost, c->stream));
+        void *wanted[FIT_F8_COLUMNS] = {out->alpha, out->beta, out->e_peak, out->amplitude, out->chi2};
+        void *wanted_i[FIT_I4_COLUMNS] = {out->n_used, out->dof, out->status};
+        if ((rc = read_columns(c, d + plan.f8_offset, plan.f8_pitch, sizeof(double) * rows, wanted, FIT_F8_COLUMNS)) ||
+            (rc = read_columns(c, d + plan.i4_offset, plan.i4_pitch, sizeof(int) * rows, wanted_i, FIT_I4_COLUMNS))) return rc;
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return MCRAT_HIP_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- the two fields on the hydro mesh
+// What the radiation field and the comoving field share: the frame whose cells the photons are located in, and the job on their block.
+
+// *h: the context whose staged frame the photons are located in.  The caller has checked its bins: EINVAL before ESTATE, as the headers order them.
+static int field_frame(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const char *mismatch, const char *no_frame, const mcrat_hip_ctx **h)
+{
+    switch (frame_of(c, hydro, false, true, h)) {
+    case FRAME_MISMATCH: c->last_error = mismatch; return MCRAT_HIP_EINVAL;
+    case FRAME_NONE: c->last_error = no_frame; return MCRAT_HIP_ESTATE;
+    default: return MCRAT_HIP_OK;
+    }
+}
+
+// A field job, on cube_run's model: the block for `plan`, one memset, one copy of the edges when there are any, the launch -- timed with
+// cfg.profile --, the planes and the head's three counters read back to wherever *out wants them.  `a` comes with everything but its device
+// pointers; launch(a, where the planes lie) returns an MCRAT_HIP_* code.
+template <class Plan, class Dev, class Launch, class Out>
+static int field_run(mcrat_hip_ctx *c, const mcrat_hip_ctx *h, int which, const Plan &plan, const std::vector<double> &edges, Dev a, Launch launch,
+                     void *const *planes, int n_planes, Out *out)
+{
+    char *d = nullptr;
+    int rc = analysis_block(c, h, which, plan.total_bytes, &d);
+    if (rc) return rc;
+    a.staged = reinterpret_cast<const double *>(d + plan.staged_offset);
+    a.head = reinterpret_cast<unsigned long long *>(d);
+    a.acc = reinterpret_cast<double *>(d + RADFIELD_ACC_OFFSET);
+    HIPCHK(c, hipMemsetAsync(d, 0, plan.zeroed_bytes, c->stream));
+    if (!edges.empty()) HIPCHK(c, hipMemcpyAsync(d + plan.staged_offset, edges.data(), sizeof(double) * edges.size(), hipMemcpyHostToDevice, c->stream));
+    c->prof_step_ms = 0; c->prof_launches = 0;                   // (cfg.profile: the kernel's own duration, mcrat_hip_profile_totals)
+    if ((rc = profiled(c, 1, [&]() -> int { return launch(a, reinterpret_cast<double *>(d + plan.planes_offset)); }))) return rc;
+    const size_t plane = sizeof(double) * (size_t)plan.n_bins;
+    static_assert(sizeof(long long) == 8 && COMOVING_ACC_OFFSET == RADFIELD_ACC_OFFSET, "the count plane and the counters are read back as they are; one head for both fields");
+    if ((rc = read_columns(c, d + plan.planes_offset, plane, plane, planes, n_planes))) return rc;
+    long long head[RADFIELD_N_SCALARS];
+    HIPCHK(c, hipMemcpyAsync(head, d, sizeof(head), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    out->n_observable = head[RF_N_OBSERVABLE]; out->n_unlocated = head[RF_N_UNLOCATED]; out->n_outside = head[RF_N_OUTSIDE];
+    return MCRAT_HIP_OK;
+}
+
+// The _bins entry points: the product's checks alone (`prepare`), for the number of bins.
+template <class Plan, class Bins, class Prepare>
+static int field_bins(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const Bins *bins, int *n_bins, Prepare prepare)
+{
+    if (!c || !bins || !n_bins) return MCRAT_HIP_EINVAL;
+    const mcrat_hip_ctx *h = nullptr;
+    Plan plan;
+    int rc = prepare(c, hydro, bins, &h, &plan);
+    if (rc) return rc;
+    *n_bins = plan.n_bins;
+    return MCRAT_HIP_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- the radiation field on the hydro mesh
-// The checks of radfield_plan.hpp on the caller's bins, then the frame: *h is the context whose staged frame the photons are located in, *plan the
-// block for its cells.  EINVAL comes before ESTATE, in the order the header gives.
-static int radfield_prepare(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_radfield_bins *bins, const mcrat_hip_ctx **h_out, RadfieldPlan *plan)
+// The checks of radfield_plan.hpp on the caller's bins, then the frame: *plan is the block for its cells.
+static int radfield_prepare(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_radfield_bins *bins, const mcrat_hip_ctx **h, RadfieldPlan *plan)
 {
     RadfieldShape shape;
     const RadfieldRefusal why = radfield_check(bins->mode, bins->n_r, bins->r_edges, bins->n_mu, bins->mu_edges, getenv("MCRAT_HIP_RADFIELD_PATH"), &shape);
     if (why != RADFIELD_OK) { c->last_error = radfield_refusal_text(why); return MCRAT_HIP_EINVAL; }
-    const mcrat_hip_ctx *h = hydro ? hydro : c;
-    if (h != c && (h->kc.dimensions != c->kc.dimensions || h->kc.geometry != c->kc.geometry || h->cfg.device != c->cfg.device)) {
-        c->last_error = radfield_refusal_text(RADFIELD_HYDRO_MISMATCH);
-        return MCRAT_HIP_EINVAL;
-    }
-    if (!h->have_hydro || h->hy.M <= 0) { c->last_error = "radiation_field: no staged hydro frame"; return MCRAT_HIP_ESTATE; }
-    *plan = radfield_layout(shape, h->hy.M);
-    *h_out = h;
+    int rc = field_frame(c, hydro, radfield_refusal_text(RADFIELD_HYDRO_MISMATCH), "radiation_field: no staged hydro frame", h);
+    if (rc) return rc;
+    *plan = radfield_layout(shape, (*h)->hy.M);
     return MCRAT_HIP_OK;
 }
 
-// The n_slots slots of c->ph located in the frame of `hydro` and summed per bin (radfield_plan.hpp, radfield.hip): one memset, one copy of the
-// edges, one launch (a bin-major build: and the transposition), the planes read back.
+// The n_slots slots of c->ph located in the frame of `hydro` and summed per bin (radfield_plan.hpp, radfield.hip): a field job whose launch is,
+// for a bin-major build, followed by the transposition.
 static int radfield_run(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_radfield_bins *bins, int n_slots, mcrat_hip_radfield *out)
 {
     c->rf_path = OBSERVE_PATH_NONE;
@@ -4788,98 +4804,65 @@ static int radfield_run(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcra
     if (rc) return rc;
     if (n_slots <= 0) { c->last_error = "radiation_field: no photons"; return MCRAT_HIP_ESTATE; }
 
-    char *d = nullptr;
-    if ((rc = analysis_block(c, h, mcrat_hip_ctx::BLOCK_RADFIELD, plan.total_bytes, &d))) return rc;
     RadfieldDev a{};
     a.n_slots = n_slots; a.n_r = plan.s.n_r; a.n_mu = plan.s.n_mu; a.n_bins = plan.n_bins;
-    a.staged = reinterpret_cast<const double *>(d + plan.staged_offset);
-    a.head = reinterpret_cast<unsigned long long *>(d);
-    a.acc = reinterpret_cast<double *>(d + RADFIELD_ACC_OFFSET);
-    HIPCHK(c, hipMemsetAsync(d, 0, plan.zeroed_bytes, c->stream));
-    std::vector<double> in;
+    std::vector<double> edges;
     if (plan.s.mode == RADFIELD_SHELLS) {
-        in.insert(in.end(), bins->r_edges, bins->r_edges + plan.s.n_r + 1);
-        in.insert(in.end(), bins->mu_edges, bins->mu_edges + plan.s.n_mu + 1);
-        HIPCHK(c, hipMemcpyAsync(d + plan.staged_offset, in.data(), sizeof(double) * in.size(), hipMemcpyHostToDevice, c->stream));
+        edges.insert(edges.end(), bins->r_edges, bins->r_edges + plan.s.n_r + 1);
+        edges.insert(edges.end(), bins->mu_edges, bins->mu_edges + plan.s.n_mu + 1);
     }
     const int cus = device_cus(c);
-    c->prof_step_ms = 0; c->prof_launches = 0;                   // (cfg.profile: the kernel's own duration, mcrat_hip_profile_totals)
-    rc = profiled(c, 1, [&]() -> int {
-        HIPCHK(c, launch_radfield(c->kc, c->ph, h->hy, a, plan, radfield_grid(plan, n_slots, cus), c->stream));
-        if (plan.bin_major) HIPCHK(c, launch_radfield_transpose(a.acc, reinterpret_cast<double *>(d + plan.planes_offset), plan.n_bins, cus, c->stream));
-        return MCRAT_HIP_OK;
-    });
-    if (rc) return rc;
-    const size_t plane = sizeof(double) * (size_t)plan.n_bins;
     void *planes[RADFIELD_PLANES] = {out->count, out->w, out->we_lab, out->we_comv, out->w_nscatt, out->w_temp};
-    static_assert(sizeof(long long) == 8, "the count plane and the counters are read back as they are");
-    for (int k = 0; k < RADFIELD_PLANES; ++k)
-        if (planes[k]) HIPCHK(c, hipMemcpyAsync(planes[k], d + plan.planes_offset + plane * (size_t)k, plane, hipMemcpyDeviceToHost, c->stream));
-    long long head[RADFIELD_N_SCALARS];
-    HIPCHK(c, hipMemcpyAsync(head, d, sizeof(head), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    out->n_observable = head[RF_N_OBSERVABLE]; out->n_unlocated = head[RF_N_UNLOCATED]; out->n_outside = head[RF_N_OUTSIDE];
+    rc = field_run(c, h, mcrat_hip_ctx::BLOCK_RADFIELD, plan, edges, a, [&](const RadfieldDev &dev, double *d_planes) -> int {
+        HIPCHK(c, launch_radfield(c->kc, c->ph, h->hy, dev, plan, radfield_grid(plan, n_slots, cus), c->stream));
+        if (plan.bin_major) HIPCHK(c, launch_radfield_transpose(dev.acc, d_planes, plan.n_bins, cus, c->stream));
+        return MCRAT_HIP_OK;
+    }, planes, RADFIELD_PLANES, out);
+    if (rc) return rc;
     c->rf_path = plan.s.path;
     return MCRAT_HIP_OK;
 }
 
 extern "C" int mcrat_hip_radiation_field_bins(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_radfield_bins *bins, int *n_bins)
 {
-    if (!c || !bins || !n_bins) return MCRAT_HIP_EINVAL;
-    const mcrat_hip_ctx *h = nullptr;
-    RadfieldPlan plan;
-    int rc = radfield_prepare(c, hydro, bins, &h, &plan);
-    if (rc) return rc;
-    *n_bins = plan.n_bins;
-    return MCRAT_HIP_OK;
+    return field_bins<RadfieldPlan>(c, hydro, bins, n_bins, radfield_prepare);
 }
 
 extern "C" int mcrat_hip_radiation_field(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_radfield_bins *bins, mcrat_hip_radfield *out)
 {
     if (!c || !bins || !out) return MCRAT_HIP_EINVAL;
-    if (c->is_pool) { c->last_error = "radiation_field: one list is a stand-alone context or a view of a pool (mcrat_hip_pool_radiation_field takes the pool)"; return MCRAT_HIP_ESTATE; }
-    if (c->have_photons) {
-        int rc = flush_pending(c);
-        if (rc) return rc;
-    }
-    return radfield_run(c, hydro, bins, c->have_photons ? c->ph.n : 0, out);
+    PhotonSource src;                            // (a context without photons goes on to the checks, then "no photons")
+    int rc = list_photons(c, 0.0, "radiation_field: one list is a stand-alone context or a view of a pool (mcrat_hip_pool_radiation_field takes the pool)", true, &src);
+    return rc ? rc : radfield_run(c, hydro, bins, src.n_slots, out);
 }
 
 extern "C" int mcrat_hip_pool_radiation_field(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_radfield_bins *bins, mcrat_hip_radfield *out)
 {
     if (!c || !bins || !out) return MCRAT_HIP_EINVAL;
-    if (!c->is_pool) { c->last_error = "pool_radiation_field: the context is no rank pool"; return MCRAT_HIP_ESTATE; }
-    // every slot of the pool, as mcrat_hip_pool_observe reads them (a selected capture included: c->ph is that capture's columns): slots beyond a
-    // list's length and lists never created are not FLAG_VALID
-    int rc = flush_pending(c);
-    if (rc) return rc;
-    return radfield_run(c, hydro, bins, c->ph.n, out);
+    PhotonSource src;
+    int rc = pool_photons(c, nullptr, "pool_radiation_field: the context is no rank pool", &src);
+    if (!rc) rc = flush_pending(c);              // (unlike the observers' pool calls)
+    return rc ? rc : radfield_run(c, hydro, bins, src.n_slots, out);
 }
 
 extern "C" int mcrat_hip_radiation_field_path(const mcrat_hip_ctx *c) { return c ? c->rf_path : 0; }
 
 // ---------------------------------------------------------------------------------------------- the comoving radiation field
-// The checks of comoving_plan.hpp on the caller's bins, then the frame, as radfield_prepare: *h is the context whose staged frame the photons are
-// located in, *plan the block for its cells (CELLS: the product of the three axes is checked here, once the cells are known).
-static int comoving_prepare(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_comoving_bins *bins, const mcrat_hip_ctx **h_out, ComovingPlan *plan)
+// The checks of comoving_plan.hpp on the caller's bins, then the frame, as radfield_prepare: *plan is the block for its cells (CELLS: the product
+// of the three axes is checked here, once the cells are known).
+static int comoving_prepare(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_comoving_bins *bins, const mcrat_hip_ctx **h, ComovingPlan *plan)
 {
     ComovingShape shape;
     ComovingRefusal why = comoving_check(bins->mode, bins->n_r, bins->r_edges, bins->n_mu, bins->mu_edges, bins->n_e, bins->e_edges, bins->n_a, bins->a_edges,
                                          getenv("MCRAT_HIP_COMOVING_PATH"), &shape);
     if (why != COMOVING_OK) { c->last_error = comoving_refusal_text(why); return MCRAT_HIP_EINVAL; }
-    const mcrat_hip_ctx *h = hydro ? hydro : c;
-    if (h != c && (h->kc.dimensions != c->kc.dimensions || h->kc.geometry != c->kc.geometry || h->cfg.device != c->cfg.device)) {
-        c->last_error = comoving_refusal_text(COMOVING_HYDRO_MISMATCH);
-        return MCRAT_HIP_EINVAL;
-    }
-    if (!h->have_hydro || h->hy.M <= 0) { c->last_error = "comoving_field: no staged hydro frame"; return MCRAT_HIP_ESTATE; }
-    if ((why = comoving_layout(shape, h->hy.M, plan)) != COMOVING_OK) { c->last_error = comoving_refusal_text(why); return MCRAT_HIP_EINVAL; }
-    *h_out = h;
+    int rc = field_frame(c, hydro, comoving_refusal_text(COMOVING_HYDRO_MISMATCH), "comoving_field: no staged hydro frame", h);
+    if (rc) return rc;
+    if ((why = comoving_layout(shape, (*h)->hy.M, plan)) != COMOVING_OK) { c->last_error = comoving_refusal_text(why); return MCRAT_HIP_EINVAL; }
     return MCRAT_HIP_OK;
 }
 
-// The n_slots slots of c->ph located in the frame of `hydro`, boosted and summed per bin (comoving_plan.hpp, comoving.hip): one memset, one copy of
-// the edges, one launch, the planes read back.
+// The n_slots slots of c->ph located in the frame of `hydro`, boosted and summed per bin (comoving_plan.hpp, comoving.hip): a field job.
 static int comoving_run(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_comoving_bins *bins, int n_slots, mcrat_hip_comoving *out)
 {
     c->cf_path = OBSERVE_PATH_NONE;
@@ -4889,72 +4872,46 @@ static int comoving_run(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcra
     if (rc) return rc;
     if (n_slots <= 0) { c->last_error = "comoving_field: no photons"; return MCRAT_HIP_ESTATE; }
 
-    char *d = nullptr;
-    if ((rc = analysis_block(c, h, mcrat_hip_ctx::BLOCK_COMOVING, plan.total_bytes, &d))) return rc;
     ComovingDev a{};
     a.n_slots = n_slots; a.n_r = plan.s.n_r; a.n_mu = plan.s.n_mu; a.n_e = plan.s.n_e; a.n_a = plan.s.n_a; a.n_bins = plan.n_bins;
-    a.staged = reinterpret_cast<const double *>(d + plan.staged_offset);
-    a.head = reinterpret_cast<unsigned long long *>(d);
-    a.acc = reinterpret_cast<double *>(d + COMOVING_ACC_OFFSET);
-    HIPCHK(c, hipMemsetAsync(d, 0, plan.zeroed_bytes, c->stream));
-    std::vector<double> in;
+    std::vector<double> edges;
     if (plan.s.mode == COMOVING_SHELLS) {
-        in.insert(in.end(), bins->r_edges, bins->r_edges + plan.s.n_r + 1);
-        in.insert(in.end(), bins->mu_edges, bins->mu_edges + plan.s.n_mu + 1);
+        edges.insert(edges.end(), bins->r_edges, bins->r_edges + plan.s.n_r + 1);
+        edges.insert(edges.end(), bins->mu_edges, bins->mu_edges + plan.s.n_mu + 1);
     }
-    in.insert(in.end(), bins->e_edges, bins->e_edges + plan.s.n_e + 1);
-    in.insert(in.end(), bins->a_edges, bins->a_edges + plan.s.n_a + 1);
-    HIPCHK(c, hipMemcpyAsync(d + plan.staged_offset, in.data(), sizeof(double) * in.size(), hipMemcpyHostToDevice, c->stream));
+    edges.insert(edges.end(), bins->e_edges, bins->e_edges + plan.s.n_e + 1);
+    edges.insert(edges.end(), bins->a_edges, bins->a_edges + plan.s.n_a + 1);
     const int cus = device_cus(c);
-    c->prof_step_ms = 0; c->prof_launches = 0;                   // (cfg.profile: the kernel's own duration, mcrat_hip_profile_totals)
-    rc = profiled(c, 1, [&]() -> int {
-        HIPCHK(c, launch_comoving(c->kc, c->ph, h->hy, a, plan, comoving_grid(plan, n_slots, cus), c->stream));
-        return MCRAT_HIP_OK;
-    });
-    if (rc) return rc;
-    const size_t plane = sizeof(double) * (size_t)plan.n_bins;
     void *planes[COMOVING_PLANES] = {out->count, out->w, out->we, out->wea, out->weaa, out->we_lab, out->wem, out->wemm};
-    static_assert(sizeof(long long) == 8, "the count plane and the counters are read back as they are");
-    for (int k = 0; k < COMOVING_PLANES; ++k)
-        if (planes[k]) HIPCHK(c, hipMemcpyAsync(planes[k], d + plan.planes_offset + plane * (size_t)k, plane, hipMemcpyDeviceToHost, c->stream));
-    long long head[COMOVING_N_SCALARS];
-    HIPCHK(c, hipMemcpyAsync(head, d, sizeof(head), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    out->n_observable = head[RF_N_OBSERVABLE]; out->n_unlocated = head[RF_N_UNLOCATED]; out->n_outside = head[RF_N_OUTSIDE];
+    rc = field_run(c, h, mcrat_hip_ctx::BLOCK_COMOVING, plan, edges, a, [&](const ComovingDev &dev, double *) -> int {
+        HIPCHK(c, launch_comoving(c->kc, c->ph, h->hy, dev, plan, comoving_grid(plan, n_slots, cus), c->stream));
+        return MCRAT_HIP_OK;
+    }, planes, COMOVING_PLANES, out);
+    if (rc) return rc;
     c->cf_path = plan.s.path;
     return MCRAT_HIP_OK;
 }
 
 extern "C" int mcrat_hip_comoving_field_bins(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_comoving_bins *bins, int *n_bins)
 {
-    if (!c || !bins || !n_bins) return MCRAT_HIP_EINVAL;
-    const mcrat_hip_ctx *h = nullptr;
-    ComovingPlan plan;
-    int rc = comoving_prepare(c, hydro, bins, &h, &plan);
-    if (rc) return rc;
-    *n_bins = plan.n_bins;
-    return MCRAT_HIP_OK;
+    return field_bins<ComovingPlan>(c, hydro, bins, n_bins, comoving_prepare);
 }
 
 extern "C" int mcrat_hip_comoving_field(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_comoving_bins *bins, mcrat_hip_comoving *out)
 {
     if (!c || !bins || !out) return MCRAT_HIP_EINVAL;
-    if (c->is_pool) { c->last_error = "comoving_field: one list is a stand-alone context or a view of a pool (mcrat_hip_pool_comoving_field takes the pool)"; return MCRAT_HIP_ESTATE; }
-    if (c->have_photons) {
-        int rc = flush_pending(c);
-        if (rc) return rc;
-    }
-    return comoving_run(c, hydro, bins, c->have_photons ? c->ph.n : 0, out);
+    PhotonSource src;                            // (a context without photons goes on to the checks, then "no photons")
+    int rc = list_photons(c, 0.0, "comoving_field: one list is a stand-alone context or a view of a pool (mcrat_hip_pool_comoving_field takes the pool)", true, &src);
+    return rc ? rc : comoving_run(c, hydro, bins, src.n_slots, out);
 }
 
 extern "C" int mcrat_hip_pool_comoving_field(mcrat_hip_ctx *c, const mcrat_hip_ctx *hydro, const mcrat_hip_comoving_bins *bins, mcrat_hip_comoving *out)
 {
     if (!c || !bins || !out) return MCRAT_HIP_EINVAL;
-    if (!c->is_pool) { c->last_error = "pool_comoving_field: the context is no rank pool"; return MCRAT_HIP_ESTATE; }
-    // every slot of the pool, as mcrat_hip_pool_radiation_field reads them (a selected capture included)
-    int rc = flush_pending(c);
-    if (rc) return rc;
-    return comoving_run(c, hydro, bins, c->ph.n, out);
+    PhotonSource src;
+    int rc = pool_photons(c, nullptr, "pool_comoving_field: the context is no rank pool", &src);
+    if (!rc) rc = flush_pending(c);              // (unlike the observers' pool calls)
+    return rc ? rc : comoving_run(c, hydro, bins, src.n_slots, out);
 }
 
 extern "C" int mcrat_hip_comoving_field_path(const mcrat_hip_ctx *c) { return c ? c->cf_path : 0; }

@@ -1410,16 +1410,22 @@ class Engine:
         self._check(self.lib.mcrat_hip_avg_energy(self.ctx, C.byref(e)), "avg_energy")
         return e.value
 
+    def _pool_clocks(self, what, time_now):
+        """time_now of a pool call, one clock per list, as the float64 array the ABI reads (the caller keeps it alive for the call)"""
+        tn = _f8(time_now).ravel()
+        if len(tn) != self.n_pool_ranks:
+            raise ValueError("%s: time_now needs one clock per rank of the pool" % what)
+        return tn
+
     @staticmethod
-    def _cube_result(shape, struct):
-        """the seven planes of an observation cube of `shape` (observer first) and the per-observer counters, zeroed, and the ABI's output
-        struct (Observation, SkyObservation) that points at them"""
-        res = {"count": np.zeros(shape, dtype=np.int64), "n_accepted": np.zeros(shape[0], dtype=np.int64), "n_outside": np.zeros(shape[0], dtype=np.int64)}
-        for k in ("w", "we", "i", "q", "u", "v"):
-            res[k] = np.zeros(shape)
+    def _cube_result(shape, struct, sums=("w", "we", "i", "q", "u", "v"), counters=("n_accepted", "n_outside")):
+        """the count plane and the `sums` planes of a product's cube of `shape` (with counters: observer first) and the per-observer `counters`,
+        zeroed, and the ABI's output struct (Observation, SkyObservation, EscapeObservation, ..., Radfield, Comoving) that points at them"""
+        res = {"count": np.zeros(shape, dtype=np.int64)}
+        res.update({k: np.zeros(shape) for k in sums})
+        res.update({k: np.zeros(shape[0], dtype=np.int64) for k in counters})
         ll = C.POINTER(C.c_longlong)
-        return res, struct(res["count"].ctypes.data_as(ll), *[res[k].ctypes.data_as(_dp) for k in ("w", "we", "i", "q", "u", "v")],
-                           res["n_accepted"].ctypes.data_as(ll), res["n_outside"].ctypes.data_as(ll))
+        return res, struct(res["count"].ctypes.data_as(ll), *([res[k].ctypes.data_as(_dp) for k in sums] + [res[k].ctypes.data_as(ll) for k in counters]))
 
     # ---- mock observations: the resident photons binned by observer, detection time and energy (include/mcrat_hip.h)
     def _observe(self, call, what, cos_obs, sin_obs, cos_lo, cos_hi, t_edges, e_edges, time_now):
@@ -1440,9 +1446,7 @@ class Engine:
 
     def pool_observe(self, cos_obs, sin_obs, cos_lo, cos_hi, t_edges, e_edges, time_now):
         """every list of the pool in one launch, list r at its own clock time_now[r] (mcrat_hip_pool_observe)"""
-        tn = _f8(time_now).ravel()
-        if len(tn) != self.n_pool_ranks:
-            raise ValueError("pool_observe: time_now needs one clock per rank of the pool")
+        tn = self._pool_clocks("pool_observe", time_now)
         return self._observe(self.lib.mcrat_hip_pool_observe, "pool_observe", cos_obs, sin_obs, cos_lo, cos_hi, t_edges, e_edges, tn.ctypes.data_as(_dp))
 
     def observe_path(self):
@@ -1495,9 +1499,7 @@ class Engine:
 
     def pool_observe_sky(self, n, cos_acc, t_edges, e_edges, time_now, ex=None, ey=None, x_edges=None, y_edges=None):
         """every list of the pool in one launch, list r at its own clock time_now[r] (mcrat_hip_pool_observe_sky)"""
-        tn = _f8(time_now).ravel()
-        if len(tn) != self.n_pool_ranks:
-            raise ValueError("pool_observe_sky: time_now needs one clock per rank of the pool")
+        tn = self._pool_clocks("pool_observe_sky", time_now)
         return self._observe_sky(self.lib.mcrat_hip_pool_observe_sky, "pool_observe_sky", n, cos_acc, t_edges, e_edges, tn.ctypes.data_as(_dp), ex, ey,
                                  x_edges, y_edges)
 
@@ -1512,15 +1514,7 @@ class Engine:
         tau = _f8(tau_edges).ravel()
         n_tau = len(tau) - 1
         obs = EscapeObserver(sky, n_tau, tau.ctypes.data_as(_dp), SightlineParams(float(step_frac), float(h_min), int(max_steps), float(tau_stop), -1.0))
-        shape = (sky_shape[0], max(n_tau, 0)) + sky_shape[1:]
-        res = {"count": np.zeros(shape, dtype=np.int64)}
-        for k in ESCAPE_SUMS:
-            res[k] = np.zeros(shape)
-        for k in ESCAPE_COUNTERS:
-            res[k] = np.zeros(shape[0], dtype=np.int64)
-        ll = C.POINTER(C.c_longlong)
-        out = EscapeObservation(res["count"].ctypes.data_as(ll), *([res[k].ctypes.data_as(_dp) for k in ESCAPE_SUMS] +
-                                                                     [res[k].ctypes.data_as(ll) for k in ESCAPE_COUNTERS]))
+        res, out = self._cube_result((sky_shape[0], max(n_tau, 0)) + sky_shape[1:], EscapeObservation, ESCAPE_SUMS, ESCAPE_COUNTERS)
         self._check(call(self.ctx, hydro.ctx if hydro is not None else None, C.byref(obs), time_now, C.byref(out)), what)
         res.update(n_observable=int(out.n_observable), n_selected=int(out.n_selected), n_status=np.array(list(out.n_status), dtype=np.int64))
         return res
@@ -1538,9 +1532,7 @@ class Engine:
     def pool_observe_escaping(self, n, cos_acc, t_edges, e_edges, tau_edges, time_now, step_frac, h_min, max_steps, tau_stop=np.inf, hydro=None, ex=None,
                               ey=None, x_edges=None, y_edges=None):
         """every list of the pool at once, list r at its own clock time_now[r] (mcrat_hip_pool_observe_escaping)"""
-        tn = _f8(time_now).ravel()
-        if len(tn) != self.n_pool_ranks:
-            raise ValueError("pool_observe_escaping: time_now needs one clock per rank of the pool")
+        tn = self._pool_clocks("pool_observe_escaping", time_now)
         return self._observe_escaping(self.lib.mcrat_hip_pool_observe_escaping, "pool_observe_escaping", n, cos_acc, t_edges, e_edges, tau_edges,
                                       tn.ctypes.data_as(_dp), step_frac, h_min, max_steps, tau_stop, hydro, ex, ey, x_edges, y_edges)
 
@@ -1552,15 +1544,7 @@ class Engine:
     def _observe_sky_resampled(self, call, what, n, cos_acc, t_edges, e_edges, time_now, mode, n_rep, stokes_frame, seed, ex, ey, x_edges, y_edges):
         sky, _alive, sky_shape, _ = self._sky_observer(what, n, cos_acc, t_edges, e_edges, ex, ey, x_edges, y_edges)
         obs = ResampleObserver(sky, int(mode), int(n_rep), int(stokes_frame), int(seed) & 0xFFFFFFFFFFFFFFFF)
-        shape = (sky_shape[0], max(int(n_rep), 0)) + sky_shape[1:]
-        res = {"count": np.zeros(shape, dtype=np.int64)}
-        for k in ("w", "we", "i", "q", "u", "v"):
-            res[k] = np.zeros(shape)
-        for k in RESAMPLE_COUNTERS:
-            res[k] = np.zeros(shape[0], dtype=np.int64)
-        ll = C.POINTER(C.c_longlong)
-        out = ResampleObservation(res["count"].ctypes.data_as(ll), *([res[k].ctypes.data_as(_dp) for k in ("w", "we", "i", "q", "u", "v")] +
-                                                                       [res[k].ctypes.data_as(ll) for k in RESAMPLE_COUNTERS]))
+        res, out = self._cube_result((sky_shape[0], max(int(n_rep), 0)) + sky_shape[1:], ResampleObservation, counters=RESAMPLE_COUNTERS)
         self._check(call(self.ctx, C.byref(obs), time_now, C.byref(out)), what)
         return res
 
@@ -1577,9 +1561,7 @@ class Engine:
     def pool_observe_sky_resampled(self, n, cos_acc, t_edges, e_edges, time_now, mode=RESAMPLE_JACKKNIFE, n_rep=32, stokes_frame=STOKES_AS_STORED, seed=0,
                                    ex=None, ey=None, x_edges=None, y_edges=None):
         """every list of the pool in one launch, list r at its own clock time_now[r] (mcrat_hip_pool_observe_sky_resampled)"""
-        tn = _f8(time_now).ravel()
-        if len(tn) != self.n_pool_ranks:
-            raise ValueError("pool_observe_sky_resampled: time_now needs one clock per rank of the pool")
+        tn = self._pool_clocks("pool_observe_sky_resampled", time_now)
         return self._observe_sky_resampled(self.lib.mcrat_hip_pool_observe_sky_resampled, "pool_observe_sky_resampled", n, cos_acc, t_edges, e_edges,
                                            tn.ctypes.data_as(_dp), mode, n_rep, stokes_frame, seed, ex, ey, x_edges, y_edges)
 
@@ -1651,9 +1633,7 @@ class Engine:
     def pool_observe_events(self, n, cos_acc, time_now, order=EVENTS_BY_TIME, stokes_frame=STOKES_AS_STORED, ex=None, ey=None, t_window=None, e_window=None,
                             capacity=None):
         """every list of the pool as one event list, list r at its own clock time_now[r] (mcrat_hip_pool_observe_events)"""
-        tn = _f8(time_now).ravel()
-        if len(tn) != self.n_pool_ranks:
-            raise ValueError("pool_observe_events: time_now needs one clock per rank of the pool")
+        tn = self._pool_clocks("pool_observe_events", time_now)
         return self._observe_events(self.lib.mcrat_hip_pool_observe_events, "pool_observe_events", n, cos_acc, tn.ctypes.data_as(_dp), order, stokes_frame, ex, ey,
                                     t_window, e_window, capacity)
 
@@ -1741,10 +1721,7 @@ class Engine:
         n_bins = C.c_int(0)
         self._check(self.lib.mcrat_hip_radiation_field_bins(self.ctx, h, C.byref(bins), C.byref(n_bins)), what)
         shape = (n_r, n_mu) if int(mode) == RADFIELD_SHELLS else (n_bins.value,)
-        res = {"count": np.zeros(shape, dtype=np.int64)}
-        for k in RADFIELD_PLANES:
-            res[k] = np.zeros(shape)
-        out = Radfield(res["count"].ctypes.data_as(C.POINTER(C.c_longlong)), *[res[k].ctypes.data_as(_dp) for k in RADFIELD_PLANES])
+        res, out = self._cube_result(shape, Radfield, RADFIELD_PLANES, ())
         self._check(call(self.ctx, h, C.byref(bins), C.byref(out)), what)
         res.update(n_observable=int(out.n_observable), n_unlocated=int(out.n_unlocated), n_outside=int(out.n_outside))
         return res
@@ -1774,10 +1751,7 @@ class Engine:
         self._check(self.lib.mcrat_hip_comoving_field_bins(self.ctx, h, C.byref(bins), C.byref(n_bins)), what)
         per_s = n_ax[2] * n_ax[3]
         shape = (n_ax[0], n_ax[1], n_ax[2], n_ax[3]) if int(mode) == COMOVING_SHELLS else (n_bins.value // per_s, n_ax[2], n_ax[3])
-        res = {"count": np.zeros(shape, dtype=np.int64)}
-        for k in COMOVING_PLANES:
-            res[k] = np.zeros(shape)
-        out = Comoving(res["count"].ctypes.data_as(C.POINTER(C.c_longlong)), *[res[k].ctypes.data_as(_dp) for k in COMOVING_PLANES])
+        res, out = self._cube_result(shape, Comoving, COMOVING_PLANES, ())
         self._check(call(self.ctx, h, C.byref(bins), C.byref(out)), what)
         res.update(n_observable=int(out.n_observable), n_unlocated=int(out.n_unlocated), n_outside=int(out.n_outside))
         return res
